@@ -15,7 +15,9 @@ nothing is enqueued ahead of the pass-1 read-back (bdx_set_enqueue_ahead mode 0)
 previous run of the same input (mode 2) or from a prior on the read count (mode 1) are reported as untimed extras.  With N > 1 every rank owns its own chromosome
 (the path shards by chromosome, no data-path collective), so scaling is weak and `value` is the aggregate.
 
-One JSON line on rank 0; see the task contract for the fields.
+One JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run does only what the line's headline needs: it sets up,
+warms up, times the K steps (`ms_per_step` = one of them) and prints the line.  --full adds every other figure below (and, for
+N = 1, the genome leg); --dump-outputs DIR writes the last timed step's results as .npy files.
   roofline      dominant kernel (K1, the streaming classifier): algorithmic bytes = 28 B/read x reads per
                 launch / the kernel's average duration measured with HIP events on the context's stream during the timed
                 steps (bdx_get_timings; the kernel is bracketed on every 4th step, an event pair idles the GPU ~10 us).
@@ -44,6 +46,7 @@ ALGO_BYTES_PER_READ = 28          # 27 B SoA record read + 1 B class byte writte
 HBM_PEAK_GBS = 8000.0             # MI355X HBM3E spec (MI355X_MICROARCH.md)
 PATH_BYTES_PER_PAIR = 57.3        # whole path, per read pair, at 1 % discordant pairs
 CHROM_LEN = 50_000_000
+FEED_PROBE_PROCESSES = 2          # processes the eight feeders of the shared-host feed figure run in (each bdx-feed-probe opens the GPU)
 CFG_LINE = "readgroup:rg1\tplatform:illumina\tmap:%s\treadlen:100.00\tlib:lib1\tlower:310.00\tupper:490.00\tmean:400.00\tstd:30.00\n"
 
 
@@ -80,7 +83,17 @@ def parse():
                     help="contexts in flight per GPU (each with its own host thread and HIP stream, all reading the same resident "
                          "input); the default 1 is the plain sequence of steps the roofline figures refer to")
     ap.add_argument("--cpu-worker", nargs=2, metavar=("BAM", "PASSES"), help=argparse.SUPPRESS)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: enqueue-ahead modes, per-stage timings, the genome leg's "
+                         "other runs, three contexts in flight, the PMC traffic sub-runs, the end-to-end timings and the CPU baseline "
+                         "(default: set up, warm up, time the K steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (summary, SV table, region table, a seeded sample "
+                         "of the read classes) as DIR/<name>.npy in float32 / float64, for comparing two builds output for output")
+    a = ap.parse_args()
+    if a.steps < 1 and not a.dry and not a.cpu_worker:
+        ap.error("--steps must be >= 1")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -437,18 +450,22 @@ def time_bam_cli_genome(fraction, n_gpu_visible, realistic=False):
         except Exception as e:  # noqa: BLE001
             ceil["feed"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
         if not realistic:
-            # the feed when EIGHT GPUs' feeders share this host (tools/feed_scaling.py, profiles/r06_feed_scaling.txt): 8 concurrent probes with the
-            # usable CPUs divided between them; the leg that a node shares is page cache -> pinned (host memory bandwidth and cores)
+            # the feed when EIGHT GPUs' feeders share this host (tools/feed_scaling.py, profiles/r06_feed_scaling.txt): eight feeders' reader
+            # threads at once, an eighth of the usable CPUs each; the leg that a node shares is page cache -> pinned (host memory bandwidth and
+            # cores).  Every bdx-feed-probe process opens the GPU, so the eight feeders run in FEED_PROBE_PROCESSES processes, not eight: the
+            # same threads and bytes compete for the host, and one feeder's share is the aggregate / 8.
             try:
-                k = 8
-                t = max(1, min(usable_cpus(), 16) // k)
-                ps = [subprocess.Popen([os.path.join(ROOT, "bin", "bdx-feed-probe"), bam, "2", str(t), "12", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE) for _ in range(k)]
+                k, per = FEED_PROBE_PROCESSES, 8 // FEED_PROBE_PROCESSES
+                t = max(1, min(usable_cpus(), 16) // 8)
+                ps = [subprocess.Popen([os.path.join(ROOT, "bin", "bdx-feed-probe"), bam, str(2 * per), str(t * per), "12", "1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+                      for _ in range(k)]
                 outs = [json.loads(p.communicate(timeout=180)[0].decode().strip().splitlines()[-1]) for p in ps]
                 host = [o["page_cache_to_pinned_gb_s"] for o in outs]
-                ceil["feed_with_8_feeders_on_this_host"] = {"instances": k, "threads_per_instance": t, "usable_cpus": usable_cpus(),
-                                                            "page_cache_to_pinned_gb_s_per_instance": sum(host) / k, "aggregate_gb_s": sum(host),
-                                                            "note": "8 concurrent bdx-feed-probe instances (mmap + memcpy into pinned staging): what each of eight GPUs' feeders "
-                                                                    "gets of this host; the inflate kernel takes 44 GB/s of this file per GPU, 30 of a level-6 file"}
+                ceil["feed_with_8_feeders_on_this_host"] = {"instances": 8, "threads_per_instance": t, "processes": k, "usable_cpus": usable_cpus(),
+                                                            "page_cache_to_pinned_gb_s_per_instance": sum(host) / 8, "aggregate_gb_s": sum(host),
+                                                            "note": "8 feeders' reader threads at once (mmap + memcpy into pinned staging, %d threads each, in %d bdx-feed-probe "
+                                                                    "processes of %d feeders): what each of eight GPUs' feeders gets of this host; the inflate kernel takes "
+                                                                    "44 GB/s of this file per GPU, 30 of a level-6 file" % (t, k, per)}
             except Exception as e:  # noqa: BLE001
                 ceil["feed_with_8_feeders_on_this_host"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
         try:
@@ -603,7 +620,7 @@ GENOME_FRACTION = 1.0 / 8
 LIBS4 = ((400.0, 30.0), (350.0, 40.0), (500.0, 50.0), (300.0, 25.0))
 
 
-def genome_leg(rank, world, local, dist, out, fraction=None, translocations=5000, steps=0, warmup=0):
+def genome_leg(rank, world, local, dist, out, fraction=None, translocations=5000, steps=0, warmup=0, full=True, dump_dir=None):
     """configs[2] and configs[3] as ONE sharded run each over the N ranks of this launch: hg38-shaped genome, 4 libraries, 30x,
     chromosomes dealt to the ranks by bdx_dist_plan (longest processing time first, on sequence length); every rank synthesises
     and loads its own chromosomes, then all call bdx_dist_run (csrc/bdx_dist_impl.h: one launch sequence per rank over all of its
@@ -611,7 +628,9 @@ def genome_leg(rank, world, local, dist, out, fraction=None, translocations=5000
     components walked where they live, rank 0 walks what spans ranks and merges the ranks' tables).  Timed between barriers, max
     over ranks.  Sizes: `weak` = hg38 x N/8, i.e. 116 M records per GPU at every N and the whole genome of configs[2] / [3] at N = 8;
     `strong` (N > 1) = the fixed hg38 x 1/8 spread over the N ranks.  At N = 1 the same records also go through ONE context
-    (bdx_run): `single_context`, the figure the sharded run is measured against.  Fills `out` on rank 0."""
+    (bdx_run): `single_context`, the figure the sharded run is measured against.  Fills `out` on rank 0.  full=False (a plain N > 1
+    run): only what the line's value needs -- the weak size with the default options; dump_dir: rank 0 writes the result of the last
+    timed step of the weak size -- the line's value -- there (dump_outputs)."""
     import torch
     from breakdancer_amd import dist as D
     from breakdancer_amd.api import LibraryConfig, Options
@@ -660,7 +679,8 @@ def genome_leg(rank, world, local, dist, out, fraction=None, translocations=5000
             per_rank = allsum(per_rank)
         total = sum(per_rank)
         legs = {}
-        for label, opts in (("default_options", Options()), ("t_option", Options(transchr_rearrange=True))):
+        variants = [("default_options", Options())] + ([("t_option", Options(transchr_rearrange=True))] if full else [])
+        for label, opts in variants:
             if threads_backend and rank != 0:
                 continue
             if threads_backend:
@@ -726,6 +746,8 @@ def genome_leg(rank, world, local, dist, out, fraction=None, translocations=5000
                     barrier()
                     timed = allmax(time.perf_counter() - t0)
                     res = ranks[0].result()
+                if dump_dir and rank == 0 and scaling == "weak":   # (the size whose timed steps are the line's value)
+                    dump_outputs(res, dump_dir, reads=False)
             gc.enable()
             for run in ranks:
                 run.release_inputs()   # (the Python side's references to the loaded arrays: not part of the run)
@@ -870,7 +892,7 @@ def genome_leg(rank, world, local, dist, out, fraction=None, translocations=5000
 
     weak_frac = fraction if fraction is not None else world / 8.0
     sizes = [(weak_frac, "weak")]
-    if fraction is None and world > 1:
+    if fraction is None and world > 1 and full:
         sizes.append((GENOME_FRACTION, "strong"))
     results = [one_size(f, sc) for f, sc in sizes]
     if rank == 0:
@@ -881,6 +903,65 @@ def genome_leg(rank, world, local, dist, out, fraction=None, translocations=5000
                     **first})
         if len(results) > 1:
             out["strong_scaling_fixed_size"] = results[1]
+
+
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs in all; every table below has a budget of its own, larger ones are sampled by a fixed seed
+DUMP_TABLE_BYTES = {"sv": 16 << 20, "region": 16 << 20, "sv_lib": 4 << 20, "sv_cn": 4 << 20}
+READ_CLASS_SAMPLE = 1 << 20       # reads whose class --dump-outputs writes (a fixed, seeded sample: 12 MB with its index)
+
+
+def dump_outputs(bd, outdir, reads=True):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the summary counters, every column of the SV
+    table with its per-library and copy-number lists, the region table and (reads=True) the classes of a seeded sample of the reads --
+    as float64 .npy files (float32 for the read classes); `bd` is the context (or the sharded run's result).  A table larger than its
+    budget (DUMP_TABLE_BYTES, masks and index included) is written as a seeded sample of its rows with <table>_sample_index, so the
+    whole stays under DUMP_LIMIT_BYTES.  Every file holds finite numbers: a floating-point column also gets <name>_finite (1 where the
+    value is finite), and its other entries are written as 0 -- e.g. the allele frequency of an SV without normal reads between its
+    regions, NaN as in the reference.  .npy files an earlier run left in `outdir` are removed first."""
+    from breakdancer_amd import _lib as L
+    os.makedirs(outdir, exist_ok=True)
+    for f in os.listdir(outdir):
+        if f.endswith(".npy"):
+            os.remove(os.path.join(outdir, f))
+
+    def save(name, arr, dtype=np.float64):
+        arr = np.asarray(arr)
+        if arr.dtype.kind == "f":
+            fin = np.isfinite(arr)
+            np.save(os.path.join(outdir, name + "_finite.npy"), np.ascontiguousarray(fin, dtype=np.float64))
+            arr = np.where(fin, arr, 0)
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(arr, dtype=dtype))
+
+    def table(prefix, rec):
+        # bytes one row takes on disk: 8 per value, 8 more per floating-point value (its mask), 8 for the sample index
+        row = 8 + sum(8 * int(np.prod(rec.dtype[f].shape)) * (2 if rec.dtype[f].base.kind == "f" else 1) for f in rec.dtype.names)
+        keep = np.arange(len(rec))
+        if len(rec) * row > DUMP_TABLE_BYTES[prefix]:
+            keep = np.sort(np.random.default_rng(7).choice(len(rec), DUMP_TABLE_BYTES[prefix] // row, replace=False))
+            save(prefix + "_sample_index", keep)
+        for f in rec.dtype.names:
+            save(prefix + "_" + f, rec[f][keep])
+
+    def pairs(names, a, b):
+        rec = np.zeros(len(a), dtype=[(names[0], a.dtype), (names[1], b.dtype)])
+        rec[names[0]], rec[names[1]] = a, b
+        return rec
+
+    s = bd.summary()
+    save("summary", [s[k] for k, _ in L.bdx_summary._fields_])
+    svs, (lib_index, lib_pairs), (cn_key, cn_value) = bd.svs()
+    table("sv", svs)
+    table("sv_lib", pairs(("index", "pairs"), lib_index, lib_pairs))
+    table("sv_cn", pairs(("key", "value"), cn_key, cn_value))
+    if reads:
+        table("region", bd.regions())
+        n = int(s["n_reads"])
+        idx = np.sort(np.random.default_rng(5).choice(n, min(n, READ_CLASS_SAMPLE), replace=False))
+        save("read_class_sample_index", idx)
+        save("read_class_sample", bd.read_class()[idx], np.float32)
+    total = sum(os.path.getsize(os.path.join(outdir, f)) for f in os.listdir(outdir) if f.endswith(".npy"))
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs wrote %d bytes, more than %d" % (total, DUMP_LIMIT_BYTES))
 
 
 _LINE_FD = None
@@ -990,46 +1071,52 @@ def main():
             t.join()
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and world == 1:   # (N > 1: the line's timed path is the sharded run, dumped by genome_leg)
+        dump_outputs(bd, a.dump_outputs)
     summary = bd.summary()
     split = bd.walk_split() + (bd.cross_window_svs(),)
 
-    # ---- untimed extras ---------------------------------------------------------------------------------------------
-    # repeated runs of one context with enqueue-ahead (the later stages sized from the previous run's counts)
-    rsteps = max(10, a.steps // 4)
-    other_ms = {}
-    for mode in (2, 1):
-        bd.set_enqueue_ahead(mode)
+    # ---- untimed extras (--full) --------------------------------------------------------------------------------------
+    if a.full:
+        # repeated runs of one context with enqueue-ahead (the later stages sized from the previous run's counts)
+        rsteps = max(10, a.steps // 4)
+        other_ms = {}
+        for mode in (2, 1):
+            bd.set_enqueue_ahead(mode)
+            for _ in range(3):
+                bd.run()
+            torch.cuda.synchronize()
+            tr = time.perf_counter()
+            for _ in range(rsteps):
+                bd.run()
+            torch.cuda.synchronize()
+            other_ms[mode] = (time.perf_counter() - tr) / rsteps * 1e3
+        repeat_ms = other_ms[2]
+        bd.set_enqueue_ahead(0)
+        # per-stage device timings need HIP events between the stages, which idle the GPU: three extra steps
+        bd.set_stage_timing(True)
+        stage = {}
         for _ in range(3):
             bd.run()
-        torch.cuda.synchronize()
-        tr = time.perf_counter()
-        for _ in range(rsteps):
-            bd.run()
-        torch.cuda.synchronize()
-        other_ms[mode] = (time.perf_counter() - tr) / rsteps * 1e3
-    repeat_ms = other_ms[2]
-    bd.set_enqueue_ahead(0)
-    # per-stage device timings need HIP events between the stages, which idle the GPU: three extra steps
-    bd.set_stage_timing(True)
-    stage = {}
-    for _ in range(3):
-        bd.run()
-        for k, v in bd.timings().items():
-            stage[k] = stage.get(k, 0.0) + v
-    bd.set_stage_timing(False)
+            for k, v in bd.timings().items():
+                stage[k] = stage.get(k, 0.0) + v
+        bd.set_stage_timing(False)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=torch.device("cpu") if SHARED_GPU_TEST else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # The sharded whole-genome runs (config.genome): timed by their own barriers, outside the K timed steps above.  They run on a
-    # helper thread under a watchdog: whatever happens to them -- RCCL with more than one rank runs here first -- the line is printed.
+    # The sharded whole-genome runs (config.genome): timed by their own barriers, outside the K timed steps above (N > 1: the line's
+    # value; N = 1: --full only).  They run on a helper thread under a watchdog: whatever happens to them -- RCCL with more than one
+    # rank runs here first -- the line is printed.
     exchange, exchange_hung = {}, False
-    if not a.no_exchange and not a.pmc_child:
+    run_genome = not a.no_exchange and not a.pmc_child and (a.full or world > 1)
+    if run_genome:
         import threading
 
         def guarded():
             try:
-                genome_leg(rank, world, local, dist, exchange, fraction=a.genome_fraction, steps=a.steps if world > 1 else 0, warmup=a.warmup)
+                genome_leg(rank, world, local, dist, exchange, fraction=a.genome_fraction, steps=a.steps if world > 1 else 0, warmup=a.warmup,
+                           full=a.full, dump_dir=a.dump_outputs if world > 1 else None)
             except Exception as e:  # noqa: BLE001
                 exchange["error"] = "%s: %s" % (type(e).__name__, str(e)[:300])
         th = threading.Thread(target=guarded, daemon=True)
@@ -1051,7 +1138,7 @@ def main():
             hung_any = bool(int(flag.item()))
         except Exception:  # noqa: BLE001
             hung_any = True
-    if world > 1 and not a.no_end_to_end and not a.no_sharded_cli and not a.pmc_child and not hung_any:
+    if world > 1 and a.full and not a.no_end_to_end and not a.no_sharded_cli and not a.pmc_child and not hung_any:
         if rank == 0:
             try:
                 with tempfile.TemporaryDirectory(prefix="bdx_bench_sh_") as td_sh:
@@ -1063,7 +1150,7 @@ def main():
     # (behind the genome runs: two dozen contexts created, run and released leave the process in a state in which rank 0's part of a
     # sharded run -- its first, with all its allocations -- took three times as long)
     overlapped = None
-    if world == 1 and len(ctxs) == 1 and not a.pmc_child and not a.no_overlap:   # (by default: three contexts in flight is how a whole-genome caller keeps one GPU busy)
+    if world == 1 and len(ctxs) == 1 and a.full and not a.pmc_child and not a.no_overlap:   # (three contexts in flight is how a whole-genome caller keeps one GPU busy)
         # the native driver (bdx_run_many): 24 contexts -- one per chromosome of a genome, here all on the same resident input --
         # of which three are in flight at a time
         from breakdancer_amd.api import run_many
@@ -1087,7 +1174,7 @@ def main():
         k1_avg_ms = float(np.mean(k1_ms))
         achieved = ALGO_BYTES_PER_READ * n / (k1_avg_ms * 1e-3) / 1e9
         traffic, traffic_note, traffic_detail = None, None, None
-        if world == 1 and not a.no_pmc and not a.pmc_child:
+        if world == 1 and a.full and not a.no_pmc and not a.pmc_child:
             traffic_detail, traffic_note = measure_k1_traffic(a.length)
             if traffic_detail:
                 traffic = traffic_detail["hbm_bytes_per_launch"]
@@ -1097,7 +1184,7 @@ def main():
         cpu = None
         if sharded_cli is not None:
             timings["bam_to_table_sharded"] = sharded_cli
-        if world == 1 and not (a.no_end_to_end and a.no_cpu_baseline):
+        if world == 1 and a.full and not (a.no_end_to_end and a.no_cpu_baseline):
             from breakdancer_amd.bamwrite import write_bam
             with tempfile.TemporaryDirectory(prefix="bdx_bench_") as td:
                 if not a.no_end_to_end:
@@ -1142,19 +1229,12 @@ def main():
                                    "record back and sizes the later stages exactly (no enqueue-ahead)" % (a.length // 1000000, pairs, n),
                        "sharding": "one chromosome per GPU, no data-path collective", "contexts_in_flight": n_ctxs_timed,
                        "svs_per_gpu": summary["n_svs_printed"],
-                       "timings": timings,
-                       "repeat_run_enqueue_ahead": {"ms_per_step": repeat_ms, "value": pairs / (repeat_ms * 1e-3), "unit": "read-pairs/s",
-                                                    "steps": rsteps, "note": "untimed extra: the same context re-running the same input, later stages "
-                                                                             "sized from the previous run's count (BENCH_r01's figure)"},
-                       "first_run_enqueue_ahead_on_prior": {"ms_per_step": other_ms[1], "value": pairs / (other_ms[1] * 1e-3), "unit": "read-pairs/s",
-                                                            "steps": rsteps, "note": "untimed extra: later stages enqueued ahead sized by a prior of n/32 "
-                                                                                     "anomalous reads (what a context's first run of an input does by default)"},
-                       "stage_ms_profiled_steps": {k: v / 3 for k, v in stage.items()},
+                       "timings": timings, "full": a.full,
                        "sv_candidates": dict(zip(("assembled_on_device", "from_host_walk", "groups_to_host_walk", "device_placed_by_order_key"), split))},
             "roofline": {"bound": "hbm", "kernel": "k1_classify_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_source": ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE sub-runs of this invocation (FETCH_SIZE x 2 on gfx950): %s" % json.dumps(traffic_detail)
-                                            if traffic_detail else "not measured: %s" % (traffic_note or "skipped (--no-pmc, N > 1)")),
+                                            if traffic_detail else "not measured: %s" % (traffic_note or ("skipped (--no-pmc, N > 1)" if a.full else "skipped (--full not given)"))),
                          "algorithmic_bytes_per_launch": ALGO_BYTES_PER_READ * n,
                          "avg_kernel_ms": k1_avg_ms,
                          # the same kernel by the bytes it really moves (PMC, `traffic`): fewer than the algorithmic figure, which
@@ -1168,6 +1248,15 @@ def main():
                                         "achieved": value / world * PATH_BYTES_PER_PAIR / 1e9,
                                         "frac": value / world * PATH_BYTES_PER_PAIR / 1e9 / HBM_PEAK_GBS}},
         }
+        if a.full:
+            out["config"].update({
+                "repeat_run_enqueue_ahead": {"ms_per_step": repeat_ms, "value": pairs / (repeat_ms * 1e-3), "unit": "read-pairs/s",
+                                             "steps": rsteps, "note": "untimed extra: the same context re-running the same input, later stages "
+                                                                      "sized from the previous run's count (BENCH_r01's figure)"},
+                "first_run_enqueue_ahead_on_prior": {"ms_per_step": other_ms[1], "value": pairs / (other_ms[1] * 1e-3), "unit": "read-pairs/s",
+                                                     "steps": rsteps, "note": "untimed extra: later stages enqueued ahead sized by a prior of n/32 "
+                                                                              "anomalous reads (what a context's first run of an input does by default)"},
+                "stage_ms_profiled_steps": {k: v / 3 for k, v in stage.items()}})
         ts = exchange.get("default_options", {}).get("timed_steps") if world > 1 else None
         if ts:
             # N > 1: the line is about the path that SHARDS -- configs[2], one whole-genome run over the N ranks (bdx_dist_run: chromosomes
@@ -1203,7 +1292,7 @@ def main():
                                  "source": "config.timings.bam_to_table_sharded"}
         if overlapped:
             out["config"]["overlapped_contexts"] = overlapped
-        if not a.no_exchange and not a.pmc_child:
+        if run_genome:
             out["config"]["genome"] = exchange
         if SHARED_GPU_TEST:
             out["config"]["test_hook"] = "BDX_BENCH_TEST_SHARED_GPU: all ranks on device 0, gloo process group -- not a measurement"

@@ -7,17 +7,18 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_two_ranks_print_one_aggregate_line():
+def test_two_ranks_print_one_aggregate_line(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["BDX_BENCH_TEST_SHARED_GPU"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--length", "6000000",
-                        "--genome-fraction", "0.004", "--sharded-cli-fraction", "0.002"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "8", "--warmup", "2", "--length", "6000000",
+                        "--genome-fraction", "0.004", "--sharded-cli-fraction", "0.002", "--dump-outputs", str(tmp_path / "out")],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [x for x in p.stdout.decode().splitlines() if x.startswith("{")]
@@ -49,13 +50,17 @@ def test_two_ranks_print_one_aggregate_line():
         assert "rank0_only" in x and 0 <= x["rank0_only"]["share_of_run"] <= 1 and "rank0_only_merge" in x["rank0_phase_ms"]
         assert sum(x["sv_candidates_device_host"]) > 0
     assert g["t_option"]["ctx_records_exchanged"] > 100   # (inter-chromosomal reads whose mates lie on a later chromosome of the other rank)
+    # --dump-outputs at N > 1: the sharded run's whole-genome result of the line's timed steps (summary and SV table)
+    files = {f.name[:-4]: np.load(f) for f in (tmp_path / "out").iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert int(files["summary"][9]) == g["default_options"]["svs_printed"] and files["sv_score"].shape == (int(files["summary"][8]),)
 
 
 def test_one_rank_line_carries_the_end_to_end_ratio_and_the_single_context_figure():
     """N = 1: vs_baseline = BAM -> table over the CPU baseline (like for like), the bam_to_table block's own figure is the one-process
     run, and the genome leg holds the single-context figure beside the sharded run"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--length", "4000000", "--genome-fraction", "0.004",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "8", "--warmup", "2", "--length", "4000000", "--genome-fraction", "0.004",
                         "--no-pmc", "--no-overlap", "--cpu-parallel", "0", "--sharded-cli-fraction", "0.002", "--genome-bam-fraction", "0.004"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     out = json.loads([x for x in p.stdout.decode().splitlines() if x.startswith("{")][0])
@@ -77,3 +82,37 @@ def test_one_rank_line_carries_the_end_to_end_ratio_and_the_single_context_figur
     assert "error" not in g, g
     assert g["ranks"] == 1 and g["single_context"]["seconds"] > 0 and g["default_options"]["svs_printed"] == g["single_context"]["svs_printed"]
     assert out["roofline"]["kernel"] == "k1_classify_kernel" and 0 < out["roofline"]["frac"] < 1
+
+
+def test_plain_run_times_k_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """N = 1 without --full: the line holds the headline figures of K timed steps and none of the extras; --dump-outputs writes the last
+    step's results as float .npy files, the same in two runs with the same arguments"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1", "--length", "4000000",
+                            "--dump-outputs", str(d)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines = [x for x in p.stdout.decode().splitlines() if x.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        pairs = 4_000_000 * 30 // 200
+        assert out["steps"] == 5 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["unit"] == "read-pairs/s" and out["higher_is_better"]
+        assert abs(out["value"] - pairs / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"] and out["dtype"] == "int32"
+        assert "cpu_baseline" not in out and "end_to_end" not in out and out["vs_baseline"] is None and out["roofline"]["traffic"] is None
+        assert not out["config"]["full"] and "genome" not in out["config"] and "overlapped_contexts" not in out["config"]
+        assert list(out["config"]["timings"]) == ["hbm_resident"]
+        files = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+        n_svs = int(files["summary"][8])
+        assert int(files["summary"][9]) == out["config"]["svs_per_gpu"] and n_svs >= out["config"]["svs_per_gpu"] > 0
+        assert files["sv_score"].shape == (n_svs,) and files["sv_pos"].shape == (n_svs, 2) and len(files["region_start"]) > 0
+        # (floating-point columns carry a finiteness mask: an SV without normal reads between its regions has no allele frequency)
+        assert files["sv_allele_frequency_finite"].shape == (n_svs,) and set(np.unique(files["sv_allele_frequency_finite"])) <= {0.0, 1.0}
+        assert len(files["read_class_sample"]) == len(files["read_class_sample_index"]) > 0
+        dumps.append(files)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
