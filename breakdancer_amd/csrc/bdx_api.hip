@@ -59,7 +59,6 @@ struct DevBuf {
 struct PinBuf {
     void* p = nullptr;
     size_t bytes = 0;
-    unsigned flags = hipHostMallocDefault;
     // A large buffer is anonymous memory on transparent huge pages, registered with the runtime (hipHostRegister): 0.02 s per 0.5 GB
     // against hipHostMalloc's 0.09-0.11 -- pinning is paid per page -- and a quarter less to hand back when the process ends
     // (tools/pin_probe.hip, profiles/r05_pin_probe.txt); the device sees it at the same address.  Small buffers -- the words the host
@@ -75,7 +74,7 @@ struct PinBuf {
         const auto t0 = std::chrono::steady_clock::now();
         hipError_t e = hipErrorOutOfMemory;
         constexpr size_t kHuge = (size_t)2 << 20;
-        if (want >= 2 * kHuge && flags == hipHostMallocDefault && use_registered()) {
+        if (want >= 2 * kHuge && use_registered()) {
             const size_t len = (want + kHuge - 1) & ~(kHuge - 1);
             void* base = mmap(nullptr, len + kHuge, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
             if (base != MAP_FAILED) {
@@ -93,7 +92,7 @@ struct PinBuf {
             }
         }
         if (e != hipSuccess) {
-            e = hipHostMalloc(&p, want, flags);
+            e = hipHostMalloc(&p, want, hipHostMallocDefault);
             // (small buffers hold the words the host polls and the counters kernels report: a block the allocator hands out again may still
             // hold another context's ready word -- the same sequence number -- and a poll would return before the kernel has run)
             if (e == hipSuccess && want <= ((size_t)1 << 20)) memset(p, 0, want);
@@ -111,8 +110,9 @@ struct PinBuf {
 };
 
 constexpr int kNumStages = 12;
-constexpr int kK1MaxGrid = 8192;  // measured best on MI355X (tools/k1_probe.hip; again at the end of round 2, BDX_K1_GRID: 2048 74.6 us, 4096 70.9,
+constexpr int kK1MaxGrid = 8192;  // measured best on MI355X (tools/k1_probe.hip; again at the end of round 2: 2048 74.6 us, 4096 70.9,
                                   // 8192 69.9, 12288 72.5, 16384 73.4): 256 CUs x 32 workgroups queued, 4 independent waves each
+constexpr uint32_t kK1EventPeriod = 4;  // K1 is bracketed by HIP events on every n-th run (an event pair idles the GPU ~10 us)
 
 }  // namespace
 
@@ -138,7 +138,7 @@ struct bdx_ctx {
     // stage buffers
     DevBuf b_libs, b_cls, b_tile_tot, b_tile_pre, b_tile_mono, b_blk_cnt, b_cnt, b_p1, b_fold, b_stash, b_chunk_tot;
     DevBuf b_c_tid, b_c_pos, b_c_isize, b_c_meta, b_c_key, b_c_check, b_c_idx, b_c_nn, b_c_pk;
-    DevBuf b_cand, b_pre_q, b_pre_rev, b_pre_nonctx, b_c_first, b_c_maxq, b_c_rid, b_region_of, b_ws_u4, b_ws_u32, b_totals, b_counts;
+    DevBuf b_cand, b_pre_q, b_pre_rev, b_pre_nonctx, b_c_first, b_c_maxq, b_c_rid, b_region_of, b_counts;
     DevBuf b_bcnt, b_boff, b_bcur, b_e_key, b_e_idx, b_partner, b_t_key, b_t_idx;
     DevBuf b_x_key, b_x_check, b_x_order, b_x_region, b_x_meta, b_x_isize, b_x_n;
     DevBuf b_lib_mean;
@@ -148,14 +148,11 @@ struct bdx_ctx {
     DevBuf b_sv_src, b_dlists, b_ltail, b_pair_lo;
     PinBuf h_hs_rec, h_hs_aux, h_hs_lists, h_printed;
     DevBuf b_ins, b_member_ids;
-    PinBuf h_flags;                   // [0] pass 1 ready, [1] host's groups ready, [2] final table ready (= run sequence number)
+    PinBuf h_flags;                   // [0] pass 1 ready, [1] host's groups ready, [2] final table ready, [3] region table ready (= run sequence number)
     uint32_t seq = 0;
     // test / measurement switches (bdx_set_debug): all off by default
-    int dbg_no_stash = 0, dbg_max_chunks = 0, dbg_finalize2_fold = 0, dbg_no_forward = 0, dbg_scan3 = 0, dbg_label_rounds = 0, dbg_k1_grid = 0,
-        dbg_end_write_value = 0, dbg_walk_lanes = 0, dbg_ins_plain = 0, dbg_gather_walk = 0, dbg_region_dma = 0, dbg_join_fwd = 0, dbg_regions_copy = 0, dbg_asm_plain = 0;
-    bool region_dma_now = false;      // this run's region table goes to the host by a copy command once the host knows its size (see bdx_run)
+    int dbg_no_stash = 0, dbg_max_chunks = 0, dbg_ins_plain = 0, dbg_gather_walk = 0, dbg_regions_copy = 0, dbg_asm_plain = 0;
     uint32_t lb_seq = 0;              // launches of look-back scans so far: every launch stamps its words with its own number (bdx_scan.h)
-    uint32_t k1_event_period = 4;     // K1 is bracketed by HIP events on every n-th run (an event pair idles the GPU ~10 us)
     float k1_ms_last = 0;
     bool k1_timed = false;
     bool stage_timing = false;        // HIP events around K2 / K3 / K4+K6 (each costs a few microseconds of idle GPU)
@@ -258,7 +255,7 @@ struct bdx_ctx {
     // keys was copied into the resident column
     struct KeySeg { uint64_t begin; const uint64_t* host; const uint16_t* host_qlen; const uint64_t* host_check; };
     std::vector<KeySeg> key_segs;
-    DevBuf b_seg, b_done, b_lb;
+    DevBuf b_seg, b_lb;
 };
 
 namespace {
@@ -511,7 +508,6 @@ void bdx_destroy(bdx_ctx* c) {
         if (st.done) (void)hipEventDestroy(st.done);
     }
     c->b_seg.release();
-    c->b_done.release();
     c->b_lb.release();
     if (c->ev_copy) (void)hipEventDestroy(c->ev_copy);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -519,7 +515,7 @@ void bdx_destroy(bdx_ctx* c) {
                       &c->b_bam, &c->b_key, &c->b_check, &c->b_c_check, &c->b_x_check, &c->b_groups, &c->b_libs, &c->b_cls, &c->b_stash, &c->b_chunk_tot, &c->b_tile_tot, &c->b_tile_pre, &c->b_tile_mono,
                       &c->b_blk_cnt, &c->b_cnt, &c->b_p1, &c->b_c_tid, &c->b_c_pos, &c->b_c_isize,
                       &c->b_c_meta, &c->b_c_key, &c->b_c_idx, &c->b_c_nn, &c->b_c_pk, &c->b_cand, &c->b_pre_q, &c->b_pre_rev,
-                      &c->b_pre_nonctx, &c->b_c_first, &c->b_c_maxq, &c->b_c_rid, &c->b_region_of, &c->b_ws_u4, &c->b_ws_u32, &c->b_totals,
+                      &c->b_pre_nonctx, &c->b_c_first, &c->b_c_maxq, &c->b_c_rid, &c->b_region_of,
                       &c->b_counts, &c->b_bcnt, &c->b_boff, &c->b_bcur, &c->b_e_key, &c->b_e_idx, &c->b_partner, &c->b_t_key,
                       &c->b_t_idx, &c->b_x_key, &c->b_x_order, &c->b_x_region,
                       &c->b_x_meta, &c->b_x_isize, &c->b_x_n, &c->b_fold, &c->b_lib_mean, &c->b_pair_lo, &c->b_sv_src, &c->b_dlists, &c->b_ltail, &c->b_r_rec, &c->b_r_pk, &c->b_out_deg,
@@ -733,8 +729,6 @@ int pass1_prepare(bdx_ctx* c, uint32_t tiles_cap) {
     add(c->b_blk_cnt.p, (size_t)kCntCopies * ncnt, 0u);
     add(c->b_p1.p, sizeof(Pass1) / 4, 0u);
     add(c->b_counts.p, sizeof(StageCounts) / 4, 0u);
-    HIPCHK(c, c->b_done.ensure(64));
-    add(c->b_done.p, 1, 0u);
     il.n = k;
     launch_init(il, s);
     return BDX_OK;
@@ -753,8 +747,7 @@ int pass1_classify(bdx_ctx* c, uint32_t upto, bool timed) {
     k1.blk_cnt = c->b_blk_cnt.as<uint32_t>();
     k1.stash = c->use_stash ? c->b_stash.as<StashRec>() : nullptr;
     const uint32_t span = upto - c->k1_done;
-    const uint32_t grid_cap = c->dbg_k1_grid > 0 ? (uint32_t)c->dbg_k1_grid : (uint32_t)kK1MaxGrid;  // (tuning probe)
-    const int grid1 = (int)std::min<uint32_t>((span + kWaves - 1) / kWaves, grid_cap);
+    const int grid1 = (int)std::min<uint32_t>((span + kWaves - 1) / kWaves, (uint32_t)kK1MaxGrid);
     launch_k1(k1, grid1, k1_lds_bytes(c->nlibs, c->nbams, c->nkeys), s, timed ? c->ev[0] : nullptr, timed ? c->ev[1] : nullptr);
     c->k1_done = upto;
     return BDX_OK;
@@ -789,7 +782,7 @@ int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second) {
     }
     c->k1_live = false;  // (consumed: a repeated run classifies everything again)
     const uint32_t tstride = c->tstride;
-    const bool time_k1 = (c->stage_timing || c->seq % c->k1_event_period == 0) && c->k1_done == 0 && ntiles > 0;
+    const bool time_k1 = (c->stage_timing || c->seq % kK1EventPeriod == 0) && c->k1_done == 0 && ntiles > 0;
     {
         const int rc = pass1_classify(c, ntiles, time_k1);
         if (rc != BDX_OK) return rc;
@@ -822,10 +815,6 @@ int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second) {
     ++c->seq;
     fp.flag_host = c->h_flags.as<uint32_t>(); fp.flag_value = c->seq;
     fp.na_cap = na_cap;
-    // The second level as the job of finalize_kernel's last workgroup (BDX_FINALIZE2_FOLD=1) was measured and lost: the
-    // device-scope fences it needs right behind K1's 15 MB of class bytes cost more (step 0.324 ms) than the launch (0.308 ms)
-    const bool fold = c->dbg_finalize2_fold != 0;
-    fp.done = fold ? c->b_done.as<uint32_t>() : nullptr;
     // enqueue-ahead: K2 follows without a host decision in between, so its launch takes the one-workgroup second level along
     c->fp_deferred = fp;
     c->finalize2_deferred = defer_second;
@@ -1031,10 +1020,6 @@ int do_cut(bdx_ctx* c, int has_next, int32_t next_qlen, uint32_t next_nn, bool f
             HIPCHK(c, c->h_regs.ensure(cap * sizeof(RegionRec)));
             HIPCHK(c, c->h_pk.ensure(cap * 2 * nkeys * 4));
         }
-        const size_t nblk = scan_grid(na, 1) + 1;  // (sized for one element per thread, the finest split the scans use)
-        HIPCHK(c, c->b_ws_u4.ensure(nblk * sizeof(U4)));
-        HIPCHK(c, c->b_ws_u32.ensure(nblk * 4));
-        HIPCHK(c, c->b_totals.ensure(64));
         k3.cap = na;
         k3.cand = c->b_cand.as<int32_t>(); k3.pre_q = c->b_pre_q.as<uint32_t>(); k3.pre_rev = c->b_pre_rev.as<uint32_t>();
         k3.pre_nonctx = c->b_pre_nonctx.as<uint32_t>(); k3.c_first = c->b_c_first.as<uint32_t>();
@@ -1046,12 +1031,10 @@ int do_cut(bdx_ctx* c, int has_next, int32_t next_qlen, uint32_t next_nn, bool f
             HIPCHK(c, c->b_out_deg.ensure(cap * 6 * 4));
             k3.r_rec_dev = c->b_r_rec.as<RegionRec>(); k3.r_pk_dev = c->b_r_pk.as<uint32_t>(); k3.out_deg = c->b_out_deg.as<uint32_t>();
             // with the direct join right behind K3, that kernel forwards the table to the host
-            const bool no_forward = c->dbg_no_forward != 0;
-            k3.host_copy_later = (!no_forward && !c->bucketed_join && na <= kDirectJoinMax) ? 1 : 0;
+            k3.host_copy_later = (!c->bucketed_join && na <= kDirectJoinMax) ? 1 : 0;
         }
-        const bool three_launch = c->dbg_scan3 != 0;  // (A/B: the block-sums / rescan pair of launches)
-        if (!three_launch) {
-            const size_t words = 5 * nblk;
+        {   // look-back words of the two scans, sized for one element per thread (the finest split they use)
+            const size_t words = 5 * (scan_grid(na, 1) + 1);
             if (c->b_lb.bytes < words * 8) {  // the look-back words must start out zero; afterwards every run brings its own stamp
                 HIPCHK(c, c->b_lb.ensure(words * 8));
                 HIPCHK(c, hipMemsetAsync(c->b_lb.p, 0, c->b_lb.bytes, s));
@@ -1059,8 +1042,7 @@ int do_cut(bdx_ctx* c, int has_next, int32_t next_qlen, uint32_t next_nn, bool f
             k3.lb_state = c->b_lb.as<unsigned long long>();
             if (!sz) HIPCHK(c, next_lb_stamp(c, &k3.lb_stamp));
         }
-        k3.ws_u4 = c->b_ws_u4.as<U4>(); k3.head_total = (U4*)c->b_totals.p; k3.ws_u32 = c->b_ws_u32.as<uint32_t>();
-        k3.acc_total = (uint32_t*)((char*)c->b_totals.p + 32); k3.counts = c->b_counts.as<StageCounts>();
+        k3.counts = c->b_counts.as<StageCounts>();
         if (for_k6) {
             HIPCHK(c, c->h_counts0.ensure(sizeof(StageCounts)));
             if (!sz) memset(c->h_counts0.p, 0, sizeof(StageCounts));
@@ -1193,7 +1175,8 @@ void decode_groups(bdx_ctx* c, const GroupRec* gr, uint32_t ng, uint32_t ph) {
 // K6 on the context's own regions (single-context runs): pair groups per region, SV assembly of the components that need
 // no traversal, everything else listed for the host walk; then the dense results and K5 for the device-assembled SVs.
 // part: 0 the whole first half; 1 up to and including k6_pairs_kernel, 2 the rest; 3 the deferred device walk; 4 the arrays and no launch
-int do_k6(bdx_ctx* c, bool force_host, int part = 0, const Sizing* sz = nullptr) {
+// rounds: min-label propagation rounds (0: kK6LabelRounds, or kK6LabelRoundsBig with the general walk)
+int do_k6(bdx_ctx* c, bool force_host, int part = 0, const Sizing* sz = nullptr, int rounds = 0) {
     hipStream_t s = c->stream;
     K6Arrays a_sz{};
     K6Arrays& a = sz ? a_sz : c->k6;
@@ -1315,16 +1298,12 @@ int do_k6(bdx_ctx* c, bool force_host, int part = 0, const Sizing* sz = nullptr)
     a.big_walk = big_walk;
     a.ins_plain = c->dbg_ins_plain;
     a.asm_plain = c->dbg_asm_plain;
-    a.walk_lanes = c->dbg_walk_lanes > 0 ? std::min(c->dbg_walk_lanes, 32) : 32;  // (measured at configs[1]: 64 regions per wave 23.7 us, 32: 22.4 us, 16: 24.5 us)
-    {
-        const int rounds = c->dbg_label_rounds;
-        // (long chains need more rounds to agree on one label; with the general walk on, the step is long enough not to care)
-        a.label_rounds = rounds ? rounds : (a.big_walk ? kK6LabelRoundsBig : kK6LabelRounds);
-    }
+    // (long chains need more rounds to agree on one label; with the general walk on, the step is long enough not to care)
+    a.propagation_rounds = rounds ? rounds : (a.big_walk ? kK6LabelRoundsBig : kK6LabelRounds);
     if (c->poll) {  // ready words set by the kernels themselves (first thread of k6_pairs_kernel / first wave of k6_walk_kernel)
         a.flag_value = c->seq;
         a.flag_groups = c->h_flags.as<uint32_t>() + 1;
-        if (c->k3.host_copy_later && !c->region_dma_now) a.flag_regions = c->h_flags.as<uint32_t>() + 3;
+        if (c->k3.host_copy_later) a.flag_regions = c->h_flags.as<uint32_t>() + 3;
         a.mirror_in_walk = (force_host || c->defer_walk) ? 0 : 1;  // (k6_walk_kernel follows k6_emit_kernel unless everything goes to the host, or the walk waits for the ranks' collectives)
     }
     if (part == 4) return BDX_OK;   // (the arrays only: rank 0 of a sharded run whose host walks the few gathered groups -- the table stage follows)
@@ -1416,8 +1395,7 @@ int do_k6_table(bdx_ctx* c) {
     // The word the host polls for the end of the run is set by a one-thread kernel behind the table kernel (a kernel boundary
     // orders it behind that kernel's stores to host memory).  A stream write-value command does the same as a one-thread kernel of
     // the runtime's own, but starts 5 us after the kernel before it has ended; back-to-back launches follow each other at once.
-    const bool write_value = c->dbg_end_write_value != 0;  // (A/B)
-    if (c->poll && !write_value) { a.flag_done = c->h_flags.as<uint32_t>() + 2; a.flag_value = c->seq; }
+    if (c->poll) { a.flag_done = c->h_flags.as<uint32_t>() + 2; a.flag_value = c->seq; }
     a.wire_rows = c->table_in_hbm ? 0 : 1;   // (a table that stays in HBM for rank 0's merge keeps its full rows)
     c->rows_packed = a.wire_rows != 0;
     launch_k6_table(a, na, std::log(10), c->opts.score_threshold, c->opts.fisher ? 0 : 1, s);
@@ -1688,7 +1666,6 @@ int bdx_run(bdx_ctx* c) {
     const bool force_host = c->host_walk_only || ph_opt || c->opts.min_read_pair < 1;
     // K2 .. K6 (first half) for c->na_alloc anomalous reads
     auto enqueue_middle = [&]() -> int {
-        c->region_dma_now = false;
         int r = do_compact(c, 0, nullptr, true);
         if (r != BDX_OK) return r;
         r = do_cut(c, 0, 0, 0, true);
@@ -1702,14 +1679,9 @@ int bdx_run(bdx_ctx* c) {
             en.k6_scratch = c->k3.out_deg; en.scratch_cap = c->k3.cap;
             // (the join kernel forwards the region table to pinned host memory.  A kernel of its own on the copy stream, beside the join, was
             // measured in round 6: 1.525 against 1.530 ms at a genome share -- the join does not wait for those 5.7 MB; profiles/r06_genome_ab.txt)
-            c->region_dma_now = c->k3.host_copy_later && c->poll && c->dbg_region_dma != 0;
-            if (c->region_dma_now) {
-                // (the join kernel only says that K3 is through: the host reads the region count and has the copy engine fetch the table)
-                en.flag_host = c->h_flags.as<uint32_t>() + 4; en.flag_value = c->seq;
-            } else if (c->k3.host_copy_later) {
+            if (c->k3.host_copy_later) {
                 en.r_rec_dev = c->k3.r_rec_dev; en.r_pk_dev = c->k3.r_pk_dev; en.r_rec_host = c->k3.r_rec; en.r_pk_host = c->k3.r_pk;
                 en.counts = c->b_counts.as<StageCounts>(); en.nkeys2 = 2 * c->nkeys;
-                en.fwd_blocks = c->dbg_join_fwd < 0 ? 0xFFFFFFFFu : (uint32_t)c->dbg_join_fwd;
             }
         }
         r = do_join_local(c, c->na_alloc, en, &c->b_p1.as<Pass1>()->n_anom, true);
@@ -1786,24 +1758,11 @@ int bdx_run(bdx_ctx* c) {
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[5], s));
     const auto t_h0 = std::chrono::steady_clock::now();
     auto t_h1 = t_h0;
-    if (na && c->region_dma_now) {
-        if (!wait_flag(c, 4, c->seq)) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            if (!flag_arrived(c, 4)) return fail(c, BDX_EINTERNAL, "the region count did not arrive: its kernels were not launched");
-        }
-        const size_t nr = c->h_counts0.as<StageCounts>()->n_regions;
-        if (nr) {
-            HIPCHK(c, hipMemcpyAsync(c->h_regs.p, c->b_r_rec.p, nr * sizeof(RegionRec), hipMemcpyDeviceToHost, c->copy_stream));
-            if (c->nkeys) HIPCHK(c, hipMemcpyAsync(c->h_pk.p, c->b_r_pk.p, nr * 2 * (size_t)c->nkeys * 4, hipMemcpyDeviceToHost, c->copy_stream));
-        }
-        HIPCHK(c, hipStreamSynchronize(c->copy_stream));
-    } else if (na) {
+    if (na) {
         if (!wait_flag(c, 3, c->seq)) {
             if (c->poll) HIPCHK(c, hipStreamSynchronize(s)); else HIPCHK(c, hipEventSynchronize(c->ev_regions));
             if (!flag_arrived(c, 3)) return fail(c, BDX_EINTERNAL, "the region table did not arrive: its kernels were not launched");
         }
-    }
-    if (na) {
         // (the table sits in pinned memory the device has just written: one streaming copy into ordinary memory is much
         // cheaper than the walk's scattered reads of it)
         if ((uint64_t)c->h_counts0.as<StageCounts>()->n_regions + ph > kMaxRegions) {   // (region ids are 26-bit fields of the packed group key)
@@ -2180,21 +2139,13 @@ int bdx_use_name_check(bdx_ctx* c, int on) {
 
 int bdx_set_debug(bdx_ctx* c, const char* name, int value) {
     if (!c || !name) return BDX_EINVAL;
-    struct { const char* n; int* p; } ints[] = {{"no_stash", &c->dbg_no_stash}, {"max_chunks", &c->dbg_max_chunks}, {"finalize2_fold", &c->dbg_finalize2_fold},
-                                                 {"no_forward", &c->dbg_no_forward}, {"scan3", &c->dbg_scan3}, {"label_rounds", &c->dbg_label_rounds},
-                                                 {"k1_grid", &c->dbg_k1_grid}, {"end_write_value", &c->dbg_end_write_value}, {"spec_test", &c->spec_test},
-                                                 {"walk_lanes", &c->dbg_walk_lanes}, {"ins_plain", &c->dbg_ins_plain}, {"gather_walk", &c->dbg_gather_walk}, {"region_dma", &c->dbg_region_dma}, {"join_fwd", &c->dbg_join_fwd}, {"regions_copy", &c->dbg_regions_copy}, {"asm_plain", &c->dbg_asm_plain},
-                                                 {"big_walk", &c->big_walk_mode}};
+    struct { const char* n; int* p; } ints[] = {{"no_stash", &c->dbg_no_stash}, {"max_chunks", &c->dbg_max_chunks}, {"spec_test", &c->spec_test},
+                                                 {"big_walk", &c->big_walk_mode}, {"ins_plain", &c->dbg_ins_plain}, {"regions_copy", &c->dbg_regions_copy},
+                                                 {"asm_plain", &c->dbg_asm_plain}, {"gather_walk", &c->dbg_gather_walk}};
     for (auto& e : ints)
         if (!strcmp(name, e.n)) { *e.p = value; return BDX_OK; }
     if (!strcmp(name, "bucketed_join")) { c->bucketed_join = value != 0; return BDX_OK; }
     if (!strcmp(name, "no_poll")) { c->poll = value == 0; return BDX_OK; }
-    if (!strcmp(name, "k1_event_period")) { c->k1_event_period = (uint32_t)std::max(1, value); return BDX_OK; }
-    if (!strcmp(name, "pin_noncoherent")) {   // (before the first run: the result tables' pinned buffers are allocated non-coherent)
-        for (PinBuf* b : {&c->h_sv_out, &c->h_lib_index, &c->h_lib_pairs, &c->h_cn_key, &c->h_cn_value, &c->h_ltail_dev, &c->h_regs, &c->h_pk})
-            b->flags = value ? hipHostMallocNonCoherent : hipHostMallocDefault;
-        return BDX_OK;
-    }
     return fail(c, BDX_EINVAL, std::string("unknown debug switch ") + name);
 }
 

@@ -59,12 +59,11 @@ struct bdx_bamdec {
     int device = 0;
     bdx_ctx* sink = nullptr;
     std::string err;
-    hipStream_t s_copy = nullptr, s_inf = nullptr, s_inf2 = nullptr, s_rec = nullptr;   // (s_inf == s_inf2 == s_rec unless stream_mode != 0: bdx_bamdec_create)
+    hipStream_t s_copy = nullptr, s_rec = nullptr;   // (the inflate launches and the record stages take turns on s_rec: bdx_bamdec_create)
     // A decoder that feeds a context copies on the context's copy stream; with the context's compute and side streams and the decoder's
     // own that makes four streams in all.  The HIP runtime spreads a process's streams over four hardware queues, and two streams on one
     // queue run in order -- with six, the completion of a 0.3 ms copy waited behind a 19 ms inflate launch.
-    bool borrowed_copy = false, borrowed_rec = false;   // (a stream of the sink's: not the decoder's to destroy)
-    bool own_inf_stream = false;      // (stream_mode 1 / 2) the inflate launches have a stream of their own; else they run in s_rec
+    bool borrowed_copy = false;   // (the sink's copy stream: not the decoder's to destroy)
     // pinned staging: one piece's compressed bytes and the caller's member table
     struct Staging {
         PinBuf h_comp, h_tab;
@@ -410,35 +409,14 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
     // Taking turns costs the record stages' own time, ~1 ms per 7,680 members.  The stream is NOT the sink's compute stream: the runtime
     // spreads a process's streams over four hardware queues, two streams on one queue run in order, and a copy's completion marker behind
     // a 30 ms inflate launch kept the feeder waiting for its staging buffers; the classifier, on the sink's stream, follows the record
-    // stages through their events.  bdx_bamdec_params::stream_mode 1: the inflate launches in a third stream, beside the record stages, as until round 4.
+    // stages through their events.
     if (sink && sink->copy_stream) {
         d->s_copy = sink->copy_stream;
         d->borrowed_copy = true;
     } else if (hipStreamCreateWithFlags(&d->s_copy, hipStreamNonBlocking) != hipSuccess) {
         return bad(BDX_EHIP);
     }
-    {
-        const bool prio = p->stream_mode == 2;   // (experiment: the three streams with queue priorities -- record stages high, inflate low)
-        const bool third = p->stream_mode == 1 || prio;
-        int pr_least = 0, pr_greatest = 0;
-        if (prio && hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest) != hipSuccess) return bad(BDX_EHIP);
-        if (prio) {
-            if (hipStreamCreateWithPriority(&d->s_rec, hipStreamNonBlocking, pr_greatest) != hipSuccess) return bad(BDX_EHIP);
-        } else if (third && sink && sink->stream) {
-            d->s_rec = sink->stream;
-            d->borrowed_rec = true;
-        } else if (hipStreamCreateWithFlags(&d->s_rec, hipStreamNonBlocking) != hipSuccess) {
-            return bad(BDX_EHIP);
-        }
-        if (third) {
-            if (prio ? hipStreamCreateWithPriority(&d->s_inf, hipStreamNonBlocking, pr_least) != hipSuccess
-                     : hipStreamCreateWithFlags(&d->s_inf, hipStreamNonBlocking) != hipSuccess) return bad(BDX_EHIP);
-            d->own_inf_stream = true;
-        } else {
-            d->s_inf = d->s_rec;
-        }
-    }
-    d->s_inf2 = d->s_inf;
+    if (hipStreamCreateWithFlags(&d->s_rec, hipStreamNonBlocking) != hipSuccess) return bad(BDX_EHIP);
     for (auto& sl : d->slot)
         if (hipEventCreateWithFlags(&sl.ev_copied, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&sl.ev_free, hipEventDisableTiming) != hipSuccess)
             return bad(BDX_EHIP);
@@ -587,7 +565,7 @@ void bdx_bamdec_destroy(bdx_bamdec* d) {
     (void)hipSetDevice(d->device);
     if (d->presize_thread.joinable()) d->presize_thread.join();
     if (d->pin_thread.joinable()) d->pin_thread.join();   // (before anything is released: the thread may still be pinning staging buffers)
-    for (hipStream_t s : {d->s_copy, d->s_inf, d->s_inf2, d->s_rec})
+    for (hipStream_t s : {d->s_copy, d->s_rec})
         if (s) (void)hipStreamSynchronize(s);
     for (auto& sl : d->slot) {
         sl.h_blocks.release(); sl.d_comp.release(); sl.d_blocks.release(); sl.d_status.release();
@@ -610,11 +588,8 @@ void bdx_bamdec_destroy(bdx_bamdec* d) {
                       &d->o_tid, &d->o_pos, &d->o_mtid, &d->o_mpos, &d->o_isize, &d->o_flag, &d->o_qlen, &d->o_mapq, &d->o_lib, &d->o_bam, &d->o_key})
         b->release();
     d->h_progress.release();
-    if (!d->own_inf_stream) d->s_inf = nullptr;
-    d->s_inf2 = nullptr;
     if (d->borrowed_copy) d->s_copy = nullptr;
-    if (d->borrowed_rec) d->s_rec = nullptr;
-    for (hipStream_t s : {d->s_copy, d->s_inf, d->s_inf2, d->s_rec})
+    for (hipStream_t s : {d->s_copy, d->s_rec})
         if (s) (void)hipStreamDestroy(s);
     delete d;
 }
@@ -664,9 +639,6 @@ int bam_launch_batch(bdx_bamdec* d, int si, bool last) {
     p.seq = ++d->n_pieces;
     p.slot = si;
     p.nblk = (uint32_t)nblocks;
-    // Batches alternate between two streams: a launch whose members outnumber the GPU's wave slots ends with the slots draining
-    // (a member takes ~10 ms however many run beside it), and the next batch's waves fill them as they come free.
-    hipStream_t s_inf = (p.seq & 1) ? d->s_inf : d->s_inf2;
     if (d->cursor + ulen > d->ring_bytes) { p.wrapped = !d->pieces.empty(); d->cursor = 0; }
     p.ring_beg = d->cursor;
     p.ring_end = p.mirror_end = d->cursor + ulen;
@@ -686,21 +658,21 @@ int bam_launch_batch(bdx_bamdec* d, int si, bool last) {
         if (!overlap) continue;
         // (a batch whose record stage still waits for its successor -- this batch -- cannot give its bytes up: the ring is too small)
         if (!q.records_done) return bfail(d, BDX_ELIMIT, "inflate ring too small for the batches in flight");
-        BHIP(d, hipStreamWaitEvent(s_inf, q.ev_records, 0));
+        BHIP(d, hipStreamWaitEvent(d->s_rec, q.ev_records, 0));
     }
     // (sized for what the slot can hold, once: growing a buffer frees it first, and hipFree waits for the device)
     BHIP(d, sl.d_blocks.ensure(std::max<size_t>(std::max(nblocks, sl.cap_blk), 1) * sizeof(BgzfBlock)));
     BHIP(d, sl.d_status.ensure(std::max<size_t>(std::max(nblocks, sl.cap_blk), 1) * 4));
     if (nblocks) BHIP(d, hipMemcpyAsync(sl.d_blocks.p, tb, nblocks * sizeof(BgzfBlock), hipMemcpyHostToDevice, d->s_copy));
     BHIP(d, hipEventRecord(sl.ev_copied, d->s_copy));
-    BHIP(d, hipStreamWaitEvent(s_inf, sl.ev_copied, 0));
+    BHIP(d, hipStreamWaitEvent(d->s_rec, sl.ev_copied, 0));
     hipEvent_t kz0 = nullptr, kz1 = nullptr;
-    if (d->time_kernels && hipEventCreate(&kz0) == hipSuccess && hipEventCreate(&kz1) == hipSuccess) (void)hipEventRecord(kz0, s_inf);
-    launch_kz_inflate(sl.d_comp.as<uint8_t>(), sl.d_blocks.as<BgzfBlock>(), (uint32_t)nblocks, d->d_ring.as<uint8_t>(), sl.d_status.as<uint32_t>(), s_inf);
-    if (kz0 && kz1) { (void)hipEventRecord(kz1, s_inf); d->kz_events.emplace_back(kz0, kz1); }
+    if (d->time_kernels && hipEventCreate(&kz0) == hipSuccess && hipEventCreate(&kz1) == hipSuccess) (void)hipEventRecord(kz0, d->s_rec);
+    launch_kz_inflate(sl.d_comp.as<uint8_t>(), sl.d_blocks.as<BgzfBlock>(), (uint32_t)nblocks, d->d_ring.as<uint8_t>(), sl.d_status.as<uint32_t>(), d->s_rec);
+    if (kz0 && kz1) { (void)hipEventRecord(kz1, d->s_rec); d->kz_events.emplace_back(kz0, kz1); }
     p.ev_inflated = bam_event(d);
     if (!p.ev_inflated) return bfail(d, BDX_EHIP, "hipEventCreate");
-    BHIP(d, hipEventRecord(p.ev_inflated, s_inf));
+    BHIP(d, hipEventRecord(p.ev_inflated, d->s_rec));
     sl.busy = true;
     sl.open = false;
     if (p.seq == 1) d->first_batch_bytes = sl.bytes;
@@ -839,8 +811,6 @@ int bdx_bamdec_finish(bdx_bamdec* d, uint64_t* n_records) {
         d->held_staging = 0;   // (pieces acquired ahead and never submitted -- a caller that stopped early -- are dropped)
     }
     BHIP(d, hipStreamSynchronize(d->s_copy));
-    BHIP(d, hipStreamSynchronize(d->s_inf));
-    BHIP(d, hipStreamSynchronize(d->s_inf2));
     BHIP(d, hipStreamSynchronize(d->s_rec));
     PieceState st{};
     BHIP(d, hipMemcpy(&st, d->d_state.p, sizeof(st), hipMemcpyDeviceToHost));
@@ -891,7 +861,7 @@ int bdx_bamdec_rearm(bdx_bamdec* d, int32_t only_tid, int32_t region_beg, int32_
     if (!d) return BDX_EINVAL;
     if (!d->finished) return bfail(d, BDX_ESTATE, "bdx_bamdec_finish first");
     BHIP(d, hipSetDevice(d->device));
-    for (hipStream_t s : {d->s_copy, d->s_inf, d->s_inf2, d->s_rec})
+    for (hipStream_t s : {d->s_copy, d->s_rec})
         if (s) BHIP(d, hipStreamSynchronize(s));
     d->filt.only_tid = only_tid; d->filt.beg = region_beg; d->filt.end = region_end;
     for (auto& st : d->staging) st.busy = false;

@@ -1513,9 +1513,8 @@ int bdx_dist_run(bdx_dist* d) {
             // (components that span ranks are mostly a translocation's two regions and their neighbours: three rounds of label propagation settle
             // them -- the eight of a context that walks large components are seven launches on rank 0's own part of the run; what has not
             // converged fails the closure check and is the host's)
-            if (!U->dbg_label_rounds) U->dbg_label_rounds = 3;
             memset(&U->counts, 0, sizeof(U->counts));
-            DCTX(d, U, do_k6(U, force_host, 0));
+            DCTX(d, U, do_k6(U, force_host, 0, nullptr, kK6LabelRoundsGather));
             if (!wait_flag(U, 1, U->seq)) {
                 DHIP(d, hipStreamSynchronize(su));
                 if (!flag_arrived(U, 1)) return dfail(d, BDX_EINTERNAL, "the pair groups of the gathered components did not arrive: their kernels were not launched");

@@ -64,17 +64,10 @@ struct K3Arrays {
     int host_copy_later;   // 1: write only the device copies here; the join kernel forwards them to r_rec / r_pk
     uint32_t* out_deg;     // K6 per-region scratch reset by k3_region_of_kernel: [6][cap] = out_deg, label (= index),
                            // bad_v, bad, mcount, pcount; may be null
-    // scan workspace and totals
-    U4* ws_u4;
-    U4* head_total;
-    uint32_t* ws_u32;
-    uint32_t* acc_total;
-    unsigned long long* lb_state;  // look-back words of the two scans: [5][scan_grid(cap, 1)], zero at allocation; null: three-launch scans
+    unsigned long long* lb_state;  // look-back words of the two scans: [5][scan_grid(cap, 1)], zero at allocation
     uint32_t lb_stamp;             // run stamp of those words (never 0, changes every run)
     StageCounts* counts;
     StageCounts* counts_host;  // pinned host mirror: n_cand / n_regions / last_maxq are stored there as well (may be null)
-    uint32_t* flag_host;       // pinned word set to flag_value by k3_region_of_kernel: the region table is complete
-    uint32_t flag_value;
 };
 
 // the read that closes the last candidate when the stream continues in another context (next chromosome)
@@ -156,9 +149,6 @@ struct Entries {
     int nkeys2;              // 2 x nkeys words of proper-read samples per region
     uint32_t* k6_scratch;    // [6][scratch_cap]
     uint32_t scratch_cap;
-    uint32_t* flag_host;     // pinned word: the region table (written by the kernel before) is complete
-    uint32_t flag_value;
-    uint32_t fwd_blocks;     // workgroups in front of the joining ones that forward the region table (0: kJoinForwardBlocks; ~0: every wave forwards, A/B)
     // sharded runs: entries n_local .. n - 1 are FOREIGN -- inter-chromosomal reads of chromosomes another rank owns whose mates lie on
     // a (later) chromosome of this rank (k7_exchange.hip) -- with their own arrays; they come first in stream order, are never the
     // second-observed mate, and have no partner[] / pair_lo[] entry.  n_local null: every entry is the context's own
@@ -215,6 +205,7 @@ constexpr uint32_t kK6RankSortMax = 1u << 17;  // entries of the insertion list 
 constexpr int kK6LabelRounds = 2;  // min-label propagation rounds (the first inside k6_pairs_kernel, the others with pointer jumping):
                                    // two settle chains of four regions in practice; a component that has not converged fails
                                    // the closure check and goes to the host
+constexpr int kK6LabelRoundsGather = 3;  // ... in rank 0's device walk of the components gathered from a sharded run's ranks
 
 struct RegSum {        // per accepted region r, written by k6_pairs_kernel
     uint32_t np_all;   // sorted, merged (lo, flag, lib) parts of the pairs whose second mate is in r, at parts[first ..)
@@ -379,11 +370,10 @@ struct K6Arrays {
     int mirror_in_walk;            // the first wave of k6_walk_kernel mirrors the counters and sets flag_groups (no k6_mirror_kernel launch)
     int big_walk;                  // components of up to kK6BigMembers regions are walked on the device (k6_walk_big_kernel); 0: up to kK6MaxMembers
     uint32_t fin_regions;          // regions k6_place_kernel's launch is sized for (the host's count once it has read it; 0: cap)
-    int walk_lanes;                // regions per wave of k6_walk_kernel (<= 64)
     int asm_plain;                 // test switch (bdx_set_debug "asm_plain"): the candidate assembly merges its parts by the three-way merge whatever the number of libraries
     int ins_plain;                 // test switch (bdx_set_debug "ins_plain"): 1 = the insertion list is ranked as before round 6 (k6_ranksort_kernel / LDS bitonic),
                                    // 2 = the bucket path declares its list crowded (the bitonic sort takes it)
-    int label_rounds;              // min-label propagation rounds incl. the one inside k6_pairs_kernel (default kK6LabelRounds)
+    int propagation_rounds;        // min-label propagation rounds incl. the one inside k6_pairs_kernel (default kK6LabelRounds)
     // sharded runs: region ids are genome-wide, the table holds this rank's regions at their genome-wide places and n == 0 everywhere
     // else.  A gate-passing group whose earlier region is another rank's makes both of its regions `tainted` (bytes, all-reduced over
     // the ranks between k6_pairs_kernel and k6_classify_kernel): their components go to the host list, i.e. to rank 0's walk

@@ -84,13 +84,6 @@ template <class T, class In, int kIters> __global__ __launch_bounds__(kScanBlock
     scan_phase1_body<T, In, kIters>(in, n_ptr, blk);
 }
 
-// phase 1 with one extra workgroup (the last) that runs an independent side job of the caller
-template <class T, class In, class Side, int kIters>
-__global__ __launch_bounds__(kScanBlock) void scan_phase1_side(In in, Side side, const uint32_t* n_ptr, T* blk) {
-    if (blockIdx.x == gridDim.x - 1) side();
-    else scan_phase1_body<T, In, kIters>(in, n_ptr, blk);
-}
-
 // single workgroup: in-place exclusive scan of the block sums, grand total -> *total
 template <class T, int kIters> __global__ __launch_bounds__(1024) void scan_phase2(T* blk, const uint32_t* n_ptr, T* total) {
     constexpr int kScanChunk = kScanBlock * kIters;
@@ -293,20 +286,6 @@ template <class T, int kIters = 1, class In, class Out>
 void scan_launch_lb(In in, Out out, const uint32_t* n_ptr, uint32_t n_upper, unsigned long long* state, uint32_t stamp, hipStream_t s) {
     const uint32_t g = scan_grid(n_upper, kIters);
     hipLaunchKernelGGL((scan_lookback<T, In, Out, kIters>), dim3(g), dim3(kScanBlock), 0, s, in, out, n_ptr, state, stamp);
-}
-
-// the same scan with a side job (a device functor run by one extra workgroup of kScanBlock threads during phase 1; its
-// results are complete before phase 3's output functor runs)
-template <class T, int kIters = kScanIters, class In, class Out, class Side>
-void scan_launch_side(In in, Out out, Side side, const uint32_t* n_ptr, uint32_t n_upper, T* blk_ws, T* total, hipStream_t s) {
-    const uint32_t g = scan_grid(n_upper, kIters);
-    hipLaunchKernelGGL((scan_phase1_side<T, In, Side, kIters>), dim3(g + 1), dim3(kScanBlock), 0, s, in, side, n_ptr, blk_ws);
-    if (g <= kScanSelfSumMax) {
-        hipLaunchKernelGGL((scan_phase3<T, In, Out, kIters, true>), dim3(g), dim3(kScanBlock), 0, s, in, out, n_ptr, blk_ws);
-        return;
-    }
-    hipLaunchKernelGGL((scan_phase2<T, kIters>), dim3(1), dim3(1024), 0, s, blk_ws, n_ptr, total);
-    hipLaunchKernelGGL((scan_phase3<T, In, Out, kIters, false>), dim3(g), dim3(kScanBlock), 0, s, in, out, n_ptr, blk_ws);
 }
 
 }  // namespace bdx

@@ -153,10 +153,6 @@ struct AcceptOut {
 
 __global__ __launch_bounds__(256) void k3_region_of_kernel(K3Arrays a, const Pass1* p1) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j == 0 && a.flag_host) {  // the kernel before this one wrote the last region record
-        __threadfence_system();
-        *(volatile uint32_t*)a.flag_host = a.flag_value;
-    }
     if (j < p1->n_anom) {
         a.region_of[j] = a.c_rid[a.cand[j]];
         if (a.out_deg) {  // K6's component scratch: out_deg, label, bad_v, bad, mcount, pcount
@@ -177,22 +173,13 @@ void launch_k3(const K3Arrays& a, const Compact& cp, const Pass1* p1, uint32_t n
     const uint32_t* n_ptr = &p1->n_anom;
     HeadIn hin{cp.tid, cp.pos, cp.meta, p1};
     HeadOut hout{a, cp.tid, tail.tid_tail ? 1 : 0};
-    if (a.lb_state) {  // one launch per scan (decoupled look-back) instead of two
-        const size_t nblk = scan_grid(a.cap, 1);
-        if (n_anom_host > (1u << 19)) scan_launch_lb<U4, 2>(hin, hout, n_ptr, n_anom_host, a.lb_state, a.lb_stamp, s);   // (two reads per lane: half the workgroups and look-back words -- 45 -> 35 us at a genome share; four: 39)
-        else scan_launch_lb<U4, 1>(hin, hout, n_ptr, n_anom_host, a.lb_state, a.lb_stamp, s);
-        const CandCtx cx{a, cp, p1, min_len, seq_coverage_lim, nn_base, tail};
-        scan_launch_lb<uint32_t, 1>(AcceptIn{cx}, AcceptOut{cx, nkeys}, &a.counts->n_cand, n_anom_host, a.lb_state + 4 * nblk, a.lb_stamp, s);
-        if (region_of_launch) hipLaunchKernelGGL(k3_region_of_kernel, dim3((n_anom_host + 255) / 256), dim3(256), 0, s, a, p1);
-        return;
-    }
-    scan_launch<U4, 1>(hin, hout, n_ptr, n_anom_host, a.ws_u4, a.head_total, s);
-    const uint32_t g = (n_anom_host + 255) / 256;
+    // one launch per scan (decoupled look-back)
+    const size_t nblk = scan_grid(a.cap, 1);
+    if (n_anom_host > (1u << 19)) scan_launch_lb<U4, 2>(hin, hout, n_ptr, n_anom_host, a.lb_state, a.lb_stamp, s);   // (two reads per lane: half the workgroups and look-back words -- 45 -> 35 us at a genome share; four: 39)
+    else scan_launch_lb<U4, 1>(hin, hout, n_ptr, n_anom_host, a.lb_state, a.lb_stamp, s);
     const CandCtx cx{a, cp, p1, min_len, seq_coverage_lim, nn_base, tail};
-    AcceptIn ain{cx};
-    AcceptOut aout{cx, nkeys};
-    scan_launch<uint32_t, 1>(ain, aout, &a.counts->n_cand, n_anom_host, a.ws_u32, a.acc_total, s);
-    if (region_of_launch) hipLaunchKernelGGL(k3_region_of_kernel, dim3(g), dim3(256), 0, s, a, p1);  // else: fused into the join
+    scan_launch_lb<uint32_t, 1>(AcceptIn{cx}, AcceptOut{cx, nkeys}, &a.counts->n_cand, n_anom_host, a.lb_state + 4 * nblk, a.lb_stamp, s);
+    if (region_of_launch) hipLaunchKernelGGL(k3_region_of_kernel, dim3((n_anom_host + 255) / 256), dim3(256), 0, s, a, p1);  // else: fused into the join
 }
 
 }  // namespace bdx

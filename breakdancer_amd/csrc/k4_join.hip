@@ -170,11 +170,10 @@ __global__ __launch_bounds__(256) void k4_direct_join_kernel(K4Arrays k4, Entrie
     // genome share, 110 us of link time -- sat in front of every wave's loads: 6 us for a coalesced load at the median, 145 us for a launch
     // that takes 94 by itself (profiles/r06_join_kernel.txt).  32 workgroups keep the link busy (16 bytes per lane in flight); they are
     // dispatched first and run beside the join.
-    const bool fwd_all = en.fwd_blocks == 0xFFFFFFFFu;   // (A/B switch: every joining wave forwards its share first, as before round 6)
-    const uint32_t fwd = (en.r_rec_host && !fwd_all) ? (en.fwd_blocks ? en.fwd_blocks : kJoinForwardBlocks) : 0u;
-    if (blockIdx.x < fwd || (fwd_all && en.r_rec_host)) {
+    const uint32_t fwd = en.r_rec_host ? kJoinForwardBlocks : 0u;
+    if (blockIdx.x < fwd) {
         const uint32_t nr = en.counts->n_regions;
-        const uint32_t t = blockIdx.x * 256 + threadIdx.x, gsz = (fwd_all ? gridDim.x : fwd) * 256;
+        const uint32_t t = blockIdx.x * 256 + threadIdx.x, gsz = fwd * 256;
         constexpr uint32_t kw = sizeof(RegionRec) / 4;
         {
             const uint32_t words = nr * kw, quads = words / 4;   // (the tables start on 256-byte boundaries)
@@ -190,16 +189,13 @@ __global__ __launch_bounds__(256) void k4_direct_join_kernel(K4Arrays k4, Entrie
             for (uint32_t i = t; i < quads; i += gsz) dst[i] = src[i];
             if (t < words - quads * 4) en.r_pk_host[quads * 4 + t] = en.r_pk_dev[quads * 4 + t];
         }
-        if (!fwd_all) return;
     }
-    const uint32_t j = (blockIdx.x - fwd) * 256 + threadIdx.x;
+    // (a forwarding workgroup holds no entry: it leaves at the bound check below.  Leaving right after the copy instead cost the kernel
+    // 17 more SGPRs, and a wave slot per SIMD)
+    const uint32_t j = blockIdx.x < fwd ? 0xFFFFFFFFu : (blockIdx.x - fwd) * 256 + threadIdx.x;
     const uint32_t kp = (blockIdx.x - fwd) * 4 + (threadIdx.x >> 6);   // (measurement build: this wave's row of clocks)
     (void)kp;
     KPROF(kp, 0);
-    if (j == 0 && en.flag_host) {  // the kernel before this one wrote the last region record
-        __threadfence_system();
-        *(volatile uint32_t*)en.flag_host = en.flag_value;
-    }
     KPROF(kp, 1);
     if (j >= na) return;
     // (sharded runs: the entries behind the context's own are foreign -- see Entries::n_local)
@@ -332,7 +328,7 @@ static void launch_k4_impl(const K4Arrays& k4, const Entries& en, const uint32_t
     if (n_anom_host == 0) return;
     const uint32_t g = (n_anom_host + kPartChunk - 1) / kPartChunk;
     if (k4.direct) {
-        const uint32_t gd = (n_anom_host + 255) / 256 + ((en.r_rec_host && en.fwd_blocks != 0xFFFFFFFFu) ? (en.fwd_blocks ? en.fwd_blocks : kJoinForwardBlocks) : 0u);
+        const uint32_t gd = (n_anom_host + 255) / 256 + (en.r_rec_host ? kJoinForwardBlocks : 0u);
         hipLaunchKernelGGL(k4_direct_join_kernel, dim3(gd), dim3(256), 0, s, k4, en, n_ptr, counts);
         if (aggregate) {
             (void)hipFuncSetAttribute((const void*)k4_aggregate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kAggSlots * 16 + 32);

@@ -837,7 +837,7 @@ struct WalkTab {
     uint32_t* p;  // this lane's column
     static constexpr int kSbeg = 0, kScnt = 4, kEbeg = 8, kEcnt = 14, kSw = 20, kEw = 24, kSslot = 30, kEslot = 34, kOrd = 40, kRid = 44,
                          kCalls = 48, kRtid = 58, kRstart = 62, kRend = 66, kRn = 70, kRrev = 74, kFields = 78;
-    static constexpr int kStride = 32;   // lanes of a wave that walk (K6Arrays::walk_lanes <= this): field f of lane l at word f * kStride + l
+    static constexpr int kStride = 32;   // lanes of a wave that walk (measured 64 / 32 / 16 per wave at configs[1]: 23.7 / 22.4 / 24.5 us): field f of lane l at word f * kStride + l
     __device__ __forceinline__ uint32_t& at(int f) const { return p[f * kStride]; }
     __device__ __forceinline__ uint32_t& Sbeg(int i) const { return at(kSbeg + i); }
     __device__ __forceinline__ uint32_t& Scnt(int i) const { return at(kScnt + i); }
@@ -914,7 +914,7 @@ __global__ __launch_bounds__(64) void k6_walk_kernel(K6Arrays a) {
     // One lane per REGION; the smallest region of a device-walked component (k6_emit_kernel marked it with the component's
     // size) walks it.  Everything the first phase needs is requested at once, the description (indexed by label = this region)
     // before it is known whether the region is such an owner: a dependent round trip costs ~1.3 us here, bytes cost nothing.
-    const uint32_t wl = (uint32_t)min(a.walk_lanes, WalkTab::kStride);  // components per wave (the other lanes stay idle: fewer addresses per memory instruction)
+    constexpr uint32_t wl = WalkTab::kStride;  // components per wave (the other lanes stay idle: fewer addresses per memory instruction)
     if ((uint32_t)lane >= wl) return;
     for (uint32_t r = blockIdx.x * wl + lane; r < NR; r += gridDim.x * wl) {
         const MemberInfo* D = a.members + (size_t)r * kK6MaxMembers;
@@ -1776,7 +1776,7 @@ void launch_k6_components(const K6Arrays& a, uint32_t n_anom_host, hipStream_t s
     constexpr uint32_t kRegionThreads = 64;  // (whole waves: the emit step's reservations are wave-aggregated; measured 256 / 128 / 64: step 0.2749 / 0.2730 / 0.2711 ms)
     const uint32_t grs = (n_anom_host + kRegionThreads - 1) / kRegionThreads;
     if (!a.force_host)
-        for (int i = 1; i < a.label_rounds; ++i) hipLaunchKernelGGL(k6_label_kernel, dim3(grs), dim3(kRegionThreads), 0, s, a);  // round 1: k6_pairs
+        for (int i = 1; i < a.propagation_rounds; ++i) hipLaunchKernelGGL(k6_label_kernel, dim3(grs), dim3(kRegionThreads), 0, s, a);  // round 1: k6_pairs
     hipLaunchKernelGGL(k6_classify_kernel, dim3(grs), dim3(kRegionThreads), 0, s, a);
     hipLaunchKernelGGL(k6_emit_kernel, dim3(grs), dim3(kRegionThreads), 0, s, a);
     if (a.counts_host && !a.mirror_in_walk) hipLaunchKernelGGL(k6_mirror_kernel, dim3(1), dim3(64), 0, s, a);
@@ -1790,7 +1790,7 @@ void launch_k6_groups(const K6Arrays& a, uint32_t n_anom_host, hipStream_t s) {
 void launch_k6_walk(const K6Arrays& a, uint32_t n_anom_host, hipStream_t s) {
     if (n_anom_host == 0 || a.force_host) return;
     const uint32_t gp = std::min<uint32_t>((n_anom_host / 8 + 3) / 4 + 1, 16384u);
-    hipLaunchKernelGGL(k6_walk_kernel, dim3(std::min<uint32_t>(n_anom_host / (uint32_t)a.walk_lanes / 4 + 1, 8192u)), dim3(64), 0, s, a);  // a lane per region, grid-stride: regions are typically a tenth of the reads
+    hipLaunchKernelGGL(k6_walk_kernel, dim3(std::min<uint32_t>(n_anom_host / WalkTab::kStride / 4 + 1, 8192u)), dim3(64), 0, s, a);  // a lane per region, grid-stride: regions are typically a tenth of the reads
     if (a.big_walk) hipLaunchKernelGGL(k6_walk_big_kernel, dim3(gp / 8 + 1), dim3(256), 0, s, a);
     // (the ranks of the device's insertion list, should it be long: beside the host's walk.  Small inputs do without the launch)
     if (a.rank_part) hipLaunchKernelGGL(k6_ranksort_kernel, dim3(kRankGrid), dim3(kScanBlock), 0, s, a);

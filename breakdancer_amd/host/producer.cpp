@@ -513,7 +513,6 @@ size_t decode_on_device(const BamConfig& cfg, size_t bam_index, const std::strin
         }
         // (test / measurement knobs of the CLI; the library reads no environment variable for them: they travel in the parameters)
         if (const char* br = getenv("BDX_BAM_BATCH_ROUNDS")) p.batch_rounds = std::max(1, std::min(16, atoi(br)));
-        if (const char* ks = getenv("BDX_KZ_STREAM")) p.stream_mode = !strcmp(ks, "own") ? 1 : !strcmp(ks, "prio") ? 2 : 0;
         if (getenv("BDX_TIMING")) p.time_kernels = 1;   // (the timing lines say what the inflate kernel took inside the pipeline)
         const size_t rounds = p.batch_rounds ? (size_t)p.batch_rounds : std::max<size_t>(1, std::min<size_t>(4, rest / ((size_t)2560 << 20)));
         const size_t blocks = p.batch_blocks ? p.batch_blocks : 7680 * rounds;

@@ -225,8 +225,8 @@ int bdx_get_sv_support(const bdx_ctx* ctx, uint32_t* sv_offsets, uint64_t* read_
 int bdx_get_read_class(const bdx_ctx* ctx, uint8_t* out, size_t cap);
 
 /* stage timings of the last bdx_run in milliseconds (HIP events on the context's stream):
- * [0] classify kernel (its own begin-to-end time from kernel-level start/stop events, taken on every 4th run by default,
- *     BDX_K1_EVENT_PERIOD=n; the latest measurement), [1] compaction, [2] region cut, [3] mate join + grouping + SV assembly + scores on the device,
+ * [0] classify kernel (its own begin-to-end time from kernel-level start/stop events, taken on every 4th run, or every run with
+ *     stage timing on; the latest measurement), [1] compaction, [2] region cut, [3] mate join + grouping + SV assembly + scores on the device,
  * [4] host: wait for the host's share of the groups, [5] host walk of that share, [6] host: final wait, merge, score
  * combination, [7] whole run; [8]-[10] split [6] into the final wait, the merge of the device's and the host's SV lists,
  * and the score combination.  Returns the number written. */
@@ -247,14 +247,19 @@ int bdx_set_enqueue_ahead(bdx_ctx* ctx, int on);
  * process_sv, BreakDancer.cpp:266-497); every other component goes through the host walk.  bdx_set_host_walk(ctx, 1)
  * sends everything through the host walk (same results; used by the parity tests).  Any pointer may be NULL. */
 int bdx_set_host_walk(bdx_ctx* ctx, int on);
-/* Test and measurement switches, by name (they used to be environment variables read inside the library): "no_stash",
- * "max_chunks", "spec_test", "big_walk", "bucketed_join", "no_poll", "finalize2_fold", "no_forward", "scan3", "label_rounds",
- * "k1_grid", "end_write_value", "k1_event_period", "pin_noncoherent", and from round 6: "walk_lanes" (regions per wave of the walk kernel),
- * "ins_plain" (1: the insertion list ranked by the rank-sort launch, 2: by the bitonic fall-back), "gather_walk" (sharded runs, rank 0's walk
- * of the gathered components: 1 device, 2 host), "region_dma" (the region table fetched by copy commands instead of forwarded by the join
- * kernel), "join_fwd" (-1: every joining wave forwards its share; n: that many forwarding workgroups), "regions_copy" (1: the host copies the
- * region table before its share of the walk, 2: never), "asm_plain" (the walk's candidate assembly merges its parts by the three-way merge).  Every switch selects another route to the same results (the parity tests force each
- * route); none is needed in production.  BDX_EINVAL for an unknown name. */
+/* Test switches, by name.  Each forces a route the product takes by itself on some input, so that the tests reach it at any size;
+ * every route gives the same results, and none is needed in production.  Value 0 restores the default (big_walk: -1).
+ *   "no_stash"       K2 gathers every record from the columns (the route of more counter keys than K1's stash holds)
+ *   "max_chunks"     n: the tile scan in at most n chunks (the chunked scan of large inputs)
+ *   "spec_test"      enqueue-ahead guesses deliberately short (the rerun when more reads are anomalous than guessed)
+ *   "big_walk"       1 / 0: components of 5..64 regions always / never walked on the device (-1: by the host's share)
+ *   "bucketed_join"  the partitioned join at every size (the route of more than kDirectJoinMax entries)
+ *   "no_poll"        blocking waits instead of polled ready words (the fall-back when a stream write-value command fails)
+ *   "ins_plain"      1: the insertion list ranked by the rank-sort launch, 2: by the bitonic fall-back (chosen by the list's length)
+ *   "regions_copy"   1: the host copies the region table before its share of the walk (small tables), 2: never (large ones)
+ *   "asm_plain"      the walk's candidate assembly merges its parts by the three-way merge (the route of one library, or of many)
+ *   "gather_walk"    sharded runs: 1 = rank 0 walks the gathered components on its device, 2 = on its host (by their number otherwise)
+ * BDX_EINVAL for any other name. */
 int bdx_set_debug(bdx_ctx* ctx, const char* name, int value);
 int bdx_get_walk_split(const bdx_ctx* ctx, uint32_t* n_sv_device, uint32_t* n_sv_host, uint32_t* n_groups_host);
 /* After a run, once the caller has what it wants: the result tables are copied out of the pinned host buffers the device assembled them
@@ -458,9 +463,6 @@ typedef struct bdx_bamdec_params {
                                      MiB, and the first pieces would otherwise wait for it one after the other) */
     int32_t batch_rounds;         /* rounds of the GPU's wave slots an inflate launch takes (7,680 members each), 1..16; 0: from expected_bytes
                                      (one round per 2.5 GB, at most four).  Ignored when batch_blocks is given */
-    int32_t stream_mode;          /* 0: inflate launches and record stages take turns on one stream (the product's arrangement);
-                                     1: the inflate launches on a stream of their own beside the record stages (round 4's arrangement);
-                                     2: as 1, with queue priorities.  1 and 2 are measurement / test arrangements */
     int32_t record_mode;          /* bits: 1 = no reader filter (secondary / supplementary / unplaced records are kept too), 2 = the quality column is
                                      MAPQ whether or not a record carries an AM tag.  0 for breakdancer-max's reader; bam2cfg sets them */
     int32_t missing_lib_plus1;    /* library of records WITHOUT a read-group tag, plus one; 0: fallback_lib, like an unknown read group */

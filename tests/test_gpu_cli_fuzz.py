@@ -74,14 +74,8 @@ def test_cli_one_bam_decoded_on_the_gpu_equals_oracle(seed, tmp_path):
     for args, kw in (FLAGSETS[seed % len(FLAGSETS)], FLAGSETS[(3 * seed + 2) % len(FLAGSETS)]):
         run = oracle_case(cfg1, streams[:1], targets, make_opts(score_threshold=-1, **kw))
         texts = {}
-        # (the stream arrangements of the decoder that are kept as switches -- inflate launches on a stream of their own, with and without
-        # queue priorities -- decode the same records: small batches, so that inflate launches and record stages do run beside each other)
         for label, env in (("device", dict(BDX_TIMING="1")), ("device-small-pieces", dict(BDX_TIMING="1", BDX_BAM_PIECE_BYTES="100000", BDX_BAM_BATCH_BLOCKS="3", BDX_BAM_RING_BYTES="1048576")),
-                           ("device-own-inflate-stream", dict(BDX_TIMING="1", BDX_KZ_STREAM="own", BDX_BAM_PIECE_BYTES="100000", BDX_BAM_BATCH_BLOCKS="3")),
-                           ("device-stream-priorities", dict(BDX_TIMING="1", BDX_KZ_STREAM="prio", BDX_BAM_PIECE_BYTES="100000", BDX_BAM_BATCH_BLOCKS="3")),
                            ("host", dict(BDX_TIMING="1", BDX_DECODE="host"))):
-            if label in ("device-own-inflate-stream", "device-stream-priorities") and seed > 1:
-                continue
             p = subprocess.run([EXE, "-y", "-1"] + args + ["cfg"], cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, **env))
             assert p.returncode == 0, (label, p.stderr.decode())
             assert ("on the GPU" in p.stderr.decode()) == label.startswith("device"), p.stderr.decode()

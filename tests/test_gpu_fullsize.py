@@ -125,12 +125,6 @@ def test_config2_one_gpu_share_of_the_genome(genome_share):
         bd.run()
         tables_equal(bd, bh)
     bd.set_debug("ins_plain", 0)
-    # the region table fetched by a copy command once the host knows its size, instead of forwarded by the join kernel (a measured route)
-    bd.set_debug("region_dma", 1)
-    bd.run()
-    tables_equal(bd, bh)
-    region_invariants(bd.regions())
-    bd.set_debug("region_dma", 0)
     for mode in (1, 2):   # the host's share of the walk on its own copy of the region table (as before round 6) / on the table in pinned memory
         bd.set_debug("regions_copy", mode)
         bd.run()
@@ -141,11 +135,6 @@ def test_config2_one_gpu_share_of_the_genome(genome_share):
     bd.run()
     tables_equal(bd, bh)
     bd.set_debug("asm_plain", 0)
-    for fwd in (-1, 3):   # ... by every joining wave (as before round 6), by three workgroups in front of them (default: 32)
-        bd.set_debug("join_fwd", fwd)
-        bd.run()
-        tables_equal(bd, bh)
-        np.testing.assert_array_equal(bd.regions(), bh.regions())
     bd.close()
     bh.close()
 

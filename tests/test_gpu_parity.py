@@ -90,6 +90,26 @@ def test_ragged_batch_is_rejected():
         bd.push_reads(d)
 
 
+KEPT_SWITCHES = {"no_stash": 1, "max_chunks": 2, "spec_test": 1, "big_walk": 1, "bucketed_join": 1, "no_poll": 1, "ins_plain": 2,
+                 "regions_copy": 2, "asm_plain": 1, "gather_walk": 2}
+RETIRED_SWITCHES = ["scan3", "finalize2_fold", "end_write_value", "no_forward", "region_dma", "join_fwd", "walk_lanes", "k1_grid",
+                    "k1_event_period", "pin_noncoherent", "label_rounds"]
+
+
+def test_debug_switch_names():
+    """bdx_set_debug accepts the switches that force a route production takes, and rejects the retired ones like any unknown name"""
+    import breakdancer_amd as bda
+    from breakdancer_amd.api import BdxError, LibraryConfig, Options
+    bd = bda.BreakDancer(Options(), [LibraryConfig(400, 30, 490, 310, 100)], 1)
+    for name, value in KEPT_SWITCHES.items():
+        bd.set_debug(name, value)
+        bd.set_debug(name, -1 if name == "big_walk" else 0)
+    for name in RETIRED_SWITCHES:
+        with pytest.raises(BdxError, match="unknown debug switch"):
+            bd.set_debug(name, 1)
+    bd.close()
+
+
 def test_poisson_kernel_against_mpmath_vectors():
     """north_star: Poisson scores within 1e-6; the kernel holds 1e-10 relative on log p"""
     from breakdancer_amd.api import poisson_log_upper_tail
