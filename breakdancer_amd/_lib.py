@@ -57,7 +57,8 @@ EXPORTS = ["bdx_opts_default", "bdx_create", "bdx_destroy", "bdx_strerror", "bdx
            "bdx_warm_up", "bdx_set_process_option", "bdx_dist_unique_id", "bdx_dist_create", "bdx_dist_create_threads", "bdx_dist_destroy", "bdx_dist_last_error", "bdx_dist_rank",
            "bdx_dist_world", "bdx_dist_chromosome", "bdx_dist_run", "bdx_dist_result", "bdx_dist_set_collect_support", "bdx_dist_get_phase_ms", "bdx_dist_phase_name", "bdx_dist_prepare", "bdx_dist_reset_reads", "bdx_dist_get_exchange", "bdx_dist_get_collectives", "bdx_dist_set_debug", "bdx_dist_owner", "bdx_dist_plan",
            "bdx_bamdec_create", "bdx_bamdec_destroy", "bdx_bamdec_last_error", "bdx_bamdec_acquire", "bdx_bamdec_submit", "bdx_bamdec_progress",
-           "bdx_bamdec_finish", "bdx_bamdec_rearm", "bdx_bamdec_fetch", "bdx_bamdec_stats", "bdx_bamdec_host_ms", "bdx_merge_decoded", "bdx_append_decoded", "bdx_inflate_blocks", "bdx_insert_size_stats"]
+           "bdx_bamdec_finish", "bdx_bamdec_rearm", "bdx_bamdec_fetch", "bdx_bamdec_stats", "bdx_bamdec_host_ms", "bdx_merge_decoded", "bdx_append_decoded", "bdx_inflate_blocks", "bdx_insert_size_stats",
+           "bdx_count_junction_pairs"]
 
 REGION_REC_DTYPE = np.dtype([("tid", "<i4"), ("start", "<i4"), ("end", "<i4"), ("n_reads", "<u4"), ("rev_reads", "<u4"),
                              ("nonctx_reads", "<u4"), ("normal_read_pairs", "<u4"), ("max_qlen", "<i4"), ("first_read", "<u4")])
@@ -127,5 +128,6 @@ def load():
     L.bdx_stage_walk.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int]
     L.bdx_set_collect_support.argtypes = [vp, C.c_int]
     L.bdx_get_sv_support.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+    L.bdx_count_junction_pairs.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_int, vp]
     _lib = L
     return L

@@ -268,6 +268,22 @@ class BreakDancer:
         self._chk(self.lib.bdx_get_read_class(self.h, out.ctypes.data_as(C.c_void_p), n), "bdx_get_read_class")
         return out
 
+    def count_junction_pairs(self, tid, pos_a, pos_b, by_library=False):
+        """Normal read pairs of the last run whose fragment covers a junction (bdx_count_junction_pairs): query i is chromosome
+        tid[i] with the junctions pos_a[i] <= pos_b[i] (1-based; the boundary between base p and p + 1), a pair counts once if it covers
+        at least one of them.  Returns an (n, nkeys) uint32 array: per library with by_library, else per BAM file."""
+        t = np.ascontiguousarray(tid, dtype=np.int32)
+        a = np.ascontiguousarray(pos_a, dtype=np.int32)
+        b = np.ascontiguousarray(pos_b, dtype=np.int32)
+        if not (len(t) == len(a) == len(b)):
+            raise ValueError("tid, pos_a and pos_b differ in length")
+        nkeys = self.nlibs if by_library else self.nbams
+        out = np.zeros((len(t), nkeys), np.uint32)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.bdx_count_junction_pairs(self.h, p(t), p(a), p(b), len(t), int(bool(by_library)), p(out)),
+                  "bdx_count_junction_pairs")
+        return out
+
     def set_stage_timing(self, on=True):
         """HIP events between the stages (compact / regions / join timings); costs a few microseconds per event."""
         self._chk(self.lib.bdx_set_stage_timing(self.h, int(on)), "bdx_set_stage_timing")

@@ -256,6 +256,10 @@ struct bdx_ctx {
     struct KeySeg { uint64_t begin; const uint64_t* host; const uint16_t* host_qlen; const uint64_t* host_check; };
     std::vector<KeySeg> key_segs;
     DevBuf b_seg, b_lb;
+
+    // ---- bdx_count_junction_pairs ----
+    size_t cls_n = (size_t)-1;        // reads the class bytes in b_cls describe (set by a completed pass 1; -1: none)
+    DevBuf b_jq, b_jc;                // its queries and counts
 };
 
 namespace {
@@ -521,7 +525,8 @@ void bdx_destroy(bdx_ctx* c) {
                       &c->b_x_meta, &c->b_x_isize, &c->b_x_n, &c->b_fold, &c->b_lib_mean, &c->b_pair_lo, &c->b_sv_src, &c->b_dlists, &c->b_ltail, &c->b_r_rec, &c->b_r_pk, &c->b_out_deg,
                       &c->b_parts, &c->b_kdens, &c->b_rs, &c->b_slot, &c->b_members, &c->b_own, &c->b_lib_stage,
                       &c->b_cn_stage, &c->b_t_lambda, &c->b_t_k, &c->b_ws6, &c->b_ins, &c->b_member_ids,
-                      &c->b_sv_out, &c->b_lib_index_out, &c->b_lib_pairs_out, &c->b_cn_key_out, &c->b_cn_value_out, &c->b_ltail_out, &c->b_sv_key};
+                      &c->b_sv_out, &c->b_lib_index_out, &c->b_lib_pairs_out, &c->b_cn_key_out, &c->b_cn_value_out, &c->b_ltail_out, &c->b_sv_key,
+                      &c->b_jq, &c->b_jc};
     for (DevBuf* b : bufs) b->release();
     PinBuf* pins[] = {&c->h_p1, &c->h_cnt, &c->h_counts, &c->h_regs, &c->h_pk, &c->h_groups, &c->h_terms, &c->h_flags, &c->h_hs_rec, &c->h_hs_aux, &c->h_hs_lists, &c->h_printed, &c->h_counts0, &c->h_counts2,
                       &c->h_sv_out, &c->h_lib_index, &c->h_lib_pairs, &c->h_cn_key, &c->h_cn_value, &c->h_ltail_dev};
@@ -611,6 +616,7 @@ int bdx_reset_reads(bdx_ctx* c) {
     }
     c->n = 0;
     c->ran = false;
+    c->cls_n = (size_t)-1;
     c->k1_live = false;
     c->k1_done = 0;
     c->copy_pending = false;
@@ -634,6 +640,7 @@ int bdx_set_device_reads(bdx_ctx* c, const bdx_batch* b) {
     c->cap = b->n;
     c->adopted = true;
     c->ran = false;
+    c->cls_n = (size_t)-1;
     c->k1_live = false;
     c->key_segs.clear();
     return BDX_OK;
@@ -762,6 +769,7 @@ int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second) {
     const uint32_t ntiles = (uint32_t)((c->n + kTile - 1) / kTile);
     c->ntiles = ntiles;
     c->ran = false; c->stage = 0; c->replayed = false;
+    c->cls_n = (size_t)-1;
     c->na_alloc = 0;
     c->regions.clear(); c->r_pk.clear(); c->parts.clear();
     c->reg = nullptr; c->nreg = 0; c->rpk = nullptr;
@@ -844,6 +852,7 @@ int wait_pass1(bdx_ctx* c) {
     // its buffers are these buffers (an enqueue-ahead run has set its guess already)
     if (!c->na_alloc && c->p1.n_anom) c->na_alloc = (uint32_t)std::min<uint64_t>((uint64_t)c->p1.n_anom + c->p1.n_anom / 8 + 1024, kMaxAnomalous);
     c->stage = 1;
+    c->cls_n = c->n;
     return BDX_OK;
 }
 
@@ -2204,6 +2213,47 @@ int bdx_classify(const bdx_opts* opts, const bdx_lib* libs, int nlibs, const bdx
     return rc;
 }
 
+int bdx_count_junction_pairs(bdx_ctx* c, const int32_t* tid, const int32_t* pos_a, const int32_t* pos_b, size_t n, int by_library,
+                             uint32_t* counts) {
+    if (!c) return BDX_EINVAL;
+    NOT_WHILE_SIZING(c);
+    if (c->cls_n != c->n && !(c->ran && c->n == 0)) return fail(c, BDX_ESTATE, "no run has classified the reads this context holds");
+    if (n == 0) return BDX_OK;
+    if (!tid || !pos_a || !pos_b || !counts) return fail(c, BDX_EINVAL, "null array");
+    for (size_t i = 0; i < n; ++i)
+        if (tid[i] < 0 || pos_a[i] < 1 || pos_a[i] > pos_b[i])
+            return fail(c, BDX_EINVAL, "query " + std::to_string(i) + ": tid < 0, pos_a < 1 or pos_a > pos_b");
+    if (n > ((size_t)1 << 31)) return fail(c, BDX_ELIMIT, "more than 2^31 queries in one call");
+    const int nkeys = by_library ? c->nlibs : c->nbams;
+    // (a context with one library / one file never copies the respective column: every read is key 0 there)
+    const uint8_t* key = nkeys > 1 ? (by_library ? c->d.lib : c->d.bam) : nullptr;
+    // K1 calls a pair normal only if (float)|isize| is not above its library's upper cutoff (-l's remaps included: NORMAL_RF needs it
+    // below the cutoff) and |isize| <= -m.  Every such integer lies below the float that follows the cutoff (a NaN cutoff bounds nothing).
+    double ub = -1.0;
+    for (const bdx_lib& l : c->libs) {
+        const float u = l.uppercutoff;
+        ub = std::max(ub, std::isnan(u) || u == INFINITY ? 2147483647.0 : std::ceil((double)std::nextafter(u, INFINITY)) - 1.0);
+    }
+    const int32_t lmax = (int32_t)std::max(-1.0, std::min<double>({ub, (double)c->opts.max_sd, 2147483647.0}));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cbytes = n * (size_t)nkeys * 4;
+    HIPCHK(c, c->b_jq.ensure(n * 12));
+    HIPCHK(c, c->b_jc.ensure(cbytes));
+    hipStream_t s = c->stream;
+    int32_t* q = c->b_jq.as<int32_t>();
+    HIPCHK(c, hipMemcpyAsync(q, tid, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(q + n, pos_a, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(q + 2 * n, pos_b, n * 4, hipMemcpyHostToDevice, s));
+    K8Params p{};
+    p.tid = c->d.tid; p.pos = c->d.pos; p.isize = c->d.isize; p.key = key; p.cls = c->b_cls.as<uint8_t>(); p.n = c->n;
+    p.q_tid = q; p.q_a = q + n; p.q_b = q + 2 * n; p.nq = (uint32_t)n; p.nkeys = nkeys; p.lmax = lmax; p.counts = c->b_jc.as<uint32_t>();
+    launch_k8(p, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(counts, p.counts, cbytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return BDX_OK;
+}
+
 int bdx_set_process_option(const char* name, int value) {
     if (!name) return BDX_EINVAL;
     if (!strcmp(name, "pin_malloc")) { PinBuf::registered_switch().store(value == 0); return BDX_OK; }
@@ -2212,7 +2262,8 @@ int bdx_set_process_option(const char* name, int value) {
 
 int bdx_warm_up(int device) {
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
-    warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k9(nullptr);
+    warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k8(nullptr);
+    warm_k9(nullptr);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? BDX_OK : BDX_EHIP;
 }
 

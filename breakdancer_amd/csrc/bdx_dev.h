@@ -188,7 +188,21 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
+// K8 (k8_junction.hip): normal pairs covering SV junctions, per query and key (bdx_count_junction_pairs)
+struct K8Params {
+    const int32_t *tid, *pos, *isize;   // the resident store, sorted by (tid, pos)
+    const uint8_t* key;                 // library or source-file column; read only when nkeys > 1
+    const uint8_t* cls;                 // K1's class bytes
+    uint64_t n;
+    const int32_t *q_tid, *q_a, *q_b;   // queries: chromosome, junctions a <= b (1-based)
+    uint32_t nq;
+    int nkeys;                          // 1..255
+    int32_t lmax;                       // no normal pair's |isize| exceeds it
+    uint32_t* counts;                   // [nq][nkeys]
+};
+
 // launchers (host side, defined in the .hip files)
+void launch_k8(const K8Params& p, hipStream_t s);
 void launch_k1(const K1Params& p, int grid, size_t lds, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 size_t k1_lds_bytes(int nlibs, int nbams, int nkeys);
 void launch_finalize(const FinalizeParams& p, hipStream_t s, bool second_level = true);

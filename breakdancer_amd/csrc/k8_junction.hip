@@ -1,0 +1,122 @@
+// K8 -- reference-supporting read pairs at SV junctions (bdx_count_junction_pairs; the input of the CLI's --vcf DR / GT columns).
+// No counterpart in the reference: its table has no genotype, and a converter outside the run would have to read the BAMs again.
+//
+// A query is one chromosome and one or two junctions a <= b (the boundary between base p and p + 1, 1-based).  A read counts for
+// the query when K1 marked it BDX_CLS_NORMAL_LEFT (each normal pair once, by its leftmost mate) and its fragment [s + 1, s + |isize|]
+// (s = 0-based pos) covers p and p + 1 of at least one of the junctions.  A normal pair's |isize| never exceeds lmax (the largest
+// library cutoff, and -m: host side), so only reads with s in [p + 1 - lmax, p - 1] can cover p.  The two junctions' windows are
+// scanned as one when they overlap; otherwise separately, and then a read of the first window cannot reach b, nor one of the second a.
+//
+// One wavefront per query.  The store is sorted by (tid, pos) (BamMerger's order, which every stage relies on): a window's first record
+// is found by a 64-ary search -- the 64 lanes probe 64 evenly spaced records and one ballot says how many lie in front, ~5 rounds of
+// one load each for 2^27 records --, then the lanes stride the window 64 records at a time until a record lies behind it.  Counts per
+// key: one ballot + popcount per step with one key; per-wave LDS counters otherwise (at most 255 keys).
+#include <hip/hip_runtime.h>
+
+#include "../../include/bdx.h"
+#include "bdx_dev.h"
+#include "bdx_shard.h"
+
+namespace bdx {
+
+namespace {
+
+constexpr int kK8Waves = 4;
+
+// first index in [0, n) whose (tid, pos) is not below (t, p); the answer is wave-uniform
+__device__ uint64_t k8_lower_bound(const int32_t* __restrict__ tid, const int32_t* __restrict__ pos, uint64_t n, int32_t t, int64_t p) {
+    const int lane = lane_id();
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t len = hi - lo;
+        const bool last = len <= 64;
+        // (len > 64: lane l probes lo + len * (l + 1) / 65, strictly increasing and inside [lo, hi))
+        const uint64_t idx = last ? lo + (uint64_t)lane : lo + len * (uint64_t)(lane + 1) / 65;
+        bool below = false;
+        if (idx < hi) {
+            const int32_t ti = tid[idx];
+            below = ti < t || (ti == t && (int64_t)pos[idx] < p);
+        }
+        const int c = popc64(ballot64(below));
+        if (last) return lo + (uint64_t)c;
+        const uint64_t lo0 = lo;
+        if (c > 0) lo = lo0 + len * (uint64_t)c / 65 + 1;
+        if (c < 64) hi = lo0 + len * (uint64_t)(c + 1) / 65;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ bool k8_covers(int64_t s, int64_t L, int64_t p) { return s + 1 <= p && p + 1 <= s + L; }
+
+__global__ __launch_bounds__(kK8Waves * 64) void k8_junction_kernel(K8Params p) {
+    extern __shared__ uint32_t s_cnt[];   // [kK8Waves][nkeys] (nkeys > 1 only)
+    const int lane = lane_id(), w = wave_id();
+    const uint32_t q = blockIdx.x * kK8Waves + (uint32_t)w;
+    const bool live = q < p.nq;   // (wave-uniform: every wave reaches the barriers)
+    const int nkeys = p.nkeys;
+    uint32_t* cnt = s_cnt + w * nkeys;
+    const bool many = nkeys > 1;
+    if (many) {
+        for (int k = lane; k < nkeys; k += 64) cnt[k] = 0;
+        __syncthreads();
+    }
+    uint32_t single = 0;
+    if (live && p.lmax >= 2 && p.n) {
+        const int32_t t = p.q_tid[q];
+        const int64_t a = p.q_a[q], b = p.q_b[q], lm = p.lmax;
+        // windows of read starts: [a + 1 - lm, a - 1] and [b + 1 - lm, b - 1], as one when they overlap or touch
+        const bool merged = b + 1 - lm <= a;
+        const int nwin = merged ? 1 : 2;
+        for (int wi = 0; wi < nwin; ++wi) {
+            const int64_t wlo = (wi == 0 ? a : b) + 1 - lm, whi = (wi == 0 && !merged ? a : b) - 1;
+            const bool test_a = wi == 0, test_b = merged || wi == 1;
+            for (uint64_t base = k8_lower_bound(p.tid, p.pos, p.n, t, wlo);; base += 64) {
+                const uint64_t i = base + (uint64_t)lane;
+                bool in = i < p.n;
+                int64_t s = 0;
+                if (in) {
+                    s = p.pos[i];
+                    in = p.tid[i] == t && s <= whi;
+                }
+                const uint64_t m_in = ballot64(in);
+                bool hit = false;
+                uint32_t key = 0;
+                if (in && (p.cls[i] & BDX_CLS_NORMAL_LEFT)) {
+                    const int64_t v = p.isize[i], L = v < 0 ? -v : v;
+                    hit = (test_a && k8_covers(s, L, a)) || (test_b && k8_covers(s, L, b));
+                    if (hit && many) {
+                        key = p.key[i];
+                        key = key < (uint32_t)nkeys ? key : 0u;   // (an index out of range counts as 0, like everywhere in the store)
+                    }
+                }
+                if (many) {
+                    if (hit) atomicAdd(&cnt[key], 1u);
+                } else {
+                    single += (uint32_t)popc64(ballot64(hit));
+                }
+                if (m_in != ~0ull) break;   // (sorted: the first record behind the window ends it)
+            }
+        }
+    }
+    if (many) {
+        __syncthreads();
+        if (live)
+            for (int k = lane; k < nkeys; k += 64) p.counts[(uint64_t)q * nkeys + k] = cnt[k];
+    } else if (live && lane == 0) {
+        p.counts[q] = single;
+    }
+}
+
+}  // namespace
+
+void launch_k8(const K8Params& p, hipStream_t s) {
+    if (!p.nq) return;
+    const size_t lds = p.nkeys > 1 ? (size_t)kK8Waves * p.nkeys * 4 : 0;
+    hipLaunchKernelGGL(k8_junction_kernel, dim3((p.nq + kK8Waves - 1) / kK8Waves), dim3(kK8Waves * 64), lds, s, p);
+}
+
+}  // namespace bdx
+
+// (bdx_warm_up: the HIP runtime loads a translation unit's device code at the first launch of any of its kernels)
+__global__ void k8_noop_kernel() {}
+namespace bdx { void warm_k8(hipStream_t s) { hipLaunchKernelGGL(k8_noop_kernel, dim3(1), dim3(64), 0, s); } }

@@ -33,6 +33,7 @@
 #include "dumps.h"
 #include "options.h"
 #include "producer.h"
+#include "vcf.h"
 
 using namespace bdhost;
 
@@ -175,6 +176,82 @@ void report_result(int status) {
 
 int run(int argc, char** argv);
 
+// --vcf: one record per printed row (svs[rows[k]] is row k + 1 of the table).  DV: the dominant type's pairs of the sample (library with
+// -a, else BAM file); DR: the normal pairs covering the call's junctions, counted on the GPU over the records the run holds -- on the
+// single context, or per rank of a sharded run on the rank that holds the chromosome.  A same-chromosome call is one query over both
+// junctions (a pair counts once); a CTX call two, added.  DR is unknown with -t (no read carries the normal-pair bit) and for a junction
+// on a chromosome the run did not read (only_tid >= 0: the -o chromosome).
+std::vector<VcfRecord> vcf_records(const Options& opts, const BamConfig& cfg, const std::vector<bdx_sv>& svs, const std::vector<size_t>& rows,
+                                   const std::vector<int32_t>& li, const std::vector<int32_t>& lp, bdx_ctx* ctx, const std::vector<bdx_dist*>& ranks,
+                                   const std::vector<int>& rank_of, int only_tid) {
+    const bool by_lib = opts.o.cn_lib != 0;
+    const size_t ns = by_lib ? cfg.num_libs() : cfg.num_bams();
+    std::vector<VcfRecord> out(rows.size());
+    std::vector<int32_t> q_tid, q_a, q_b;
+    std::vector<size_t> q_row;
+    auto held = [&](int t) { return t >= 0 && (only_tid < 0 || t == only_tid) && (ranks.empty() || (size_t)t < rank_of.size()); };
+    for (size_t k = 0; k < rows.size(); ++k) {
+        const bdx_sv& s = svs[rows[k]];
+        VcfRecord& r = out[k];
+        r.row = k + 1;
+        r.chr1 = s.chr[0]; r.pos1 = s.pos[0]; r.chr2 = s.chr[1]; r.pos2 = s.pos[1];
+        r.ori1 = std::to_string(s.fwd[0]) + "+" + std::to_string(s.rev[0]) + "-";
+        r.ori2 = std::to_string(s.fwd[1]) + "+" + std::to_string(s.rev[1]) + "-";
+        r.type = opts.sv_type(s.flag);
+        r.size = s.size; r.score = s.score; r.nreads = s.num_reads; r.af = s.allele_frequency;
+        r.dv.assign(ns, 0);
+        for (int i = 0; i < s.lib_count; ++i) {
+            const size_t lib = (size_t)li[s.lib_begin + i];
+            const size_t key = by_lib ? lib : cfg.library_config(lib).bam_file_index;
+            if (key < ns) r.dv[key] += lp[s.lib_begin + i];
+        }
+        r.dr.assign(ns, -1);
+        const bool same = s.chr[0] == s.chr[1];
+        if (opts.o.transchr_rearrange || !held(s.chr[0]) || !held(s.chr[1]) || s.pos[0] < 1 || s.pos[1] < 1) continue;
+        r.dr.assign(ns, 0);
+        if (same) {
+            q_tid.push_back(s.chr[0]); q_a.push_back(std::min(s.pos[0], s.pos[1])); q_b.push_back(std::max(s.pos[0], s.pos[1])); q_row.push_back(k);
+        } else {
+            for (int e = 0; e < 2; ++e) { q_tid.push_back(s.chr[e]); q_a.push_back(s.pos[e]); q_b.push_back(s.pos[e]); q_row.push_back(k); }
+        }
+    }
+    const size_t nq = q_tid.size();
+    if (!nq) return out;
+    std::vector<uint32_t> counts(nq * ns, 0);
+    if (ranks.empty()) {
+        check(ctx, bdx_count_junction_pairs(ctx, q_tid.data(), q_a.data(), q_b.data(), nq, by_lib ? 1 : 0, counts.data()), "bdx_count_junction_pairs");
+    } else {   // every rank counts the queries of its chromosomes on its own context, on a thread of its own
+        const size_t world = ranks.size();
+        std::vector<std::vector<size_t>> mine(world);
+        for (size_t i = 0; i < nq; ++i) mine[(size_t)rank_of[q_tid[i]]].push_back(i);
+        std::vector<std::string> errs(world);
+        std::vector<std::thread> th;
+        for (size_t r = 0; r < world; ++r) {
+            if (mine[r].empty()) continue;
+            th.emplace_back([&, r] {
+                const std::vector<size_t>& m = mine[r];
+                std::vector<int32_t> t(m.size()), a(m.size()), b(m.size());
+                for (size_t j = 0; j < m.size(); ++j) { t[j] = q_tid[m[j]]; a[j] = q_a[m[j]]; b[j] = q_b[m[j]]; }
+                std::vector<uint32_t> c(m.size() * ns);
+                // (one context per rank, the same for every chromosome: asking for the last sequence passes the feeding-order check whatever was fed)
+                bdx_ctx* rc = bdx_dist_chromosome(ranks[r], (int)rank_of.size() - 1);
+                const int st = rc ? bdx_count_junction_pairs(rc, t.data(), a.data(), b.data(), m.size(), by_lib ? 1 : 0, c.data()) : BDX_EINTERNAL;
+                if (st != BDX_OK) {
+                    errs[r] = std::string("bdx_count_junction_pairs on rank ") + std::to_string(r) + ": " + bdx_strerror(st) + (rc ? std::string(" (") + bdx_last_error(rc) + ")" : "");
+                    return;
+                }
+                for (size_t j = 0; j < m.size(); ++j) std::copy(c.begin() + j * ns, c.begin() + (j + 1) * ns, counts.begin() + m[j] * ns);
+            });
+        }
+        for (auto& t : th) t.join();
+        for (auto const& e : errs)
+            if (!e.empty()) throw std::runtime_error(e);
+    }
+    for (size_t i = 0; i < nq; ++i)
+        for (size_t k = 0; k < ns; ++k) out[q_row[i]].dr[k] += counts[i * ns + k];
+    return out;
+}
+
 }  // namespace
 
 // Releasing a GPU context takes the driver longer than the whole GPU path runs, and a process cannot return before its resources
@@ -259,6 +336,9 @@ int run(int argc, char** argv) {
             std::cout << "Error: no bams files in config file!\n";
             return 1;
         }
+        // --vcf: the file is opened before anything else is done -- an unwritable path fails here, before the GPU is touched
+        std::unique_ptr<VcfWriter> vcf;
+        if (!opts.vcf.empty()) vcf.reset(new VcfWriter(opts.vcf));
         // Decode threads: the work is CPU-bound on zlib (~375 MB/s of inflated bytes per core), so what counts is the number of
         // cores this process may really use -- the cgroup's CPU quota when there is one (a container with "16 CPUs" on a
         // 256-thread host: 16 threads 0.64 s, 32 0.55 s, 64 0.70 s for 15 M records), else the hardware threads.  Twice that
@@ -280,6 +360,7 @@ int run(int argc, char** argv) {
         const std::vector<int> devices = gpu_list();
         const bool sharded = devices.size() > 1 && opts.chr.empty();
         std::vector<bdx_dist*> ranks(sharded ? devices.size() : 0, nullptr);
+        std::vector<int> rank_of;   // (sharded runs) chromosome -> rank
         struct RanksGuard {
             std::vector<bdx_dist*>& r;
             ~RanksGuard() { for (bdx_dist* d : r) if (d) bdx_dist_destroy(d); }
@@ -316,7 +397,7 @@ int run(int argc, char** argv) {
                 for (bdx_dist* r : ranks) bdx_dist_set_collect_support(r, 1);
             std::vector<uint64_t> weight(lengths.begin(), lengths.end());  // chromosomes -> ranks by sequence length
             weight.resize(ntids, 0);
-            std::vector<int> rank_of(ntids, 0);
+            rank_of.assign(ntids, 0);
             bdx_dist_plan(weight.data(), ntids, world, rank_of.data());
             // BAMs with their indexes: every rank pulls the BGZF ranges of ITS chromosomes and decodes them on ITS GPU (bdx_bamdec_*), as the
             // reference reads one chromosome through the index (io/RegionLimitedBamReader.hpp:43-71); several files are merged per
@@ -450,6 +531,17 @@ int run(int argc, char** argv) {
         std::vector<int32_t> li(nl), lp(nl), ck(nc);
         std::vector<float> cv(nc);
         check(ctx, bdx_get_sv_lists(ctx, li.data(), lp.data(), nl, ck.data(), cv.data(), nc), "bdx_get_sv_lists");
+        std::vector<size_t> printed_rows;
+        for (size_t i = 0; i < svs.size(); ++i)
+            if (svs[i].printed) printed_rows.push_back(i);
+        // (--vcf: the junction counts run before the trimmer starts, which must not run beside another call on the context)
+        std::vector<VcfRecord> vcf_rows;
+        if (vcf) {
+            const auto tv = now();
+            const int only_tid = opts.chr.empty() ? -1 : region_tid(cfg, opts.chr);   // (the producer has parsed the same argument)
+            vcf_rows = vcf_records(opts, cfg, svs, printed_rows, li, lp, ctx, ranks, rank_of, only_tid);
+            if (timing) fprintf(stderr, "[bdx timing] --vcf: junction counts of %zu rows %.4f s\n", printed_rows.size(), secs(tv, now()));
+        }
 
         // (a large run's pinned result tables go back while the table is printed: the process's end is that much shorter.  BDX_TRIM=0: kept)
         if (n_reads > (size_t)(8u << 20) && !want_dumps && !getenv("BDX_CLEAN_EXIT") && !(getenv("BDX_TRIM") && !strcmp(getenv("BDX_TRIM"), "0"))) {
@@ -539,9 +631,6 @@ int run(int argc, char** argv) {
         // A large table (a genome's: tens of thousands of rows, 0.7 us each through the stream's formatting) is written by several threads,
         // each into its own string stream that starts in the state the sequential loop would have reached at its first row; the strings
         // leave in order.  The dumps (-g / -d) keep the sequential loop.
-        std::vector<size_t> printed_rows;
-        for (size_t i = 0; i < svs.size(); ++i)
-            if (svs[i].printed) printed_rows.push_back(i);
         size_t fmt_threads = want_dumps || printed_rows.size() < 8192 ? 1 : std::min<size_t>(std::min<size_t>(io_threads, 8), printed_rows.size() / 2048);
         if (const char* ft = getenv("BDX_FORMAT_THREADS"))   // (tests, A/B: 1 = the sequential loop; n = n threads whatever the table's size)
             if (!want_dumps) fmt_threads = std::max<size_t>(1, std::min<size_t>((size_t)atoi(ft), std::max<size_t>(printed_rows.size(), 1)));
@@ -585,6 +674,21 @@ int run(int argc, char** argv) {
                     if (fastq) fastq->write(d);
                 }
             }
+        }
+        if (vcf) {
+            std::vector<std::string> contigs;
+            std::vector<uint32_t> lengths;
+            read_targets(cfg, contigs, lengths);
+            std::vector<std::string> samples;
+            if (opts.o.cn_lib)
+                for (size_t i = 0; i < cfg.num_libs(); ++i) samples.push_back(cfg.library_config(i).name);
+            else
+                for (auto const& b : cfg.bam_files()) {
+                    const size_t p = b.rfind("/");
+                    samples.push_back(p != std::string::npos ? b.substr(p + 1) : b);
+                }
+            vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(vcf_rows));
+            vcf.reset();
         }
         if (timing) {
             float ms[8] = {0};

@@ -60,6 +60,7 @@ void print_usage(const bdx_opts& o) {
         if (r.show_default) fprintf(stderr, "       -%c %s       %s [%d]\n", r.letter, arg, r.help, o.*(r.num));
         else fprintf(stderr, "       -%c %s       %s\n", r.letter, arg, r.help);
     }
+    fprintf(stderr, "       --vcf FILE     write the printed calls as VCF with per-sample genotypes (GT:GQ:PL:DR:DV)\n");
     fprintf(stderr, "\n");
 }
 
@@ -68,8 +69,15 @@ void print_usage(const bdx_opts& o) {
 Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
+    // (the reference's letters parse exactly as with getopt; --vcf is the one long option)
+    enum { kVcf = 256 };
+    static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {nullptr, 0, nullptr, 0}};
     int c;
-    while ((c = getopt(argc, argv, spec.c_str())) >= 0) {
+    while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
+        if (c == kVcf) {
+            vcf = optarg;
+            continue;
+        }
         const Row* row = nullptr;
         for (const Row& r : kRows)
             if (r.letter == c) row = &r;

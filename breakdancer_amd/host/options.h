@@ -1,5 +1,5 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
-// (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included.
+// (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long option --vcf.
 #pragma once
 #include <string>
 #include <vector>
@@ -15,6 +15,7 @@ struct Options {
     std::string bam_config_path;
     std::string prefix_fastq;    // -d
     std::string dump_BED;        // -g
+    std::string vcf;             // --vcf: the printed calls as VCF with per-sample genotypes (vcf.h)
     bdx_opts o;                  // numeric options in the C-ABI layout
     std::vector<std::string> orig_argv;
     int device = 0;              // env BDX_DEVICE

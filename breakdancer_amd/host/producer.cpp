@@ -1065,6 +1065,13 @@ void read_targets(const BamConfig& cfg, std::vector<std::string>& names, std::ve
     lengths = rd.target_lengths();
 }
 
+int region_tid(const BamConfig& cfg, const std::string& chr) {
+    if (cfg.num_bams() == 0) return -1;
+    ColumnReader rd(cfg.bam_files()[0], 1, nullptr);
+    int tid = -1, beg = 0, end = 0;
+    return parse_region(rd, chr, tid, beg, end) ? tid : -1;
+}
+
 void produce_merged_by_columns(const BamConfig& cfg, const std::string& chr, int threads, ReadStream& out) {
     const LibraryResolver libs(cfg);
     const size_t nb = cfg.num_bams();

@@ -1,0 +1,103 @@
+#include "vcf.h"
+
+#include <algorithm>
+#include <cmath>
+#include <stdexcept>
+
+namespace bdhost {
+
+Genotype call_genotype(int64_t dr, int64_t dv) {
+    Genotype g;
+    if (dr < 0 || dv < 0 || dr + dv == 0) return g;
+    static const double kAltP[3] = {0.01, 0.5, 0.99};
+    double l[3], best = -INFINITY;
+    for (int i = 0; i < 3; ++i) {
+        l[i] = (double)dv * std::log10(kAltP[i]) + (double)dr * std::log10(1.0 - kAltP[i]);
+        best = std::max(best, l[i]);
+    }
+    for (int i = 0; i < 3; ++i) g.pl[i] = (int64_t)std::round(-10.0 * (l[i] - best));
+    for (int i = 1; i < 3; ++i)
+        if (g.pl[i] < g.pl[g.gt]) g.gt = i;
+    int64_t s[3] = {g.pl[0], g.pl[1], g.pl[2]};
+    std::sort(s, s + 3);
+    g.gq = (int)std::min<int64_t>(99, s[1]);
+    g.called = true;
+    return g;
+}
+
+VcfWriter::VcfWriter(const std::string& path) : path_(path) {
+    f_ = fopen(path.c_str(), "w");
+    if (!f_) throw std::runtime_error("unable to open VCF output file '" + path + "'");
+}
+
+VcfWriter::~VcfWriter() {
+    if (f_) fclose(f_);
+}
+
+void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
+                      const std::vector<std::string>& samples, std::vector<VcfRecord> records) {
+    if (!f_) throw std::runtime_error("VCF output file '" + path_ + "' is already closed");
+    FILE* f = f_;
+    fprintf(f, "##fileformat=VCFv4.2\n##source=breakdancer-max-mi355x\n##command=");
+    for (size_t i = 0; i < argv.size(); ++i) fprintf(f, "%s%s", i ? " " : "", argv[i].c_str());
+    fprintf(f, "\n");
+    for (size_t t = 0; t < contigs.size(); ++t)
+        fprintf(f, "##contig=<ID=%s,length=%u>\n", contigs[t].c_str(), t < lengths.size() ? lengths[t] : 0u);
+    fputs("##FILTER=<ID=PASS,Description=\"All filters passed\">\n"
+          "##ALT=<ID=DEL,Description=\"Deletion\">\n"
+          "##ALT=<ID=INS,Description=\"Insertion\">\n"
+          "##ALT=<ID=INV,Description=\"Inversion\">\n"
+          "##ALT=<ID=ITX,Description=\"Intra-chromosomal translocation\">\n"
+          "##ALT=<ID=CTX,Description=\"Inter-chromosomal translocation\">\n"
+          "##INFO=<ID=IMPRECISE,Number=0,Type=Flag,Description=\"Imprecise structural variation: breakpoints from read-pair clusters\">\n"
+          "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant (the table's Type column)\">\n"
+          "##INFO=<ID=CHR2,Number=1,Type=String,Description=\"Chromosome of the second breakpoint (Chr2)\">\n"
+          "##INFO=<ID=POS2,Number=1,Type=Integer,Description=\"Position of the second breakpoint (Pos2)\">\n"
+          "##INFO=<ID=END,Number=1,Type=Integer,Description=\"End position of the variant (Pos2; same chromosome, Pos2 >= Pos1 only)\">\n"
+          "##INFO=<ID=SVLEN,Number=1,Type=Integer,Description=\"Difference in length between REF and ALT alleles (-Size; DEL and INS only)\">\n"
+          "##INFO=<ID=ORI1,Number=1,Type=String,Description=\"Reads on the + and - strand at the first breakpoint (Orientation1)\">\n"
+          "##INFO=<ID=ORI2,Number=1,Type=String,Description=\"Reads on the + and - strand at the second breakpoint (Orientation2)\">\n"
+          "##INFO=<ID=NREADS,Number=1,Type=Integer,Description=\"Read pairs supporting the call (num_Reads)\">\n"
+          "##INFO=<ID=BDAF,Number=1,Type=Float,Description=\"BreakDancer allele frequency (Allele_frequency)\">\n"
+          "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+          "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: second-smallest PL, capped at 99\">\n"
+          "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods (binomial, alt-read probability 0.01/0.5/0.99)\">\n"
+          "##FORMAT=<ID=DR,Number=1,Type=Integer,Description=\"Normal read pairs whose fragment covers a breakpoint junction\">\n"
+          "##FORMAT=<ID=DV,Number=1,Type=Integer,Description=\"Read pairs supporting the call (the dominant type's pairs)\">\n",
+          f);
+    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT");
+    for (auto const& s : samples) fprintf(f, "\t%s", s.c_str());
+    fprintf(f, "\n");
+    std::stable_sort(records.begin(), records.end(),
+                     [](const VcfRecord& x, const VcfRecord& y) { return x.chr1 != y.chr1 ? x.chr1 < y.chr1 : x.pos1 < y.pos1; });
+    auto name = [&](int t) { return t >= 0 && (size_t)t < contigs.size() ? contigs[t] : std::to_string(t); };
+    for (auto const& r : records) {
+        const std::string type = r.type.empty() ? "." : r.type;
+        fprintf(f, "%s\t%d\tBDX%zu\tN\t%s\t%d\tPASS\tIMPRECISE;SVTYPE=%s;CHR2=%s;POS2=%d", name(r.chr1).c_str(), r.pos1, r.row,
+                r.type.empty() ? "." : ("<" + r.type + ">").c_str(), r.score, type.c_str(), name(r.chr2).c_str(), r.pos2);
+        if (r.chr2 == r.chr1 && r.pos2 >= r.pos1) fprintf(f, ";END=%d", r.pos2);
+        if (r.type == "DEL" || r.type == "INS") fprintf(f, ";SVLEN=%lld", -(long long)r.size);
+        fprintf(f, ";ORI1=%s;ORI2=%s;NREADS=%d;BDAF=", r.ori1.c_str(), r.ori2.c_str(), r.nreads);
+        if (std::isfinite(r.af)) fprintf(f, "%.6g", (double)r.af);
+        else fputs(".", f);
+        fputs("\tGT:GQ:PL:DR:DV", f);
+        for (size_t k = 0; k < samples.size(); ++k) {
+            const int64_t dr = k < r.dr.size() ? r.dr[k] : -1, dv = k < r.dv.size() ? r.dv[k] : 0;
+            const Genotype g = call_genotype(dr, dv);
+            static const char* kGt[3] = {"0/0", "0/1", "1/1"};
+            if (g.called)
+                fprintf(f, "\t%s:%d:%lld,%lld,%lld:", kGt[g.gt], g.gq, (long long)g.pl[0], (long long)g.pl[1], (long long)g.pl[2]);
+            else
+                fputs("\t./.:.:.:", f);
+            if (dr < 0) fprintf(f, ".:%lld", (long long)dv);
+            else fprintf(f, "%lld:%lld", (long long)dr, (long long)dv);
+        }
+        fputs("\n", f);
+    }
+    const bool bad = ferror(f) != 0;
+    const int rc = fclose(f);
+    f_ = nullptr;
+    if (bad || rc != 0) throw std::runtime_error("writing VCF output file '" + path_ + "' failed");
+}
+
+}  // namespace bdhost

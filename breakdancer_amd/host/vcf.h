@@ -1,0 +1,50 @@
+// --vcf: the printed calls as VCFv4.2 with per-sample genotypes (GT:GQ:PL:DR:DV).  No counterpart in the reference, whose table
+// carries the supporting pairs of a call (DV) but not the normal pairs that cover its breakpoints (DR): those are counted on the GPU
+// over the run's resident records (bdx_count_junction_pairs).
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+namespace bdhost {
+
+// Biallelic binomial model, alt-read probability 0.01 / 0.5 / 0.99 for 0/0, 0/1, 1/1:
+//   log10 L(g) = dv log10(p_g) + dr log10(1 - p_g);  PL_g = round(-10 (log10 L(g) - max log10 L))  (halves away from zero);
+//   GT = the smallest PL (ties: the lower genotype), GQ = min(99, second-smallest PL).  dr < 0 (unknown) or dr + dv == 0: no call.
+struct Genotype {
+    bool called = false;
+    int gt = 0;        // 0 = 0/0, 1 = 0/1, 2 = 1/1
+    int gq = 0;
+    int64_t pl[3] = {0, 0, 0};
+};
+Genotype call_genotype(int64_t dr, int64_t dv);
+
+// one printed row of the table
+struct VcfRecord {
+    size_t row = 0;                  // 1-based row number among the printed rows (ID = BDX<row>)
+    int chr1 = 0, pos1 = 0, chr2 = 0, pos2 = 0;
+    std::string ori1, ori2, type;
+    int size = 0, score = 0, nreads = 0;
+    float af = 0;
+    std::vector<int64_t> dr, dv;     // per sample; dr < 0: unknown ('.')
+};
+
+class VcfWriter {
+public:
+    // opens (truncates) the file at once: an unwritable path fails before any work is done
+    explicit VcfWriter(const std::string& path);
+    ~VcfWriter();
+    VcfWriter(const VcfWriter&) = delete;
+    VcfWriter& operator=(const VcfWriter&) = delete;
+    // header + records, sorted by (chr1, pos1) with ties in row order; `contigs` are the reference sequences (names are also the
+    // records' CHROM / CHR2 values); the file is closed afterwards
+    void write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
+               const std::vector<std::string>& samples, std::vector<VcfRecord> records);
+
+private:
+    std::string path_;
+    FILE* f_ = nullptr;
+};
+
+}  // namespace bdhost

@@ -509,6 +509,17 @@ typedef struct bdx_insert_stats {
 } bdx_insert_stats;
 int bdx_insert_size_stats(int device, const double* x, const uint32_t* offsets, int nlibs, bdx_insert_stats* out);
 
+/* Reference-supporting read pairs at SV junctions: no counterpart in the reference (the input of --vcf's DR / GT).
+ * Query i: chromosome tid[i], junctions pos_a[i] <= pos_b[i] (1-based; pos_a == pos_b: one junction).
+ * counts[i * nkeys + k]: pairs of key k (library with by_library, else BAM file; nkeys = nlibs / nbams) that the last run counted as
+ * normal pairs (BDX_CLS_NORMAL_LEFT, each pair once by its leftmost mate) whose fragment [pos+1, pos+|isize|] covers base p and p+1
+ * of at least one junction p of the query.  After bdx_run, or on a rank's context (bdx_dist_chromosome) after bdx_dist_run: that
+ * rank's chromosomes.  A chromosome the context holds no reads of counts 0.
+ * BDX_ESTATE before a run has classified the reads the context holds (or while a sizing pass is in flight); BDX_EINVAL for a null
+ * array with n > 0, tid < 0, pos_a < 1 or pos_a > pos_b.  Not beside another call on the same context (bdx_trim_results included). */
+int bdx_count_junction_pairs(bdx_ctx* ctx, const int32_t* tid, const int32_t* pos_a, const int32_t* pos_b, size_t n,
+                             int by_library, uint32_t* counts);
+
 /* device the context is bound to and the HIP stream it launches on (as void*), for callers that time it */
 int bdx_device(const bdx_ctx* ctx);
 void* bdx_stream(const bdx_ctx* ctx);
