@@ -19,6 +19,28 @@ WG_OPTS = [dict(), dict(transchr_rearrange=1), dict(cn_lib=1, print_af=1), dict(
 
 dev_total = [0]
 
+# bdx_dist_phase_name: thirteen of the eighteen timing slots carry a name, five are empty (bench.py and the tools read them by name)
+PHASE_NAMES = {0: "pass1_compaction_first_reads", 1: "allreduce_statistics_first_reads_exchange_counts", 4: "rebase_and_region_cut",
+               5: "allreduce_regions", 6: "globalize_and_pack", 7: "alltoall_join_records_census_windows", 10: "joins_components_walk_table",
+               11: "allreduce_package_sizes", 13: "gather_packages_to_rank0", 14: "rank0_only_merge", 15: "replay_route",
+               16: "rank0_only_host_walk", 17: "rank0_only_device_walk_of_gathered_groups"}
+
+
+def check_protocol_shape(util, gathers):
+    """a run over several ranks that has a region enters FIVE collectives on every rank -- three all-reduces (A, B, S), one
+    all-to-all (X) and one gather (G) -- and six on the replay route, whose region records and compact records travel in a gather each"""
+    ranks = util._sharded_run._ranks
+    assert len(ranks) > 1
+    for r, d in enumerate(ranks):
+        c = d.collectives()
+        assert (c["allreduce"], c["alltoall"], c["gather"]) == (3, 1, gathers), (r, c)
+    assert ranks[0].phase_names() == [PHASE_NAMES.get(i, "") for i in range(18)]
+
+
+def has_region(run):
+    """(a negative -s registers a read-less region 0 that is not one of the sharded run's: one more is asked for)"""
+    return run.n_regions > (1 if run.opts["min_len"] < 0 else 0)
+
 
 @pytest.mark.parametrize("seed", range(24))
 def test_staged_whole_genome_equals_single_run(seed):
@@ -71,6 +93,8 @@ def test_sharded_run_over_five_and_eight_ranks(seed):
             n_ctx, n_travel = expected_ctx_travel(run, world)
             ex = keep[0].exchange
             assert sum(e["ctx_records_sent"] for e in ex) == n_travel == sum(e["ctx_records_received"] for e in ex)
+            if has_region(run) and not util.was_replayed():
+                check_protocol_shape(util, 1)
 
 
 def test_staged_chr21_all_sequences():
@@ -102,6 +126,8 @@ def test_only_inter_chromosomal_records_cross_ranks():
         ex = keep[0].exchange
         n_ctx, n_travel = expected_ctx_travel(run, 3)
         assert sum(e["ctx_records_sent"] for e in ex) == n_travel == sum(e["ctx_records_received"] for e in ex)
+        if has_region(run) and not util.was_replayed():
+            check_protocol_shape(util, 1)
         assert n_ctx > 5000 and 0 < n_travel < n_ctx                      # at most one mate of a pair travels, none inside a rank
         assert n_ctx < 0.01 * run.n_merged or kw                          # ... a sliver of the reads
         if not kw:
@@ -200,9 +226,12 @@ def test_sharded_run_with_read_names_seen_more_than_twice(seed):
     replayed = 0
     for i, o in enumerate((osets[seed % len(osets)], dict(transchr_rearrange=1, min_read_pair=1), dict(min_read_pair=1, buffer_size=1))):
         run = oracle_case(cfg, streams, targets, make_opts(score_threshold=-1, **o))
-        util = sharded_from_oracle(run, world=1 + (seed + i) % 3)
+        world = 1 + (seed + i) % 3
+        util = sharded_from_oracle(run, world=world)
         compare(run, util, check_cls=False)
         replayed += util.was_replayed()
+        if world > 1 and has_region(run) and util.was_replayed():
+            check_protocol_shape(util, 2)
     assert replayed > 0
 
 
@@ -222,9 +251,12 @@ def test_sharded_run_returns_the_supporting_reads(seed):
         if o.get("min_len", 0) < 0:
             continue
         run = oracle_case(cfg, streams, targets, make_opts(score_threshold=-1, **o))
-        util = sharded_from_oracle(run, world=1 + (seed + i) % 3, support=True, collide=3 if seed == 3 else 0)
+        world = 1 + (seed + i) % 3
+        util = sharded_from_oracle(run, world=world, support=True, collide=3 if seed == 3 else 0)
         compare(run, util, check_cls=False)
         compare_support(run, util)
+        if world > 1 and has_region(run):   # (supporting reads are the read-level walk's: the replay route, whatever the names look like)
+            check_protocol_shape(util, 2)
         done += 1
     assert done >= 2
 
