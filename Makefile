@@ -28,7 +28,7 @@ bin/breakdancer-max: $(HOSTCOMMON) $(HOST)/main.cpp $(wildcard $(HOST)/*.h) brea
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOSTCOMMON) $(HOST)/main.cpp -Lbreakdancer_amd -lbdx -lz -Wl,-rpath,'$$ORIGIN/../breakdancer_amd' -Wl,-rpath,/opt/rocm/lib
 
-bin/bdx-inflate-check: $(HOST)/inflate_check_main.cpp $(HOST)/fast_inflate.cpp $(HOST)/fast_inflate.h
+bin/bdx-inflate-check: $(HOST)/inflate_check_main.cpp $(HOST)/fast_inflate.cpp $(HOST)/fast_inflate.h $(HOST)/bgzf.h
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -O3 -o $@ $(HOST)/inflate_check_main.cpp $(HOST)/fast_inflate.cpp -lz
 
@@ -37,7 +37,7 @@ bin/bdx-feed-probe: tools/feed_probe.hip
 	@mkdir -p bin
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -mavx2 -o $@ $< -lpthread
 
-bin/bam2cfg: $(HOST)/bam2cfg_main.cpp $(HOST)/bam_reader.cpp $(HOST)/bam_reader.h breakdancer_amd/libbdx.so
+bin/bam2cfg: $(HOST)/bam2cfg_main.cpp $(HOST)/bam_reader.cpp $(HOST)/bam_reader.h $(HOST)/bgzf.h breakdancer_amd/libbdx.so
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/bam2cfg_main.cpp $(HOST)/bam_reader.cpp -Lbreakdancer_amd -lbdx -lz -lpthread -Wl,-rpath,'$$ORIGIN/../breakdancer_amd' -Wl,-rpath,/opt/rocm/lib
 

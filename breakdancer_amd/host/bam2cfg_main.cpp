@@ -8,12 +8,8 @@
 // mates mapped to the same reference, proper-pair bit set.  Records come from this build's own BGZF/BAM reader instead
 // of a `samtools view` pipe.  Output lines follow the order of the @RG header lines (the Perl script walks a hash).
 // Not carried over: -h (PNG histograms through GD::Graph), -C (SOLiD orientation rules), MAQ-era Aq:i / MF:i tags.
-#include <fcntl.h>
 #include <getopt.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
 #include <unistd.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <cmath>
@@ -339,120 +335,18 @@ struct DeviceRecords {
     bool whole_file = false;   // the stretch reached the end of the file
 };
 
-struct Mapped {
-    const uint8_t* p = nullptr;
-    size_t n = 0;
-    int fd = -1;
-    explicit Mapped(const std::string& path) {
-        fd = open(path.c_str(), O_RDONLY);
-        struct stat sb;
-        if (fd < 0 || fstat(fd, &sb) != 0) {
-            if (fd >= 0) close(fd);
-            throw std::runtime_error("cannot open " + path);
-        }
-        n = (size_t)sb.st_size;
-        if (n) {
-            void* m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) {
-                close(fd);
-                throw std::runtime_error("cannot map " + path);
-            }
-            p = (const uint8_t*)m;
-        }
-    }
-    ~Mapped() {
-        if (p) munmap((void*)p, n);
-        if (fd >= 0) close(fd);
-    }
-    Mapped(const Mapped&) = delete;
-    Mapped& operator=(const Mapped&) = delete;
-};
-
-inline uint32_t rd16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-inline uint32_t rd32(const uint8_t* p) { return rd16(p) | (rd16(p + 2) << 16); }
-
-struct Member { size_t off, total, payload_off, payload_len; uint32_t ulen; };
-// the BGZF member at `off` (RFC 1952 header with the BC extra field, SAM specification 4.1); false at the end of the file
-bool member_at(const Mapped& f, size_t off, Member& m, const std::string& path) {
-    if (off >= f.n) return false;
-    const uint8_t* h = f.p + off;
-    if (off + 18 > f.n || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) throw std::runtime_error("not a BGZF file: " + path);
-    const size_t xlen = rd16(h + 10);
-    if (off + 12 + xlen > f.n) throw std::runtime_error("truncated BGZF file: " + path);
-    int bsize = -1;
-    for (size_t x = 12; x + 4 <= 12 + xlen;) {
-        const size_t slen = rd16(h + x + 2);
-        if (h[x] == 'B' && h[x + 1] == 'C' && slen == 2) bsize = (int)rd16(h + x + 4);
-        x += 4 + slen;
-    }
-    if (bsize < 0) throw std::runtime_error("BGZF block without BC field: " + path);
-    m.off = off;
-    m.total = (size_t)bsize + 1;
-    if (m.total < 12 + xlen + 8 || off + m.total > f.n) throw std::runtime_error("truncated BGZF file: " + path);
-    m.payload_off = off + 12 + xlen;
-    m.payload_len = m.total - 12 - xlen - 8;
-    m.ulen = rd32(h + m.total - 4);
-    if (m.ulen > 65536) throw std::runtime_error("BGZF block larger than 64 KiB: " + path);
-    return true;
-}
-
-// Where the first record lies: the member that holds it and its offset in that member's inflated bytes.  The header is inflated with
-// zlib (a few members) and measured: magic, l_text, text, n_ref, and per reference l_name, name, l_ref (SAM specification 4.2)
-void first_record(const Mapped& f, const std::string& path, size_t* member_off, uint64_t* rec_off) {
-    std::vector<uint8_t> text;
-    std::vector<size_t> starts, offs;   // inflated offset and file offset of every member read so far
-    size_t off = 0;
-    auto more = [&]() {
-        Member m;
-        if (!member_at(f, off, m, path)) throw std::runtime_error("truncated BAM header: " + path);
-        starts.push_back(text.size());
-        offs.push_back(off);
-        const size_t at = text.size();
-        text.resize(at + m.ulen);
-        z_stream z{};
-        if (inflateInit2(&z, -15) != Z_OK) throw std::runtime_error("zlib");
-        z.next_in = const_cast<Bytef*>(f.p + m.payload_off);
-        z.avail_in = (uInt)m.payload_len;
-        z.next_out = text.data() + at;
-        z.avail_out = m.ulen;
-        const int rc = inflate(&z, Z_FINISH);
-        inflateEnd(&z);
-        if (rc != Z_STREAM_END || z.avail_out != 0) throw std::runtime_error("corrupt BGZF block in the header of " + path);
-        off += m.total;
-    };
-    auto need = [&](size_t n) { while (text.size() < n) more(); };
-    need(12);
-    if (memcmp(text.data(), "BAM\1", 4) != 0) throw std::runtime_error("not a BAM file: " + path);
-    size_t q = 8 + (size_t)rd32(text.data() + 4);
-    need(q + 4);
-    const uint32_t n_ref = rd32(text.data() + q);
-    q += 4;
-    for (uint32_t i = 0; i < n_ref; ++i) {
-        need(q + 4);
-        q += 4 + (size_t)rd32(text.data() + q) + 4;
-        need(q);
-    }
-    // (the header ends a member: the first record opens the next one)
-    if (q == text.size()) { *member_off = off; *rec_off = 0; return; }
-    size_t k = starts.size() - 1;
-    while (starts[k] > q) --k;
-    *member_off = offs[k];
-    *rec_off = q - starts[k];
-}
-
-void decode_prefix(const std::string& path, int device, const std::vector<std::string>& rg_ids, int n_targets, bool mapq_only, size_t max_members,
-                   DeviceRecords& out) {
-    Mapped f(path);
-    size_t off = 0;
-    uint64_t rec_off = 0;
-    first_record(f, path, &off, &rec_off);
+// rd: the file's reader, for where the first record lies (the member that holds it, its offset in that member's inflated bytes)
+void decode_prefix(const bdhost::BamReader& rd, int device, const std::vector<std::string>& rg_ids, bool mapq_only, size_t max_members, DeviceRecords& out) {
+    const std::string& path = rd.path();
+    const bdhost::MappedFile f(path, false);
+    size_t off = rd.first_member_offset();
     const size_t kPieceMembers = 1024, kPieceBytes = (size_t)4 << 20;
     std::vector<const char*> idp;
     std::vector<uint8_t> index;
     for (size_t i = 0; i < rg_ids.size(); ++i) { idp.push_back(rg_ids[i].c_str()); index.push_back((uint8_t)i); }
     bdx_bamdec_params p{};
     p.device = device;
-    p.n_targets = n_targets;
+    p.n_targets = (int)rd.target_names().size();
     p.only_tid = -1;
     p.n_read_groups = (uint32_t)rg_ids.size();
     p.rg_ids = idp.empty() ? nullptr : idp.data();
@@ -460,10 +354,10 @@ void decode_prefix(const std::string& path, int device, const std::vector<std::s
     p.fallback_lib = kUnknownRg;
     p.missing_lib_plus1 = (int32_t)kNoTag + 1;
     p.record_mode = 1 | (mapq_only ? 2 : 0);
-    p.first_record_offset = rec_off;
+    p.first_record_offset = rd.first_record_offset();
     p.batch_blocks = std::min<size_t>(std::max<size_t>(max_members, 64), 4096);
     p.ring_bytes = 4 * (p.batch_blocks + kPieceMembers + 64) * 65536;
-    p.expected_bytes = std::min(f.n - std::min(f.n, off), max_members * 65536);
+    p.expected_bytes = std::min(f.size() - std::min(f.size(), off), max_members * 65536);
     p.piece_bytes = kPieceBytes + 65536;
     p.piece_blocks = kPieceMembers;
     bdx_bamdec* dec = nullptr;
@@ -477,32 +371,26 @@ void decode_prefix(const std::string& path, int device, const std::vector<std::s
     bool at_end = false;
     while (!at_end && fed < max_members) {
         // a piece: whole members, at most kPieceMembers of them and kPieceBytes
-        std::vector<Member> ms;
-        size_t bytes = 0;
+        std::vector<bdx_bgzf_block> blocks;   // (of those that inflate to something: not the end-of-file marker, flush blocks)
+        size_t members = 0, bytes = 0;
         const size_t begin = off;
-        while (ms.size() < kPieceMembers && fed + ms.size() < max_members) {
-            Member m;
-            if (!member_at(f, off, m, path)) { at_end = true; break; }
-            if (!ms.empty() && bytes + m.total > kPieceBytes) break;
-            ms.push_back(m);
+        while (members < kPieceMembers && fed + members < max_members) {
+            bdhost::BgzfMember m;
+            if (!bdhost::bgzf_member_at(f.data(), f.size(), off, path, &m)) break;
+            if (members && bytes + m.total > kPieceBytes) break;
+            if (m.ulen) blocks.push_back(bdx_bgzf_block{bytes + m.payload_off, (uint32_t)m.payload_len, m.ulen});
+            ++members;
             bytes += m.total;
             off += m.total;
         }
-        if (!at_end && off >= f.n) at_end = true;
+        at_end = off >= f.size();
         void* buf = nullptr;
         bdx_bgzf_block* tab = nullptr;
         check(bdx_bamdec_acquire(dec, std::max<size_t>(bytes, 1), kPieceMembers, &buf, &tab), "bdx_bamdec_acquire");
-        if (bytes) memcpy(buf, f.p + begin, bytes);
-        size_t nb = 0;
-        for (auto const& m : ms) {
-            if (!m.ulen) continue;   // (the end-of-file marker, flush blocks)
-            tab[nb].offset = m.payload_off - begin;
-            tab[nb].payload_len = (uint32_t)m.payload_len;
-            tab[nb].inflated_len = m.ulen;
-            ++nb;
-        }
-        fed += ms.size();
-        check(bdx_bamdec_submit(dec, bytes, nb, at_end ? 1 : 0), "bdx_bamdec_submit");
+        if (bytes) memcpy(buf, f.data() + begin, bytes);
+        std::copy(blocks.begin(), blocks.end(), tab);
+        fed += members;
+        check(bdx_bamdec_submit(dec, bytes, blocks.size(), at_end ? 1 : 0), "bdx_bamdec_submit");
     }
     uint64_t n = 0;
     check(bdx_bamdec_finish(dec, &n), "bdx_bamdec_finish");
@@ -587,7 +475,7 @@ int main(int argc, char** argv) {
                 size_t members = std::max<size_t>(64, (size_t)(12.0 * (double)std::max<size_t>(1, sc.libs.size()) * (double)o.n * 256.0 / 65536.0) + 16);
                 for (;;) {
                     DeviceRecords dr;
-                    decode_prefix(fbam, o.device, ids, (int)rd.target_names().size(), o.use_mapq, members, dr);
+                    decode_prefix(rd, o.device, ids, o.use_mapq, members, dr);
                     Scan trial(o, forced, rd.header_text());
                     bool ended = false;
                     const std::string unknown("\x01");   // (a read group the header does not name: no library, the record only counts for the loop's exits)

@@ -1,11 +1,5 @@
 #include "bam_reader.h"
 
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <zlib.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -22,34 +16,13 @@ constexpr size_t kSegBytesDefault = 2u << 20;      // decompressed bytes per dec
 
 // test knobs: BDX_BAM_FILL_BLOCKS / BDX_BAM_SEG_BYTES shrink the batches / the decode segments so that small files go
 // through many batch hand-overs and many guessed record boundaries
-size_t env_or(const char* name, size_t dflt) {
-    const char* v = getenv(name);
-    const long long x = v ? atoll(v) : 0;
-    return x > 0 ? (size_t)x : dflt;
-}
 const size_t kMaxBlocksPerFill = env_or("BDX_BAM_FILL_BLOCKS", kMaxBlocksPerFillDefault);
 const size_t kSegBytes = env_or("BDX_BAM_SEG_BYTES", kSegBytesDefault);
-
-inline uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-inline uint16_t le16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 
 struct Block {
     size_t coff, clen;   // deflate payload within comp_
     size_t uoff, ulen;   // destination within buf_
 };
-
-void inflate_block(const uint8_t* src, size_t clen, uint8_t* dst, size_t ulen) {
-    z_stream zs;
-    memset(&zs, 0, sizeof(zs));
-    if (inflateInit2(&zs, -15) != Z_OK) throw std::runtime_error("zlib inflateInit2 failed");
-    zs.next_in = const_cast<Bytef*>(src);
-    zs.avail_in = (uInt)clen;
-    zs.next_out = dst;
-    zs.avail_out = (uInt)ulen;
-    const int rc = inflate(&zs, Z_FINISH);
-    inflateEnd(&zs);
-    if (rc != Z_STREAM_END || zs.avail_out != 0) throw std::runtime_error("corrupt BGZF block");
-}
 
 }  // namespace
 
@@ -109,43 +82,20 @@ void BamReader::Chunk::reserve(size_t n) {
 }
 
 BamReader::BamReader(const std::string& path, int threads, size_t fill_blocks)
-    : path_(path), threads_(threads < 1 ? 1 : threads), fill_blocks_(fill_blocks ? fill_blocks : kMaxBlocksPerFill) {
-    {
-        const int fd = open(path.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("Failed to open samfile " + path);
-        struct stat st;
-        if (fstat(fd, &st) != 0) { close(fd); throw std::runtime_error("Failed to open samfile " + path); }
-        map_size_ = (size_t)st.st_size;
-        if (map_size_) {
-            void* m = mmap(nullptr, map_size_, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { close(fd); throw std::runtime_error("Failed to map samfile " + path); }
-            map_ = (const uint8_t*)m;
-            madvise(m, map_size_, MADV_SEQUENTIAL);
-        }
-        close(fd);
-    }
-    if (!ensure(12) || memcmp(at(), "BAM\1", 4) != 0) throw std::runtime_error(path + " is not a valid bam file");
-    const uint32_t l_text = le32(at() + 4);
-    cur_ += 8;
-    if (!ensure((size_t)l_text + 4)) throw std::runtime_error(path + " is not a valid bam file");
-    header_text_.assign((const char*)at(), l_text);
-    cur_ += l_text;
-    const uint32_t n_ref = le32(at());
-    cur_ += 4;
-    for (uint32_t i = 0; i < n_ref; ++i) {
-        if (!ensure(4)) throw std::runtime_error(path + " is not a valid bam file");
-        const uint32_t l = le32(at());
-        if (!ensure((size_t)4 + l + 4)) throw std::runtime_error(path + " is not a valid bam file");
-        targets_.emplace_back((const char*)at() + 4, l ? l - 1 : 0);
-        cur_ += 4 + l + 4;
-    }
-    // the records follow: decode the rest of this batch now, and let the helper thread prepare the next one
-    records_mode_ = true;
+    : path_(path), file_(path), threads_(threads < 1 ? 1 : threads), fill_blocks_(fill_blocks ? fill_blocks : kMaxBlocksPerFill) {
+    BamHeader h = read_bam_header(file_.data(), file_.size(), path);
+    header_text_ = std::move(h.text);
+    targets_ = std::move(h.target_names);
+    first_member_offset_ = comp_off_ = h.first_member_offset;
+    first_record_offset_ = h.first_record_offset;
+    // the first batch is inflated and decoded now, from the first record on; the helper thread prepares the next one.  A file
+    // that ends with its header has no batch: the chunk stays empty and next() returns false
     Chunk& c = chunk_[cur_chunk_];
-    c.beg = cur_;
-    c.end = end_;
-    parse_chunk(c);
-    part_ = rec_ = 0;
+    if (fill(c)) {
+        if (c.end - c.beg < first_record_offset_) throw std::runtime_error(path + " is not a valid bam file");
+        c.beg += (size_t)first_record_offset_;
+        parse_chunk(c);
+    }
     const Chunk* cur = &c;
     const int other = cur_chunk_ ^ 1;
     next_ready_ = std::async(std::launch::async, [this, other, cur] { return fill_and_parse(chunk_[other], cur); });
@@ -155,7 +105,6 @@ BamReader::~BamReader() {
     if (next_ready_.valid()) {
         try { next_ready_.get(); } catch (...) {}
     }
-    if (map_) munmap((void*)map_, map_size_);
 }
 
 int BamReader::tid_of(const std::string& name) const {
@@ -168,42 +117,20 @@ bool BamReader::fill(Chunk& c) {
     std::vector<Block> blocks;
     size_t uoff = kFrontGap;
     // the compressed file is mapped, not read: the inflate threads take their input straight from the page cache
-    while (blocks.size() < fill_blocks_) {
-        const size_t avail = map_size_ - comp_off_;
-        if (avail == 0) break;
-        if (avail < 18) throw std::runtime_error("truncated BGZF file: " + path_);
-        const uint8_t* h = map_ + comp_off_;
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) throw std::runtime_error("not a BGZF file: " + path_);
-        const uint16_t xlen = le16(h + 10);
-        if (avail < (size_t)12 + xlen) throw std::runtime_error("truncated BGZF file: " + path_);
-        int bsize = -1;
-        for (size_t x = 12; x + 4 <= (size_t)12 + xlen;) {
-            const uint16_t slen = le16(h + x + 2);
-            if (h[x] == 'B' && h[x + 1] == 'C' && slen == 2) bsize = le16(h + x + 4);
-            x += 4 + (size_t)slen;
-        }
-        if (bsize < 0) throw std::runtime_error("BGZF block without BC field: " + path_);
-        const size_t total = (size_t)bsize + 1;
-        if (avail < total || total < (size_t)12 + xlen + 8) throw std::runtime_error("truncated BGZF file: " + path_);
-        const uint32_t isize = le32(h + total - 4);
-        if (isize > 65536) throw std::runtime_error("BGZF block larger than 64 KiB: " + path_);
-        Block b;
-        b.coff = comp_off_ + 12 + xlen;
-        b.clen = total - 12 - xlen - 8;
-        b.uoff = uoff;
-        b.ulen = isize;
-        uoff += isize;
-        comp_off_ += total;
-        if (isize) blocks.push_back(b);
+    BgzfMember m;
+    while (blocks.size() < fill_blocks_ && bgzf_member_at(file_.data(), file_.size(), comp_off_, path_, &m)) {
+        if (m.ulen) blocks.push_back(Block{comp_off_ + m.payload_off, m.payload_len, uoff, m.ulen});
+        uoff += m.ulen;
+        comp_off_ += m.total;
     }
     if (blocks.empty()) return false;
-    const uint8_t* comp = map_;
+    const uint8_t* comp = file_.data();
     c.beg = c.end = 0;
     c.reserve(std::max(uoff, kFrontGap + (size_t)40 * 1024 * 1024));  // sized once: fresh pages under eight writers are slow
     uint8_t* out = c.data.get();
     const int nt = (int)std::min<size_t>((size_t)threads_, blocks.size());
     if (nt <= 1) {
-        for (const Block& b : blocks) inflate_block(comp + b.coff, b.clen, out + b.uoff, b.ulen);
+        for (const Block& b : blocks) bgzf_inflate_zlib(comp + b.coff, b.clen, out + b.uoff, b.ulen, path_);
     } else {
         std::vector<std::thread> th;
         std::vector<std::string> errs(nt);
@@ -211,12 +138,12 @@ bool BamReader::fill(Chunk& c) {
             th.emplace_back([&, t] {
                 try {
                     for (size_t i = (size_t)t; i < blocks.size(); i += (size_t)nt)
-                        inflate_block(comp + blocks[i].coff, blocks[i].clen, out + blocks[i].uoff, blocks[i].ulen);
+                        bgzf_inflate_zlib(comp + blocks[i].coff, blocks[i].clen, out + blocks[i].uoff, blocks[i].ulen, path_);
                 } catch (std::exception const& e) { errs[t] = e.what(); }
             });
         for (auto& x : th) x.join();
         for (auto& e : errs)
-            if (!e.empty()) throw std::runtime_error(e + ": " + path_);
+            if (!e.empty()) throw std::runtime_error(e);
     }
     c.beg = kFrontGap;
     c.end = uoff;
@@ -237,24 +164,6 @@ void BamReader::attach_tail(Chunk& n, const uint8_t* src, size_t tail) {
         n.beg = kFrontGap;
         n.data = std::move(nd);
     }
-}
-
-// Header mode (constructor): the next batch is inflated synchronously, the unread bytes of the current one go in front.
-bool BamReader::advance() {
-    const int nxt = cur_chunk_ ^ 1;
-    Chunk& n = chunk_[nxt];
-    if (!fill(n)) return false;
-    if (end_ > cur_) attach_tail(n, chunk_[cur_chunk_].data.get() + cur_, end_ - cur_);
-    cur_chunk_ = nxt;
-    cur_ = n.beg;
-    end_ = n.end;
-    return true;
-}
-
-bool BamReader::ensure(size_t need) {
-    while (end_ - cur_ < need)
-        if (!advance()) return end_ - cur_ >= need;
-    return true;
 }
 
 namespace {
@@ -393,7 +302,7 @@ bool BamReader::fill_and_parse(Chunk& c, const Chunk* prev) {
     return true;
 }
 
-// Record mode: the batch after the current one is inflated AND decoded on a helper thread while the caller consumes the
+// The batch after the current one is inflated AND decoded on a helper thread while the caller consumes the
 // current one; here the caller takes it over and starts the one after it (whose front gap receives this one's tail).
 bool BamReader::advance_records() {
     if (!next_ready_.valid()) return false;

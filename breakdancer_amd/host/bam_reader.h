@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "bgzf.h"
+
 namespace bdhost {
 
 struct BamRecord {
@@ -41,6 +43,9 @@ public:
     const std::vector<std::string>& target_names() const { return targets_; }
     const std::string& header_text() const { return header_text_; }  // the SAM header (@HD/@SQ/@RG ... lines)
     int tid_of(const std::string& name) const;  // -1 if absent
+    // where the records start: file offset of the BGZF member that holds the first one, its offset in that member's inflated bytes
+    size_t first_member_offset() const { return first_member_offset_; }
+    uint64_t first_record_offset() const { return first_record_offset_; }
     // next record of the file (no filtering); false at end of file
     bool next(BamRecord& r);
     // decode the record whose block_size word is at p (thread-safe: touches nothing but its arguments)
@@ -61,22 +66,18 @@ private:
     bool fill(Chunk& c);               // inflate the next batch of BGZF blocks into c; false at EOF (runs on the helper thread)
     void attach_tail(Chunk& c, const uint8_t* src, size_t n);  // put n bytes in front of c's bytes
     void parse_chunk(Chunk& c);        // decode every complete record of c (several threads)
-    bool fill_and_parse(Chunk& c, const Chunk* prev);  // the helper thread's job in record mode
-    bool advance();                    // header mode: make the next batch current; false at EOF
-    bool advance_records();            // record mode: take over the batch the helper thread prepared, start the next one
-    bool ensure(size_t need);          // header mode: make `need` decompressed bytes available at cur_
-    const uint8_t* at() const { return chunk_[cur_chunk_].data.get() + cur_; }
+    bool fill_and_parse(Chunk& c, const Chunk* prev);  // the helper thread's job
+    bool advance_records();            // take over the batch the helper thread prepared, start the next one
     std::string path_;
-    const uint8_t* map_ = nullptr;     // the compressed file, memory-mapped
-    size_t map_size_ = 0;
+    MappedFile file_;                  // the compressed file
     int threads_;
     size_t fill_blocks_ = 0;
+    size_t first_member_offset_ = 0;
+    uint64_t first_record_offset_ = 0;
     size_t comp_off_ = 0;              // first compressed byte not yet consumed
     Chunk chunk_[2];                   // one being parsed, one being inflated
-    int cur_chunk_ = 1;                // (the first batch lands in chunk 0)
-    size_t cur_ = 0, end_ = 0;         // parse position / end of the valid bytes in the current chunk
+    int cur_chunk_ = 0;
     std::future<bool> next_ready_;     // the helper thread's fill_and_parse() of the other chunk
-    bool records_mode_ = false;        // false while the header is read byte-wise
     size_t part_ = 0, rec_ = 0;        // next record to hand out: chunk_[cur_chunk_].parts[part_][rec_]
     std::vector<std::string> targets_;
     std::string header_text_;

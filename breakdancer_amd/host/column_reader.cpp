@@ -1,11 +1,5 @@
 #include "column_reader.h"
 
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-#include <zlib.h>
-
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -23,58 +17,11 @@ namespace {
 constexpr size_t kPieceBlocksDefault = 128;  // BGZF blocks per piece: <= 8 MiB inflated, ~40 k records
 constexpr size_t kIndexAhead = 64;           // blocks indexed beyond a piece before it is queued (a record that straddles)
 
-size_t env_or(const char* name, size_t dflt) {
-    const char* v = getenv(name);
-    const long long x = v ? atoll(v) : 0;
-    return x > 0 ? (size_t)x : dflt;
-}
 // test knob: BDX_BAM_PIECE_BLOCKS=1 makes every BGZF block its own piece (every piece boundary a guessed record start)
 const size_t kPieceBlocks = env_or("BDX_BAM_PIECE_BLOCKS", kPieceBlocksDefault);
 const bool kProfile = getenv("BDX_BAM_PROFILE") != nullptr;
 std::atomic<long long> g_inflate_ns{0}, g_parse_ns{0}, g_wait_ns{0}, g_redo{0}, g_scan_ns{0}, g_idle_ns{0};
 inline long long now_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-inline uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-inline uint16_t le16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-
-void inflate_raw(const uint8_t* src, size_t clen, uint8_t* dst, size_t ulen, const std::string& path) {
-    z_stream zs;
-    memset(&zs, 0, sizeof(zs));
-    if (inflateInit2(&zs, -15) != Z_OK) throw std::runtime_error("zlib inflateInit2 failed");
-    zs.next_in = const_cast<Bytef*>(src);
-    zs.avail_in = (uInt)clen;
-    zs.next_out = dst;
-    zs.avail_out = (uInt)ulen;
-    const int rc = inflate(&zs, Z_FINISH);
-    inflateEnd(&zs);
-    if (rc != Z_STREAM_END || zs.avail_out != 0) throw std::runtime_error("corrupt BGZF block in " + path);
-}
-
-// header of the BGZF member at `off`: payload offset / length and inflated size; false at the end of the file
-bool bgzf_member(const uint8_t* map, size_t size, size_t off, const std::string& path, size_t* coff, size_t* clen, uint32_t* ulen,
-                 size_t* total) {
-    const size_t avail = size - off;
-    if (avail == 0) return false;
-    if (avail < 18) throw std::runtime_error("truncated BGZF file: " + path);
-    const uint8_t* h = map + off;
-    if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) throw std::runtime_error("not a BGZF file: " + path);
-    const uint16_t xlen = le16(h + 10);
-    if (avail < (size_t)12 + xlen) throw std::runtime_error("truncated BGZF file: " + path);
-    int bsize = -1;
-    for (size_t x = 12; x + 4 <= (size_t)12 + xlen;) {
-        const uint16_t slen = le16(h + x + 2);
-        if (h[x] == 'B' && h[x + 1] == 'C' && slen == 2) bsize = le16(h + x + 4);
-        x += 4 + (size_t)slen;
-    }
-    if (bsize < 0) throw std::runtime_error("BGZF block without BC field: " + path);
-    *total = (size_t)bsize + 1;
-    if (avail < *total || *total < (size_t)12 + xlen + 8) throw std::runtime_error("truncated BGZF file: " + path);
-    *ulen = le32(h + *total - 4);
-    if (*ulen > 65536) throw std::runtime_error("BGZF block larger than 64 KiB: " + path);
-    *coff = off + 12 + xlen;
-    *clen = *total - 12 - xlen - 8;
-    return true;
-}
 
 }  // namespace
 
@@ -88,20 +35,13 @@ uint8_t LibraryResolver::of(const char* rg, uint32_t len) const {
 }
 
 ColumnReader::ColumnReader(const std::string& path, int threads, const LibraryResolver* libs)
-    : path_(path), threads_(threads < 1 ? 1 : threads), libs_(libs) {
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) throw std::runtime_error("Failed to open samfile " + path);
-    struct stat st;
-    if (fstat(fd, &st) != 0) { close(fd); throw std::runtime_error("Failed to open samfile " + path); }
-    map_size_ = (size_t)st.st_size;
-    if (map_size_) {
-        void* m = mmap(nullptr, map_size_, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (m == MAP_FAILED) { close(fd); throw std::runtime_error("Failed to map samfile " + path); }
-        map_ = (const uint8_t*)m;
-        if (!getenv("BDX_BAM_NO_MADV")) madvise(m, map_size_, MADV_SEQUENTIAL);
-    }
-    close(fd);
-    read_header();
+    : path_(path), file_(path, !getenv("BDX_BAM_NO_MADV")), threads_(threads < 1 ? 1 : threads), libs_(libs) {
+    // the header is read on the calling thread; what is remembered is where the first record lies
+    BamHeader h = read_bam_header(file_.data(), file_.size(), path_);
+    targets_ = std::move(h.target_names);
+    target_len_ = std::move(h.target_lengths);
+    first_block_coff_ = h.first_member_offset;
+    first_rec_abs_ = h.first_record_offset;
 }
 
 ColumnReader::~ColumnReader() {
@@ -115,7 +55,6 @@ ColumnReader::~ColumnReader() {
     if (scanner_.joinable()) scanner_.join();
     for (auto& t : threads_v_)
         if (t.joinable()) t.join();
-    if (map_) munmap((void*)map_, map_size_);
     if (kProfile)
         fprintf(stderr, "[bam] %s: inflate %.3f s, parse+columns %.3f s (summed over %d workers), workers idle %.3f s, block index %.3f s, consumer waited %.3f s, "
                         "pieces decoded again %lld\n", path_.c_str(), g_inflate_ns / 1e9, g_parse_ns / 1e9, threads_, g_idle_ns / 1e9, g_scan_ns / 1e9,
@@ -126,54 +65,6 @@ int ColumnReader::tid_of(const std::string& name) const {
     for (size_t i = 0; i < targets_.size(); ++i)
         if (targets_[i] == name) return (int)i;
     return -1;
-}
-
-// The header (magic, SAM text, reference names) is read block by block on the calling thread; what is remembered is the
-// BGZF block that holds the first record and the record's offset inside it.
-void ColumnReader::read_header() {
-    std::vector<uint8_t> h;
-    std::vector<std::pair<size_t, size_t>> starts;  // (compressed offset, inflated offset) of every block read so far
-    size_t off = 0;
-    auto more = [&]() -> bool {
-        size_t coff, clen, total;
-        uint32_t ulen;
-        if (!bgzf_member(map_, map_size_, off, path_, &coff, &clen, &ulen, &total)) return false;
-        starts.emplace_back(off, h.size());
-        const size_t at = h.size();
-        h.resize(at + ulen);
-        if (ulen) inflate_raw(map_ + coff, clen, h.data() + at, ulen, path_);
-        off += total;
-        return true;
-    };
-    auto need = [&](size_t n) {
-        while (h.size() < n)
-            if (!more()) throw std::runtime_error(path_ + " is not a valid bam file");
-    };
-    need(12);
-    if (memcmp(h.data(), "BAM\1", 4) != 0) throw std::runtime_error(path_ + " is not a valid bam file");
-    const uint32_t l_text = le32(h.data() + 4);
-    size_t p = 8 + (size_t)l_text;
-    need(p + 4);
-    const uint32_t n_ref = le32(h.data() + p);
-    p += 4;
-    for (uint32_t i = 0; i < n_ref; ++i) {
-        need(p + 4);
-        const uint32_t l = le32(h.data() + p);
-        need(p + 4 + (size_t)l + 4);
-        targets_.emplace_back((const char*)h.data() + p + 4, l ? l - 1 : 0);
-        target_len_.push_back(le32(h.data() + p + 4 + (size_t)l));
-        p += 4 + (size_t)l + 4;
-    }
-    // the block that holds byte p of the inflated stream (the next block if the header ends exactly at a block boundary)
-    size_t k = starts.size();
-    while (k > 0 && starts[k - 1].second > p) --k;
-    if (k > 0 && p < h.size()) {
-        first_block_coff_ = starts[k - 1].first;
-        first_rec_abs_ = p - starts[k - 1].second;
-    } else {
-        first_block_coff_ = off;
-        first_rec_abs_ = 0;
-    }
 }
 
 void ColumnReader::locate(const RecordFilter& f, size_t* member_offset, uint64_t* record_offset, bool* seeked) {
@@ -266,7 +157,7 @@ bool ColumnReader::seek_with_index(int tid, int beg) {
         if (!off) off = min_chunk == ~0ull ? 0 : min_chunk;
         if (!off) return false;  // nothing indexed for this sequence: let the full scan find out
         const size_t coff = (size_t)(off >> 16);
-        if (coff >= map_size_) return false;
+        if (coff >= file_.size()) return false;
         first_block_coff_ = coff;
         first_rec_abs_ = off & 0xFFFF;
         return true;
@@ -323,8 +214,8 @@ bool ColumnReader::index_span(int tid, size_t* begin, size_t* end, bool* empty) 
         if ((int)r != tid) continue;
         if (lo == ~0ull) { if (empty) *empty = true; return false; }
         *begin = (size_t)(lo >> 16);
-        *end = std::min<size_t>(map_size_, (size_t)(hi >> 16) + 65536 + 28);
-        return *begin < map_size_;
+        *end = std::min<size_t>(file_.size(), (size_t)(hi >> 16) + 65536 + 28);
+        return *begin < file_.size();
     }
     return false;
 }
@@ -336,16 +227,16 @@ bool ColumnReader::wait_for_block(size_t i) {
     const long long t0 = kProfile ? now_ns() : 0;
     struct Acc { long long t0; ~Acc() { if (kProfile) g_scan_ns += now_ns() - t0; } } acc{t0};
     while (blocks_.size() <= i && !scan_done_) {
-        size_t coff, clen, total;
-        uint32_t ulen;
-        if (!bgzf_member(map_, map_size_, next_scan_, path_, &coff, &clen, &ulen, &total)) {
+        BgzfMember m;
+        if (!bgzf_member_at(file_.data(), file_.size(), next_scan_, path_, &m)) {
             scan_done_ = true;
             break;
         }
-        next_scan_ += total;
-        if (ulen == 0) continue;  // members that inflate to nothing (the EOF marker, flush blocks)
-        blocks_.push_back(Block{coff, clen, ulen, total_ulen_});
-        total_ulen_ += ulen;
+        const size_t coff = next_scan_ + m.payload_off;
+        next_scan_ += m.total;
+        if (m.ulen == 0) continue;  // members that inflate to nothing (the EOF marker, flush blocks)
+        blocks_.push_back(Block{coff, m.payload_len, m.ulen, total_ulen_});
+        total_ulen_ += m.ulen;
     }
     return blocks_.size() > i;
 }
@@ -447,13 +338,13 @@ void ColumnReader::inflate_into(Scratch& sc, const Piece& p, size_t block) {
     // own decoder first (fast_inflate.cpp); zlib decides about anything it does not like, and takes the blocks whose payload
     // ends too close to the end of the mapping for the decoder's 8-byte loads
     static const bool zlib_only = getenv("BDX_BAM_ZLIB") != nullptr;
-    if (zlib_only || b.coff + b.clen + 32 > map_size_ ||
-        !fast_inflate(map_ + b.coff, b.clen, sc.buf.data() + at, b.ulen, sc.buf.size() - (at + b.ulen)))
-        inflate_raw(map_ + b.coff, b.clen, sc.buf.data() + at, b.ulen, path_);
+    if (zlib_only || b.coff + b.clen + 32 > file_.size() ||
+        !fast_inflate(file_.data() + b.coff, b.clen, sc.buf.data() + at, b.ulen, sc.buf.size() - (at + b.ulen)))
+        bgzf_inflate_zlib(file_.data() + b.coff, b.clen, sc.buf.data() + at, b.ulen, path_);
     // the member's CRC-32 (the four bytes behind its payload) against what came out: a flipped bit in a stored or literal-heavy block
     // inflates without complaint (htslib checks it too; BDX_BAM_NO_CRC=1 skips the check)
     static const bool no_crc = getenv("BDX_BAM_NO_CRC") != nullptr;
-    if (!no_crc && b.coff + b.clen + 4 <= map_size_ && crc32_fast(sc.buf.data() + at, b.ulen) != le32(map_ + b.coff + b.clen))
+    if (!no_crc && b.coff + b.clen + 4 <= file_.size() && crc32_fast(sc.buf.data() + at, b.ulen) != le32(file_.data() + b.coff + b.clen))
         throw std::runtime_error("BGZF block fails its CRC-32 (corrupt file): " + path_);
     sc.filled = at + b.ulen;
 }

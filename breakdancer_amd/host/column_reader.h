@@ -19,6 +19,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "bgzf.h"
 #include "config.h"
 
 namespace bdhost {
@@ -70,8 +71,8 @@ public:
     // offset of the BGZF member that holds the first record to look at, the record's offset in that member's inflated bytes,
     // and whether the BAM index was used to get there (then the records behind the region may be left unread).
     void locate(const RecordFilter& f, size_t* member_offset, uint64_t* record_offset, bool* seeked);
-    const uint8_t* mapped() const { return map_; }
-    size_t mapped_size() const { return map_size_; }
+    const uint8_t* mapped() const { return file_.data(); }
+    size_t mapped_size() const { return file_.size(); }
     // <path>.bai: the range of the file that holds sequence tid's records -- [begin, end) in compressed bytes, member aligned at its
     // begin, a member's worth of slack at its end.  false: no index, or nothing indexed for the sequence (*empty tells which)
     bool index_span(int tid, size_t* begin, size_t* end, bool* empty) const;
@@ -105,7 +106,6 @@ private:
         std::vector<Block> blocks;
     };
 
-    void read_header();
     bool seek_with_index(int tid, int beg);   // <path>.bai: start at the first block that can hold a record of the region
     void scan_blocks();                       // scanner thread: the block index, then the pieces' queue
     void worker();
@@ -116,8 +116,7 @@ private:
     void release_piece(Piece* p);
 
     std::string path_;
-    const uint8_t* map_ = nullptr;
-    size_t map_size_ = 0;
+    MappedFile file_;
     int threads_;
     const LibraryResolver* libs_;
     RecordFilter filter_;

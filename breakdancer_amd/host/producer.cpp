@@ -339,9 +339,6 @@ size_t produce_stream(const BamConfig& cfg, const std::string& chr, int threads,
 // ---- device-side decode of a one-BAM configuration ----
 namespace {
 
-inline uint32_t dle32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-inline uint32_t dle16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-
 // Pieces of a file read AHEAD of the one being cut into members: a pool of threads that lives as long as the decode, fed with slices of 1 MiB.
 // The slices are copied out of the file's MAPPING (the reader's own, ColumnReader::mapped) when there is one: pread() of the same bytes from the
 // page cache fed the copy engine 39-42 GB/s, memcpy from the mapping 51 -- the engine's own rate -- with half the threads
@@ -422,9 +419,6 @@ private:
 
 namespace {
 
-inline uint32_t le16_at(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-inline uint32_t le32_at(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
 // Decoders that have done their work.  Releasing one (a 3 GiB ring, four batches' buffers, pinned staging, streams) takes the
 // driver tens of milliseconds, and the clustering run does not need the memory back: they are kept until
 // release_device_decoders(), which the CLI calls only when it walks its destructors.
@@ -497,14 +491,12 @@ size_t decode_on_device(const BamConfig& cfg, size_t bam_index, const std::strin
         // and "large" is about the INFLATED bytes: a real 30x BAM compresses 5 x, the random-base test files 1.57 x.  The ratio is read off
         // the first members (BSIZE / ISIZE of their headers); one round per 4 GB of inflated bytes expected, at most four.
         {
-            const uint8_t* m = hdr.mapped();
+            const uint8_t* map = hdr.mapped();
             size_t off = member_off, comp = 0, infl = 0;
-            for (int k = 0; k < 64 && off + 28 <= file_size; ++k) {
-                if (m[off] != 31 || m[off + 1] != 139 || le16_at(m + off + 10) != 6 || m[off + 12] != 'B' || m[off + 13] != 'C') break;   // (the usual BGZF header: else no estimate)
-                const size_t total = (size_t)le16_at(m + off + 16) + 1;
-                if (total < 26 || off + total > file_size) break;
-                comp += total; infl += le32_at(m + off + total - 4);
-                off += total;
+            BgzfMember m;
+            for (int k = 0; k < 64 && off < file_size && bgzf_parse(map + off, file_size - off, &m) == BgzfStatus::kMember; ++k) {
+                comp += m.total; infl += m.ulen;
+                off += m.total;
             }
             if (comp && infl && !p.batch_blocks) {
                 const double expected_inflated = (double)rest * (double)infl / (double)comp;
@@ -606,31 +598,19 @@ size_t decode_on_device(const BamConfig& cfg, size_t bam_index, const std::strin
         bdx_bgzf_block* tab = cur->tab;
         // the members
         size_t q = 0, nb = 0;
-        while (q + 18 <= have) {
-            const uint8_t* h = b + q;
-            if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) throw std::runtime_error("not a BGZF file: " + path);
-            const size_t xlen = dle16(h + 10);
-            if (q + 12 + xlen > have) break;
-            int bsize = -1;
-            for (size_t x = 12; x + 4 <= 12 + xlen;) {
-                const size_t slen = dle16(h + x + 2);
-                if (h[x] == 'B' && h[x + 1] == 'C' && slen == 2) bsize = (int)dle16(h + x + 4);
-                x += 4 + slen;
-            }
-            if (bsize < 0) throw std::runtime_error("BGZF block without BC field: " + path);
-            const size_t total = (size_t)bsize + 1;
-            if (total < 12 + xlen + 8) throw std::runtime_error("truncated BGZF file: " + path);
-            if (q + total > have) break;
-            const uint32_t ulen = dle32(h + total - 4);
-            if (ulen > 65536) throw std::runtime_error("BGZF block larger than 64 KiB: " + path);
-            if (ulen) {   // (members that inflate to nothing -- the EOF marker, flush blocks -- are skipped)
+        for (;;) {
+            BgzfMember m;
+            const BgzfStatus st = bgzf_parse(b + q, have - q, &m);
+            if (st == BgzfStatus::kEnd || st == BgzfStatus::kNeedBytes) break;   // (the rest of a member cut at the piece's end comes with the next piece)
+            if (st != BgzfStatus::kMember) bgzf_throw(st, path);
+            if (m.ulen) {   // (members that inflate to nothing -- the EOF marker, flush blocks -- are skipped)
                 if (nb >= max_blocks) { too_many_members = true; break; }
-                tab[nb].offset = base + q + 12 + xlen;
-                tab[nb].payload_len = (uint32_t)(total - 12 - xlen - 8);
-                tab[nb].inflated_len = ulen;
+                tab[nb].offset = base + q + m.payload_off;
+                tab[nb].payload_len = (uint32_t)m.payload_len;
+                tab[nb].inflated_len = m.ulen;
                 ++nb;
             }
-            q += total;
+            q += m.total;
         }
         if (too_many_members) break;
         if (at_eof && q != have) throw std::runtime_error("truncated BGZF file: " + path);
