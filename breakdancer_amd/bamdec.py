@@ -25,6 +25,7 @@ class bdx_bamdec_params(C.Structure):
 
 
 BLOCK_DTYPE = np.dtype([("offset", "<u8"), ("payload_len", "<u4"), ("inflated_len", "<u4")])
+INTERVAL_DTYPE = np.dtype([("tid", "<i4"), ("beg", "<i4"), ("end", "<i4")])   # bdx_interval: 0-based, half-open
 
 
 def _lib():
@@ -43,8 +44,37 @@ def _lib():
         lib.bdx_bamdec_fetch.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(L.bdx_batch_buf)]
         lib.bdx_bamdec_stats.argtypes = [vp, vp, vp, vp, vp]
         lib.bdx_inflate_blocks.argtypes = [C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+        lib.bdx_bamdec_rearm.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_size_t]
+        lib.bdx_bamdec_set_exclude.argtypes = [vp, vp, C.c_size_t]
+        lib.bdx_bamdec_excluded.argtypes = [vp, vp]
+        lib.bdx_exclude_mask.argtypes = [C.c_int, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp]
         lib._bamdec_bound = True
     return lib
+
+
+def intervals_array(intervals):
+    """rows of (tid, beg, end) -- a sequence of triples, an (n, 3) array or an INTERVAL_DTYPE array -- as the C ABI's bdx_interval[]"""
+    if isinstance(intervals, np.ndarray) and intervals.dtype == INTERVAL_DTYPE:
+        return np.ascontiguousarray(intervals)
+    a = np.asarray(intervals, dtype=np.int64).reshape(-1, 3)
+    out = np.zeros(len(a), dtype=INTERVAL_DTYPE)
+    out["tid"], out["beg"], out["end"] = a[:, 0], a[:, 1], a[:, 2]
+    return out
+
+
+def exclude_mask(tid, pos, mtid, mpos, intervals, device=0):
+    """bdx_exclude_mask: uint8 array, 1 where the --exclude rule drops the record (its own start, or its mate's, in an interval)"""
+    lib = _lib()
+    cols = [np.ascontiguousarray(x, dtype=np.int32) for x in (tid, pos, mtid, mpos)]
+    n = len(cols[0])
+    if any(len(c) != n for c in cols):
+        raise ValueError("columns of different lengths")
+    iv = intervals_array(intervals)
+    out = np.zeros(n, dtype=np.uint8)
+    rc = lib.bdx_exclude_mask(device, *[c.ctypes.data for c in cols], n, iv.ctypes.data if len(iv) else None, len(iv), out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("bdx_exclude_mask: %s" % lib.bdx_strerror(rc).decode())
+    return out
 
 
 def scan_bgzf(data):
@@ -135,10 +165,10 @@ def bam_header(data, members):
 
 class BamDecoder:
     """One BAM file through bdx_bamdec_*.  sink: a breakdancer_amd.api.BreakDancer whose store receives the records, or None
-    (the columns stay in the decoder; fetch() copies them out)."""
+    (the columns stay in the decoder; fetch() copies them out).  exclude: rows of (tid, beg, end), the --exclude mask (bdx_bamdec_set_exclude)."""
 
     def __init__(self, n_targets, sink=None, device=0, bam_index=0, rg_ids=(), rg_lib=(), fallback_lib=0, region=None,
-                 first_record_offset=0, ring_bytes=0, batch_bytes=0, batch_blocks=0):
+                 first_record_offset=0, ring_bytes=0, batch_bytes=0, batch_blocks=0, exclude=None):
         self.lib = _lib()
         p = bdx_bamdec_params()
         p.device = device
@@ -160,6 +190,25 @@ class BamDecoder:
         if rc != 0:
             raise RuntimeError("bdx_bamdec_create: %s" % self.lib.bdx_strerror(rc).decode())
         self.h = h
+        self.n = None
+        if exclude is not None:
+            self.set_exclude(exclude)
+
+    def set_exclude(self, intervals):
+        """the mask, before the first submit (kept when the decoder is armed again); no rows: no mask"""
+        iv = intervals_array(intervals)
+        self._check(self.lib.bdx_bamdec_set_exclude(self.h, iv.ctypes.data if len(iv) else None, len(iv)), "bdx_bamdec_set_exclude")
+
+    def excluded(self):
+        """after finish(): records the mask dropped since the decoder's creation or its last rearm()"""
+        n = C.c_uint64(0)
+        self._check(self.lib.bdx_bamdec_excluded(self.h, C.byref(n)), "bdx_bamdec_excluded")
+        return n.value
+
+    def rearm(self, region=None, first_record_offset=0, expected_bytes=0):
+        """a finished decoder takes another stretch of the same file (bdx_bamdec_rearm)"""
+        only_tid, beg, end = region if region is not None else (-1, 0, 1 << 29)
+        self._check(self.lib.bdx_bamdec_rearm(self.h, only_tid, beg, end, first_record_offset, expected_bytes), "bdx_bamdec_rearm")
         self.n = None
 
     def _check(self, rc, what):
@@ -279,17 +328,20 @@ def merge_decoded(sink, decoders, src_file, src_index):
 
 
 def decode_file(path, rg_ids=(), rg_lib=(), fallback_lib=0, bam_index=0, region=None, piece_blocks=512, ring_bytes=0, sink=None, device=0,
-                batch_blocks=0, ahead=1):
-    """whole file -> (columns or None with a sink, target names, decoder statistics)"""
+                batch_blocks=0, ahead=1, exclude=None):
+    """whole file -> (columns or None with a sink, target names, decoder statistics; with exclude the statistics carry "excluded")"""
     data = np.fromfile(path, dtype=np.uint8)
     members = scan_bgzf(data)
     names, lens, k, off = bam_header(data, members)
     d = BamDecoder(len(names), sink=sink, device=device, bam_index=bam_index, rg_ids=rg_ids, rg_lib=rg_lib, fallback_lib=fallback_lib,
-                   region=region, first_record_offset=off, ring_bytes=ring_bytes, batch_blocks=batch_blocks)
+                   region=region, first_record_offset=off, ring_bytes=ring_bytes, batch_blocks=batch_blocks, exclude=exclude)
     try:
         d.feed(data, members[k:], piece_blocks, ahead=ahead)
         d.finish()
         cols = d.fetch() if sink is None else None
-        return cols, names, d.stats()
+        stats = d.stats()
+        if exclude is not None:
+            stats["excluded"] = d.excluded()
+        return cols, names, stats
     finally:
         d.close()

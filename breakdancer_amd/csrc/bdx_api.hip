@@ -2263,7 +2263,7 @@ int bdx_set_process_option(const char* name, int value) {
 int bdx_warm_up(int device) {
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
     warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k8(nullptr);
-    warm_k9(nullptr);
+    warm_k9(nullptr); warm_kx(nullptr);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? BDX_OK : BDX_EHIP;
 }
 

@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "bdx_exclude.h"
+
 namespace bdx {
 
 // one BGZF member: deflate payload in the compressed piece, destination in the inflated ring
@@ -80,6 +82,7 @@ struct PieceState {        // running state of one file's decode, in device memo
     uint32_t past_region;  // a record behind the -o region was met (sorted file: nothing of it follows)
     uint32_t piece_raw;    // records of the piece being processed
     uint32_t redo;         // blocks whose guessed start was wrong (statistics)
+    unsigned long long n_excluded;   // records that passed the reader filter and the -o test and were dropped by the --exclude mask
 };
 
 // u: the inflated ring; blocks: the piece's BGZF blocks (out_off = ring offsets, ascending and contiguous);
@@ -93,7 +96,7 @@ void launch_kb_chain(const uint8_t* u, const BgzfBlock* blocks, uint32_t nblk, u
 void launch_kb_stitch(const uint8_t* u, const BgzfBlock* blocks, uint32_t nblk, uint64_t avail_end, int is_last, ChainBlock* cb, uint16_t* offs,
                       uint32_t* rec_base, PieceState* st, const uint32_t* inflate_status, uint64_t rebase_from, uint64_t rebase_to, hipStream_t s);
 void launch_kb_extract(const uint8_t* u, const BgzfBlock* blocks, uint32_t nblk, const ChainBlock* cb, const uint16_t* offs,
-                       const uint32_t* rec_base, RgTable rg, RecordFilterDev f, RawColumns raw, PieceState* st, hipStream_t s);
+                       const uint32_t* rec_base, RgTable rg, RecordFilterDev f, ExcludeMask ex, RawColumns raw, PieceState* st, hipStream_t s);
 // kept records of the piece -> dst at st->n_kept, in order; advances st->n_kept / n_raw; progress (pinned host memory, may be
 // null) receives {n_kept, error, past_region, sequence}
 void launch_kb_compact(RawColumns raw, uint32_t raw_cap, DstColumns dst, uint64_t dst_cap, uint8_t bam_index, uint32_t* scan_ws, PieceState* st,
@@ -111,6 +114,11 @@ struct GatherSource {      // a decoder's own columns
 struct GatherSources { GatherSource s[kMaxGatherSources]; int k; };
 // record i of the destination = record src_index[i] of source src_file[i]; err is raised by an index out of range
 void launch_kb_gather(const GatherSources& src, const uint8_t* src_file, const uint32_t* src_index, uint64_t n, DstColumns dst, uint32_t* err, hipStream_t s);
+
+// ---- --exclude over plain columns (kx_exclude.hip): out[i] = 1 where the rule of bdx_exclude.h drops record i; n_dropped (may be null) += their number
+void launch_kx_exclude(const ExcludeMask& m, const int32_t* tid, const int32_t* pos, const int32_t* mtid, const int32_t* mpos, uint64_t n, uint8_t* out,
+                       unsigned long long* n_dropped, hipStream_t s);
+void warm_kx(hipStream_t s);   // one no-op launch (see bdx_warm_up)
 
 // the 64-bit name key of the host producer (host/bam_reader.cpp hash_name), same function on both sides
 __host__ __device__ inline uint64_t name_hash_step(uint64_t h, uint64_t w) {

@@ -118,6 +118,10 @@ struct bdx_bamdec {
     DevBuf d_rg_hash, d_rg_off, d_rg_chars, d_rg_lib;
     RgTable rg{};
     RecordFilterDev filt{};
+    // --exclude (bdx_bamdec_set_exclude): the merged table in HBM, uploaded once; ntids == 0: no mask
+    DevBuf d_ex_first, d_ex_beg, d_ex_end;
+    ExcludeMask exclude{nullptr, nullptr, nullptr, 0};
+    uint64_t excluded = 0;        // records the mask dropped since creation or the last re-arming (read by bdx_bamdec_finish)
     uint8_t bam_index = 0;
     // own destination (no sink)
     DevBuf o_tid, o_pos, o_mtid, o_mpos, o_isize, o_flag, o_qlen, o_mapq, o_lib, o_bam, o_key, o_check;
@@ -354,7 +358,7 @@ int bam_record_stage(bdx_bamdec* d, BamPiece& p, const BamPiece* next, int is_la
     RawColumns raw{d->r_tid.as<int32_t>(), d->r_pos.as<int32_t>(), d->r_mtid.as<int32_t>(), d->r_mpos.as<int32_t>(), d->r_isize.as<int32_t>(),
                    d->r_flag.as<uint16_t>(), d->r_qlen.as<uint16_t>(), d->r_mapq.as<uint8_t>(), d->r_lib.as<uint8_t>(), d->r_keep.as<uint8_t>(),
                    d->r_key.as<uint64_t>(), d->r_check.as<uint64_t>()};
-    launch_kb_extract(u, blocks, nblk, cb, offs, base, d->rg, d->filt, raw, st, s);
+    launch_kb_extract(u, blocks, nblk, cb, offs, base, d->rg, d->filt, d->exclude, raw, st, s);
     uint64_t dst_cap = 0;
     DstColumns dst = bam_dst(d, &dst_cap);
     launch_kb_compact(raw, (uint32_t)std::min<uint64_t>(bound, d->raw_cap), dst, dst_cap, d->bam_index, d->d_scan.as<uint32_t>(), st,
@@ -584,7 +588,7 @@ void bdx_bamdec_destroy(bdx_bamdec* d) {
     for (hipEvent_t e : d->ev_pool) (void)hipEventDestroy(e);
     for (auto& pr : d->kz_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     for (DevBuf* b : {&d->d_ring, &d->d_cb, &d->d_offs, &d->d_base, &d->d_scan, &d->d_state, &d->r_tid, &d->r_pos, &d->r_mtid, &d->r_mpos, &d->r_isize,
-                      &d->r_flag, &d->r_qlen, &d->r_mapq, &d->r_lib, &d->r_keep, &d->r_key, &d->r_check, &d->o_check, &d->d_rg_hash, &d->d_rg_off, &d->d_rg_chars, &d->d_rg_lib,
+                      &d->r_flag, &d->r_qlen, &d->r_mapq, &d->r_lib, &d->r_keep, &d->r_key, &d->r_check, &d->o_check, &d->d_ex_first, &d->d_ex_beg, &d->d_ex_end, &d->d_rg_hash, &d->d_rg_off, &d->d_rg_chars, &d->d_rg_lib,
                       &d->o_tid, &d->o_pos, &d->o_mtid, &d->o_mpos, &d->o_isize, &d->o_flag, &d->o_qlen, &d->o_mapq, &d->o_lib, &d->o_bam, &d->o_key})
         b->release();
     d->h_progress.release();
@@ -821,6 +825,7 @@ int bdx_bamdec_finish(bdx_bamdec* d, uint64_t* n_records) {
         return bfail(d, st.error == 2 ? BDX_ELIMIT : BDX_EINVAL, what[st.error < 6 ? st.error : 1]);
     }
     d->confirmed = st.n_kept;
+    d->excluded = st.n_excluded;
     d->confirmed_seq = d->n_pieces;
     d->bounds.clear();
     d->bound_in_flight = 0;
@@ -882,6 +887,7 @@ int bdx_bamdec_rearm(bdx_bamdec* d, int32_t only_tid, int32_t region_beg, int32_
     d->bytes_at_arm = d->compressed_bytes;
     d->records_at_arm = d->sink ? d->sink->n : 0;
     d->finished = false; d->any_submitted = false;
+    d->excluded = 0;
     d->host_ms[8] = d->host_ms[9] = 0;
     d->t_armed = std::chrono::steady_clock::now();
     d->expected_bytes = expected_bytes;
@@ -921,6 +927,77 @@ int bdx_bamdec_fetch(bdx_bamdec* d, uint64_t first, uint64_t n, const bdx_batch_
     if (out->name_key) BHIP(d, hipMemcpy(out->name_key, d->o_key.as<uint64_t>() + first, n * 8, hipMemcpyDeviceToHost));
     if (out->name_check) BHIP(d, hipMemcpy(out->name_check, d->o_check.as<uint64_t>() + first, n * 8, hipMemcpyDeviceToHost));
     return BDX_OK;
+}
+
+namespace {
+
+// the C ABI's intervals checked and turned into the table of bdx_exclude.h
+int exclude_table(const bdx_interval* iv, size_t n, std::vector<uint32_t>& first, std::vector<int32_t>& beg, std::vector<int32_t>& end) {
+    if (n && !iv) return BDX_EINVAL;
+    for (size_t i = 0; i < n; ++i) {
+        if (iv[i].tid < 0 || iv[i].beg < 0 || iv[i].end < iv[i].beg) return BDX_EINVAL;
+        if (iv[i].tid >= kMaxExcludeTids) return BDX_ELIMIT;
+    }
+    return exclude_build(iv, n, first, beg, end) > kMaxExcludeIntervals ? BDX_ELIMIT : BDX_OK;
+}
+
+}  // namespace
+
+int bdx_bamdec_set_exclude(bdx_bamdec* d, const bdx_interval* iv, size_t n) {
+    if (!d) return BDX_EINVAL;
+    if (d->any_submitted) return bfail(d, BDX_ESTATE, "the mask is set before the decoder's first submit");
+    std::vector<uint32_t> first;
+    std::vector<int32_t> beg, end;
+    const int rc = exclude_table(iv, n, first, beg, end);
+    if (rc != BDX_OK) return bfail(d, rc, rc == BDX_ELIMIT ? "more than 2^24 merged intervals, or sequences, in the mask" : "bad interval");
+    d->exclude = ExcludeMask{nullptr, nullptr, nullptr, 0};
+    if (beg.empty()) return BDX_OK;   // (no mask: the record stage takes its old path)
+    BHIP(d, hipSetDevice(d->device));
+    // (nothing is in flight: the decoder is new, or finished and armed again -- both waited for its streams)
+    BHIP(d, d->d_ex_first.ensure(first.size() * 4)); BHIP(d, d->d_ex_beg.ensure(beg.size() * 4)); BHIP(d, d->d_ex_end.ensure(end.size() * 4));
+    BHIP(d, hipMemcpy(d->d_ex_first.p, first.data(), first.size() * 4, hipMemcpyHostToDevice));
+    BHIP(d, hipMemcpy(d->d_ex_beg.p, beg.data(), beg.size() * 4, hipMemcpyHostToDevice));
+    BHIP(d, hipMemcpy(d->d_ex_end.p, end.data(), end.size() * 4, hipMemcpyHostToDevice));
+    d->exclude = ExcludeMask{d->d_ex_first.as<uint32_t>(), d->d_ex_beg.as<int32_t>(), d->d_ex_end.as<int32_t>(), (int32_t)first.size() - 1};
+    return BDX_OK;
+}
+
+int bdx_bamdec_excluded(const bdx_bamdec* d, uint64_t* n) {
+    if (!d || !n) return BDX_EINVAL;
+    if (!d->finished) return BDX_ESTATE;
+    *n = d->excluded;
+    return BDX_OK;
+}
+
+// Kernel-level entry point for the parity tests: the rule over plain columns (KX), host arrays in and out.
+int bdx_exclude_mask(int device, const int32_t* tid, const int32_t* pos, const int32_t* mtid, const int32_t* mpos, size_t n, const bdx_interval* iv,
+                     size_t niv, uint8_t* mask) {
+    if (n && (!tid || !pos || !mtid || !mpos || !mask)) return BDX_EINVAL;
+    std::vector<uint32_t> first;
+    std::vector<int32_t> beg, end;
+    const int trc = exclude_table(iv, niv, first, beg, end);
+    if (trc != BDX_OK) return trc;
+    if (n > 0xFFFFFFFFull) return BDX_ELIMIT;
+    if (!n) return BDX_OK;
+    if (beg.empty()) { memset(mask, 0, n); return BDX_OK; }
+    if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
+    DevBuf b_first, b_beg, b_end, b_cols, b_out;
+    auto done = [&](int code) { b_first.release(); b_beg.release(); b_end.release(); b_cols.release(); b_out.release(); return code; };
+    if (b_first.ensure(first.size() * 4) != hipSuccess || b_beg.ensure(beg.size() * 4) != hipSuccess || b_end.ensure(end.size() * 4) != hipSuccess ||
+        b_cols.ensure(n * 16) != hipSuccess || b_out.ensure(n) != hipSuccess)
+        return done(BDX_ENOMEM);
+    int32_t* c = b_cols.as<int32_t>();
+    if (hipMemcpy(b_first.p, first.data(), first.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b_beg.p, beg.data(), beg.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b_end.p, end.data(), end.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c, tid, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c + n, pos, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c + 2 * n, mtid, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c + 3 * n, mpos, n * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return done(BDX_EHIP);
+    const ExcludeMask m{b_first.as<uint32_t>(), b_beg.as<int32_t>(), b_end.as<int32_t>(), (int32_t)first.size() - 1};
+    launch_kx_exclude(m, c, c + n, c + 2 * n, c + 3 * n, n, b_out.as<uint8_t>(), nullptr, nullptr);
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return done(BDX_EHIP);
+    if (hipMemcpy(mask, b_out.p, n, hipMemcpyDeviceToHost) != hipSuccess) return done(BDX_EHIP);
+    return done(BDX_OK);
 }
 
 int bdx_bamdec_stats(const bdx_bamdec* d, uint64_t* compressed_bytes, uint64_t* inflated_bytes, uint64_t* pieces, uint64_t* blocks_walked_twice) {

@@ -224,14 +224,15 @@ __device__ __forceinline__ uint8_t resolve_library(const RgTable& rg, const uint
 // one wave per BGZF block, one lane per record
 __global__ __launch_bounds__(64) void kb_extract_kernel(const uint8_t* __restrict__ u, const BgzfBlock* __restrict__ blocks, uint32_t nblk,
                                                         const ChainBlock* __restrict__ cb, const uint16_t* __restrict__ offs,
-                                                        const uint32_t* __restrict__ rec_base, RgTable rg, RecordFilterDev f, RawColumns raw,
-                                                        PieceState* st) {
+                                                        const uint32_t* __restrict__ rec_base, RgTable rg, RecordFilterDev f, ExcludeMask ex,
+                                                        RawColumns raw, PieceState* st) {
     const uint32_t b = blockIdx.x;
     if (b >= nblk) return;
     if (st->error) return;
     const uint32_t count = cb[b].count;
     const uint64_t ubeg = blocks[b].out_off;
     const uint32_t base = rec_base[b];
+    uint32_t n_excluded = 0;   // (this lane's; a block holds at most kRecSlots records: 32 per lane)
     for (uint32_t k = threadIdx.x; k < count; k += 64) {
         const uint8_t* rec = u + ubeg + offs[(size_t)b * kRecSlots + k];
         const uint32_t bs = ld32(rec);
@@ -264,6 +265,9 @@ __global__ __launch_bounds__(64) void kb_extract_kernel(const uint8_t* __restric
                 keep = tid == f.only_tid && (uint32_t)endp > (uint32_t)f.beg && (uint32_t)pos < (uint32_t)f.end;
             }
         }
+        // --exclude: a record that got this far and starts, or whose mate starts, in a masked interval does not exist for anything
+        // downstream (bdx_exclude.h).  Ahead of the aux sweep: a dropped record skips it
+        if (keep && ex.ntids && exclude_record(ex, tid, pos, mtid, mpos)) { keep = false; ++n_excluded; }
         raw.keep[r] = keep ? 1 : 0;
         if (!keep) continue;
         // aux sweep: RG:Z and AM:<int> (bam_aux_get / bam_aux2i; host/bam_reader.cpp parse_record)
@@ -326,6 +330,12 @@ __global__ __launch_bounds__(64) void kb_extract_kernel(const uint8_t* __restric
         hash_name_pair(p + 32, l_read_name ? l_read_name - 1 : 0, nk, nc);
         raw.key[r] = nk;
         raw.check[r] = nc;
+    }
+    if (ex.ntids) {   // (uniform; the wave is whole again behind the loop) the lanes' counts summed bit by bit: ballot + popcount, one atomic per wave
+        uint32_t total = 0;
+#pragma unroll
+        for (int bit = 0; bit < 6; ++bit) total += (uint32_t)__builtin_popcountll(__ballot((n_excluded >> bit) & 1u)) << bit;
+        if (threadIdx.x == 0 && total) atomicAdd(&st->n_excluded, (unsigned long long)total);
     }
 }
 
@@ -452,9 +462,9 @@ void launch_kb_stitch(const uint8_t* u, const BgzfBlock* blocks, uint32_t nblk, 
 }
 
 void launch_kb_extract(const uint8_t* u, const BgzfBlock* blocks, uint32_t nblk, const ChainBlock* cb, const uint16_t* offs,
-                       const uint32_t* rec_base, RgTable rg, RecordFilterDev f, RawColumns raw, PieceState* st, hipStream_t s) {
+                       const uint32_t* rec_base, RgTable rg, RecordFilterDev f, ExcludeMask ex, RawColumns raw, PieceState* st, hipStream_t s) {
     if (!nblk) return;
-    hipLaunchKernelGGL(kb_extract_kernel, dim3(nblk), dim3(64), 0, s, u, blocks, nblk, cb, offs, rec_base, rg, f, raw, st);
+    hipLaunchKernelGGL(kb_extract_kernel, dim3(nblk), dim3(64), 0, s, u, blocks, nblk, cb, offs, rec_base, rg, f, ex, raw, st);
 }
 
 void launch_kb_compact(RawColumns raw, uint32_t raw_cap, DstColumns dst, uint64_t dst_cap, uint8_t bam_index, uint32_t* scan_ws, PieceState* st,

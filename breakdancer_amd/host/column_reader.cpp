@@ -372,6 +372,7 @@ void ColumnReader::decode_piece(Scratch& sc, Piece& p, bool known_start, uint64_
     struct Acc { long long t0; ~Acc() { if (kProfile) g_parse_ns += now_ns() - t0; } } acc{t_pa};
     p.cols.clear();
     p.past_region = false;
+    p.excluded = 0;
     size_t pos;
     if (known_start) {
         pos = (size_t)(start_abs - p.abs_begin);
@@ -452,6 +453,11 @@ void ColumnReader::decode_piece(Scratch& sc, Piece& p, bool known_start, uint64_
             }
             continue;
         }
+        // --exclude: the record's own start or its mate's in a masked interval (csrc/bdx_exclude.h, the device decode's rule)
+        if (filter_.exclude.ntids && bdx::exclude_record(filter_.exclude, r.tid, r.pos, r.mtid, r.mpos)) {
+            ++p.excluded;
+            continue;
+        }
         uint8_t lib = 0;
         if (libs_) {
             const uint32_t lr = r.rg ? r.l_rg : 0;
@@ -518,6 +524,7 @@ const ColumnChunk* ColumnReader::next() {
             }
         }
         expected_abs_ = p->next_abs;
+        excluded_ += p->excluded;
         current_ = p;
         if (p->past_region) {  // the rest of the file is behind the region: stop the decoders
             region_done_ = true;

@@ -21,6 +21,7 @@
 
 #include "bgzf.h"
 #include "config.h"
+#include "../csrc/bdx_exclude.h"
 
 namespace bdhost {
 
@@ -40,6 +41,7 @@ private:
 struct RecordFilter {  // -o <region>: one tid, records overlapping [beg, end) (bam_index.c:571-576 is_overlap); tid < 0: all
     int only_tid = -1;
     int beg = 0, end = 1 << 29;
+    bdx::ExcludeMask exclude{nullptr, nullptr, nullptr, 0};   // --exclude, tested after the region (the table outlives the reader); ntids == 0: none
 };
 
 struct ColumnChunk {
@@ -78,6 +80,8 @@ public:
     bool index_span(int tid, size_t* begin, size_t* end, bool* empty) const;
     // the next piece's columns in file order, or nullptr at the end of the file; valid until the following call
     const ColumnChunk* next();
+    // records the --exclude mask dropped from the pieces handed out so far
+    uint64_t excluded() const { return excluded_; }
 
 private:
     struct Block {
@@ -92,6 +96,7 @@ private:
         uint64_t next_abs = 0;               // where the first record of the following piece starts
         bool found_start = false;
         bool past_region = false;            // met a record behind the -o region (sorted file: nothing of it follows)
+        uint64_t excluded = 0;               // records of the piece the --exclude mask dropped
         ColumnChunk cols;
         std::string error;
         bool done = false;
@@ -143,6 +148,7 @@ private:
     Piece* current_ = nullptr;
     Scratch redo_;                            // the consumer's own buffer for a piece it has to decode again
     uint64_t expected_abs_ = 0;
+    uint64_t excluded_ = 0;
     bool started_ = false;
     bool seeked_ = false;                     // decoding starts in the middle of the file (-o with a BAM index)
     bool region_done_ = false;                // a piece ran past the region: the stream ends there

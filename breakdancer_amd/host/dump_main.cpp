@@ -6,6 +6,7 @@
 #include <stdexcept>
 
 #include "config.h"
+#include "exclude.h"
 #include "options.h"
 #include "producer.h"
 
@@ -15,9 +16,19 @@ int main(int argc, char** argv) {
         std::ifstream in(opts.bam_config_path.c_str());
         if (!in.is_open()) throw std::runtime_error("unable to open config file '" + opts.bam_config_path + "'");
         bdhost::BamConfig cfg(in, opts.o.cut_sd);
+        bdhost::ExcludeTable exclude_table;   // --exclude: the masked stream
+        const bdhost::ExcludeTable* exclude = nullptr;
+        if (!opts.exclude.empty()) {
+            std::vector<std::string> names;
+            std::vector<uint32_t> lengths;
+            bdhost::read_targets(cfg, names, lengths);
+            bdhost::read_exclude_bed(opts.exclude, names, exclude_table);
+            exclude = &exclude_table;
+        }
         bdhost::ReadStream rs;
-        if (getenv("BDX_DUMP_MERGE")) bdhost::produce_merged_by_columns(cfg, opts.chr, 4, rs);   // (the device path's merge, on host-decoded columns)
-        else bdhost::produce(cfg, opts.chr, 4, rs);
+        if (getenv("BDX_DUMP_MERGE")) bdhost::produce_merged_by_columns(cfg, opts.chr, exclude, 4, rs);   // (the device path's merge, on host-decoded columns)
+        else bdhost::produce(cfg, opts.chr, exclude, 4, rs);
+        if (exclude && getenv("BDX_TIMING")) bdhost::print_exclude_timing(*exclude);
         printf("#w0=%d nlibs=%zu nbams=%zu n=%zu\n", cfg.max_read_window_size(), cfg.num_libs(), cfg.num_bams(), rs.size());
         for (size_t i = 0; i < cfg.num_libs(); ++i) {
             const bdhost::LibraryConfig& l = cfg.library_config(i);

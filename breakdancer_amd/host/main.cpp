@@ -31,6 +31,7 @@
 #include "cache.h"
 #include "config.h"
 #include "dumps.h"
+#include "exclude.h"
 #include "options.h"
 #include "producer.h"
 #include "vcf.h"
@@ -339,6 +340,17 @@ int run(int argc, char** argv) {
         // --vcf: the file is opened before anything else is done -- an unwritable path fails here, before the GPU is touched
         std::unique_ptr<VcfWriter> vcf;
         if (!opts.vcf.empty()) vcf.reset(new VcfWriter(opts.vcf));
+        // --exclude: the BED file is read here as well -- a malformed line fails with FILE:LINE before the GPU is touched.  Names are
+        // those of the first BAM's header, the one -o is resolved against
+        ExcludeTable exclude_table;
+        const ExcludeTable* exclude = nullptr;
+        if (!opts.exclude.empty()) {
+            std::vector<std::string> names;
+            std::vector<uint32_t> lengths;
+            read_targets(cfg, names, lengths);
+            read_exclude_bed(opts.exclude, names, exclude_table);
+            exclude = &exclude_table;
+        }
         // Decode threads: the work is CPU-bound on zlib (~375 MB/s of inflated bytes per core), so what counts is the number of
         // cores this process may really use -- the cgroup's CPU quota when there is one (a container with "16 CPUs" on a
         // 256-thread host: 16 threads 0.64 s, 32 0.55 s, 64 0.70 s for 15 M records), else the hardware threads.  Twice that
@@ -407,7 +419,7 @@ int run(int argc, char** argv) {
             bool on_device = false;
             if (!(dm && !strcmp(dm, "host"))) {
                 bool unsupported = true;
-                n_reads = produce_sharded_on_device(cfg, (int)std::min(std::max(usable_cpus(), 2u), 32u), &targets, ranks, devices, rank_of, &unsupported);
+                n_reads = produce_sharded_on_device(cfg, exclude, (int)std::min(std::max(usable_cpus(), 2u), 32u), &targets, ranks, devices, rank_of, &unsupported);
                 on_device = !unsupported;
                 if (unsupported)   // (no index: nothing was appended; a file the device path gave up on half way: what it appended goes again)
                     for (bdx_dist* r : ranks)
@@ -415,7 +427,7 @@ int run(int argc, char** argv) {
             }
             if (!on_device) {
                 RoutingSink sink(ranks, rank_of);
-                n_reads = produce_stream(cfg, opts.chr, (int)io_threads, &targets, sink);
+                n_reads = produce_stream(cfg, opts.chr, exclude, (int)io_threads, &targets, sink);
             }
             if (timing)
                 fprintf(stderr, "[bdx timing] sharded run over %d ranks: %s\n", world,
@@ -455,13 +467,13 @@ int run(int argc, char** argv) {
                     sink.bring_up(false);
                     if (timing) fprintf(stderr, "[bdx timing] GPU context + resident store ready %.3f s after start (waited %.3f s for it)\n", secs(t_start, now()), secs(tb, now()));
                     bool unsupported = false;
-                    n_reads = produce_on_device(cfg, opts.chr, getenv("BDX_READ_THREADS") ? std::max(1, atoi(getenv("BDX_READ_THREADS"))) : (int)std::min(std::max(usable_cpus(), 2u), 16u), &targets, ctx, &unsupported);
+                    n_reads = produce_on_device(cfg, opts.chr, exclude, getenv("BDX_READ_THREADS") ? std::max(1, atoi(getenv("BDX_READ_THREADS"))) : (int)std::min(std::max(usable_cpus(), 2u), 16u), &targets, ctx, &unsupported);
                     if (unsupported) check(ctx, bdx_reset_reads(ctx), "bdx_reset_reads");
                     else { decoded = true; sink.up = true; }
                     device_decoded = decoded;
                 }
                 if (!decoded) {
-                    n_reads = produce_stream(cfg, opts.chr, (int)io_threads, &targets, sink);
+                    n_reads = produce_stream(cfg, opts.chr, exclude, (int)io_threads, &targets, sink);
                     sink.bring_up();  // (an input without records never asked for a batch)
                 }
             } catch (...) {
@@ -571,7 +583,11 @@ int run(int argc, char** argv) {
                 if (svs[i].printed) wanted.insert(wanted.end(), sup_idx.begin() + sup_off[i], sup_idx.begin() + sup_off[i + 1]);
             std::sort(wanted.begin(), wanted.end());
             wanted.erase(std::unique(wanted.begin(), wanted.end()), wanted.end());
-            collect_reads(cfg, opts.chr, (int)io_threads, wanted, sup_reads);
+            // (the replay drops what the run's reader dropped: the indices are positions in the masked stream)
+            const uint64_t replay_dropped = collect_reads(cfg, opts.chr, exclude, (int)io_threads, wanted, sup_reads);
+            if (exclude && replay_dropped != exclude->dropped.load())
+                throw std::runtime_error("--exclude: the dump pass dropped " + std::to_string(replay_dropped) + " records, the run's reader " +
+                                         std::to_string(exclude->dropped.load()));
         }
         // one row of the table (BreakDancer.cpp:395-497) into `os`; returns nothing, the stream's manipulators carry over to the next row
         auto print_row = [&](std::ostream& os, const bdx_sv& s) {
@@ -687,10 +703,11 @@ int run(int argc, char** argv) {
                     const size_t p = b.rfind("/");
                     samples.push_back(p != std::string::npos ? b.substr(p + 1) : b);
                 }
-            vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(vcf_rows));
+            vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(vcf_rows), opts.exclude);
             vcf.reset();
         }
         if (timing) {
+            if (exclude) print_exclude_timing(*exclude);
             float ms[8] = {0};
             bdx_get_timings(ctx, ms, 8);
             fprintf(stderr, "[bdx timing] reads=%zu decode+merge+stream=%.3fs (%s, single pass, records classified "

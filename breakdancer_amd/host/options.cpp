@@ -61,6 +61,7 @@ void print_usage(const bdx_opts& o) {
         else fprintf(stderr, "       -%c %s       %s\n", r.letter, arg, r.help);
     }
     fprintf(stderr, "       --vcf FILE     write the printed calls as VCF with per-sample genotypes (GT:GQ:PL:DR:DV)\n");
+    fprintf(stderr, "       --exclude FILE drop read pairs with a mate starting in a region of this BED file (centromeres, gaps, pile-ups)\n");
     fprintf(stderr, "\n");
 }
 
@@ -69,13 +70,17 @@ void print_usage(const bdx_opts& o) {
 Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
-    // (the reference's letters parse exactly as with getopt; --vcf is the one long option)
-    enum { kVcf = 256 };
-    static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {nullptr, 0, nullptr, 0}};
+    // (the reference's letters parse exactly as with getopt; --vcf and --exclude are the long options)
+    enum { kVcf = 256, kExclude };
+    static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude}, {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
         if (c == kVcf) {
             vcf = optarg;
+            continue;
+        }
+        if (c == kExclude) {
+            exclude = optarg;
             continue;
         }
         const Row* row = nullptr;

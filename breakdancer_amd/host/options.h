@@ -1,5 +1,5 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
-// (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long option --vcf.
+// (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf and --exclude.
 #pragma once
 #include <string>
 #include <vector>
@@ -16,6 +16,7 @@ struct Options {
     std::string prefix_fastq;    // -d
     std::string dump_BED;        // -g
     std::string vcf;             // --vcf: the printed calls as VCF with per-sample genotypes (vcf.h)
+    std::string exclude;         // --exclude: a BED file of regions whose read pairs the readers drop (exclude.h)
     bdx_opts o;                  // numeric options in the C-ABI layout
     std::vector<std::string> orig_argv;
     int device = 0;              // env BDX_DEVICE

@@ -86,6 +86,8 @@ struct Stream {
     int bam_index = 0;
     int only_tid = -1;
     int beg = 0, end = 1 << 29;
+    bdx::ExcludeMask exclude{nullptr, nullptr, nullptr, 0};   // --exclude (csrc/bdx_exclude.h); ntids == 0: none
+    uint64_t excluded = 0;   // records the mask dropped
     BamRecord cur{};
     bool valid = false;
     // reader filter of the reference: primary (not secondary / supplementary) and tid >= 0
@@ -96,6 +98,7 @@ struct Stream {
             if (cur.tid < 0) continue;
             // bam_iter_read keeps the records of the region that overlap it (bam_index.c:571-576 is_overlap)
             if (only_tid >= 0 && (cur.tid != only_tid || !((uint32_t)cur.end_pos > (uint32_t)beg && (uint32_t)cur.pos < (uint32_t)end))) continue;
+            if (exclude.ntids && bdx::exclude_record(exclude, cur.tid, cur.pos, cur.mtid, cur.mpos)) { ++excluded; continue; }
             return valid = true;
         }
         return valid = false;
@@ -114,14 +117,16 @@ struct StreamGreater {  // BamMerger::Stream::operator> (io/BamMerger.cpp:40-61)
 };
 
 
-// opens the BAMs and runs the k-way merge, calling f(stream_index, record, bam_index, library) per merged record
+// opens the BAMs and runs the k-way merge, calling f(stream_index, record, bam_index, library) per merged record; returns the records
+// the --exclude mask dropped
 template <class F>
-void merge_streams(const BamConfig& cfg, const std::string& chr, int threads, std::vector<std::string>* targets, F&& f) {
+uint64_t merge_streams(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, F&& f) {
     std::vector<std::unique_ptr<Stream>> streams;
     for (size_t b = 0; b < cfg.num_bams(); ++b) {
         std::unique_ptr<Stream> s(new Stream);
         s->rd.reset(new BamReader(cfg.bam_files()[b], threads));
         s->bam_index = (int)b;
+        if (ex) s->exclude = ex->mask();
         if (!chr.empty() && !parse_region(*s->rd, chr, s->only_tid, s->beg, s->end))
             throw std::runtime_error("Failed to parse bam region '" + chr + "' in file " + cfg.bam_files()[b] + ". ");
         streams.push_back(std::move(s));
@@ -144,6 +149,11 @@ void merge_streams(const BamConfig& cfg, const std::string& chr, int threads, st
     uint64_t last_key = ~0ull;
     uint8_t last_lib = fallback;
     uint64_t index = 0;
+    auto excluded = [&] {
+        uint64_t n = 0;
+        for (auto& s : streams) n += s->excluded;
+        return n;
+    };
     auto lib_of = [&](const BamRecord& r) {
         if (r.rg_key == last_key) return last_lib;  // runs of one RG
         auto hit = by_key.find(r.rg_key);  // (a key stands for its string: two RG ids with one 64-bit key are not expected)
@@ -160,7 +170,7 @@ void merge_streams(const BamConfig& cfg, const std::string& chr, int threads, st
         do {
             f(index++, s->cur, s->bam_index, lib_of(s->cur));
         } while (s->advance());
-        return;
+        return excluded();
     }
     while (!pq.empty()) {
         Stream* s = pq.top();
@@ -169,6 +179,7 @@ void merge_streams(const BamConfig& cfg, const std::string& chr, int threads, st
         f(index++, r, s->bam_index, lib_of(r));
         if (s->advance()) pq.push(s);
     }
+    return excluded();
 }
 
 }  // namespace
@@ -290,7 +301,7 @@ struct VectorSink : BatchSink {  // batches appended to a ReadStream
 
 }  // namespace
 
-size_t produce_stream(const BamConfig& cfg, const std::string& chr, int threads, std::vector<std::string>* targets, BatchSink& sink,
+size_t produce_stream(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, BatchSink& sink,
                       size_t batch_records) {
     const LibraryResolver libs(cfg);
     const size_t nb = cfg.num_bams();
@@ -302,6 +313,7 @@ size_t produce_stream(const BamConfig& cfg, const std::string& chr, int threads,
         c->rd.reset(new ColumnReader(cfg.bam_files()[b], per, &libs));
         c->bam = (uint8_t)b;
         RecordFilter f;
+        if (ex) f.exclude = ex->mask();
         if (!chr.empty() && !parse_region(*c->rd, chr, f.only_tid, f.beg, f.end))
             throw std::runtime_error("Failed to parse bam region '" + chr + "' in file " + cfg.bam_files()[b] + ". ");
         c->rd->start(f);
@@ -319,6 +331,7 @@ size_t produce_stream(const BamConfig& cfg, const std::string& chr, int threads,
         w.finish();
         if (getenv("BDX_BAM_PROFILE"))
             fprintf(stderr, "[producer] consumer: copying into batches %.3f s (of which acquire %.3f s, submit %.3f s)\n", w.copy_s_, w.acquire_s_, w.submit_s_);
+        if (ex) ex->dropped += c.rd->excluded();
         return w.total();
     }
     // the reference's k-way merge: a priority queue on (tid, pos, strand), same push / pop sequence as BamMerger
@@ -332,6 +345,8 @@ size_t produce_stream(const BamConfig& cfg, const std::string& chr, int threads,
         if (c->advance()) pq.push(c);
     }
     w.finish();
+    if (ex)
+        for (auto& c : cur) ex->dropped += c->rd->excluded();
     return w.total();
 }
 
@@ -436,7 +451,9 @@ void retire(bdx_bamdec* d) {
 // takes of the file (sizes the decoder's buffers and the sink's store instead of "the rest of the file")
 // reuse (sharded runs): in / out -- a finished decoder of the same file and sink is armed again (bdx_bamdec_rearm) instead of a new one
 // being set up; sized_for: the largest span it will be used for (its buffers are sized once)
-size_t decode_on_device(const BamConfig& cfg, size_t bam_index, const std::string& chr, int threads, std::vector<std::string>* targets, bdx_ctx* ctx,
+// ex (may be null): the --exclude table, handed to a new decoder (it keeps it when it is armed again); *excluded += the records it dropped
+size_t decode_on_device(const BamConfig& cfg, size_t bam_index, const std::string& chr, const ExcludeTable* ex, uint64_t* excluded, int threads,
+                        std::vector<std::string>* targets, bdx_ctx* ctx,
                         int device, bool* unsupported, bdx_bamdec** keep, int whole_tid = -1, size_t span_bytes = 0, bdx_bamdec** reuse = nullptr,
                         size_t sized_for = 0) {
     const std::string& path = cfg.bam_files()[bam_index];
@@ -525,6 +542,14 @@ size_t decode_on_device(const BamConfig& cfg, size_t bam_index, const std::strin
     } else {
         rc = bdx_bamdec_create(&dec, ctx, &p);
         if (rc != BDX_OK) throw std::runtime_error(std::string("bdx_bamdec_create: ") + bdx_strerror(rc));
+        if (ex && !ex->intervals.empty()) {
+            rc = bdx_bamdec_set_exclude(dec, ex->intervals.data(), ex->intervals.size());
+            if (rc != BDX_OK) {
+                const std::string msg = std::string("bdx_bamdec_set_exclude: ") + bdx_strerror(rc) + " (" + bdx_bamdec_last_error(dec) + ")";
+                bdx_bamdec_destroy(dec);
+                throw std::runtime_error(msg);
+            }
+        }
         if (reuse) *reuse = dec;
     }
     const double create_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_create).count();
@@ -665,6 +690,11 @@ size_t decode_on_device(const BamConfig& cfg, size_t bam_index, const std::strin
     if ((rc == BDX_ELIMIT || too_many_members) && unsupported) { *unsupported = true; return 0; }
     if (too_many_members) throw std::runtime_error("too many BGZF members in a piece: " + path);
     check(rc, "bdx_bamdec_finish");
+    if (ex && excluded) {
+        uint64_t x = 0;
+        check(bdx_bamdec_excluded(dec, &x), "bdx_bamdec_excluded");
+        *excluded += x;
+    }
     if (keep) { *keep = dec; guard.d = nullptr; }
     return (size_t)n;
 }
@@ -806,7 +836,7 @@ void merge_order(const std::vector<const int32_t*>& tid, const std::vector<const
 namespace {
 // (tid, pos, strand) of the LAST record of sequence tid in a file, by the host reader through the index: the tail of the sequence is
 // decoded (a window of 32 kb in front of the sequence's end, widened while it holds no record).  false: the file has none
-bool last_key_of(const std::string& path, int tid, int32_t* pos, int* strand) {
+bool last_key_of(const std::string& path, int tid, const ExcludeTable* ex, int32_t* pos, int* strand) {
     for (int64_t back = 2 * 16384;; back *= 32) {
         ColumnReader rd(path, 1, nullptr);
         const int64_t len = (size_t)tid < rd.target_lengths().size() ? (int64_t)rd.target_lengths()[tid] : ((int64_t)1 << 29);
@@ -814,6 +844,7 @@ bool last_key_of(const std::string& path, int tid, int32_t* pos, int* strand) {
         f.only_tid = tid;
         f.beg = (int)std::max<int64_t>(0, len - back);
         f.end = 0x7FFFFFFF;
+        if (ex) f.exclude = ex->mask();   // (a record the run does not see did not emit anything)
         rd.start(f);
         bool any = false;
         while (const ColumnChunk* c = rd.next())
@@ -831,7 +862,7 @@ bool last_key_of(const std::string& path, int tid, int32_t* pos, int* strand) {
 // chromosome), the merge order worked out from three columns as for one GPU (merge_order: BamMerger's queue, io/BamMerger.cpp:40-126),
 // one gather in HBM behind what the rank's store holds (bdx_append_decoded).  Nothing is decoded twice and no record crosses the host.
 // unsupported: a file without an index (or one that does not cover the header's sequences), nothing was done.
-size_t produce_sharded_on_device(const BamConfig& cfg, int threads, std::vector<std::string>* targets, const std::vector<bdx_dist*>& ranks,
+size_t produce_sharded_on_device(const BamConfig& cfg, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, const std::vector<bdx_dist*>& ranks,
                                  const std::vector<int>& devices, const std::vector<int>& rank_of, bool* unsupported) {
     *unsupported = true;
     const size_t nb = cfg.num_bams();
@@ -856,6 +887,7 @@ size_t produce_sharded_on_device(const BamConfig& cfg, int threads, std::vector<
     if (targets) *targets = names;
     const int world = (int)ranks.size();
     std::vector<size_t> n_of(world, 0);
+    std::vector<uint64_t> excluded_of(world, 0);   // (added to ex->dropped only when every rank came through: a run that starts over counts afresh)
     std::vector<std::string> errs(world);
     std::vector<int> gave_up(world, 0);
     std::vector<std::thread> th;
@@ -898,7 +930,7 @@ size_t produce_sharded_on_device(const BamConfig& cfg, int threads, std::vector<
                     const auto tc = std::chrono::steady_clock::now();
                     if (nb == 1) {
                         // (the decoder reports the store's record count: the rank's total so far)
-                        n_of[r] = decode_on_device(cfg, 0, "", per, nullptr, c, devices[r], &un, nullptr, (int)t, span[0][t].end - span[0][t].begin, &decs[0], largest[0]);
+                        n_of[r] = decode_on_device(cfg, 0, "", ex, &excluded_of[r], per, nullptr, c, devices[r], &un, nullptr, (int)t, span[0][t].end - span[0][t].begin, &decs[0], largest[0]);
                         if (un) { gave_up[r] = 1; return; }
                     } else {
                         std::vector<size_t> n;
@@ -907,7 +939,7 @@ size_t produce_sharded_on_device(const BamConfig& cfg, int threads, std::vector<
                         std::vector<const uint16_t*> pflag;
                         size_t total = 0;
                         for (size_t b : files) {
-                            const size_t nr = decode_on_device(cfg, b, "", per, nullptr, nullptr, devices[r], &un, nullptr, (int)t, span[b][t].end - span[b][t].begin, &decs[b], largest[b]);
+                            const size_t nr = decode_on_device(cfg, b, "", ex, &excluded_of[r], per, nullptr, nullptr, devices[r], &un, nullptr, (int)t, span[b][t].end - span[b][t].begin, &decs[b], largest[b]);
                             if (un) { gave_up[r] = 1; return; }
                             tid[b].resize(nr); pos[b].resize(nr); flag[b].resize(nr);
                             bdx_batch_buf out{};
@@ -939,7 +971,7 @@ size_t produce_sharded_on_device(const BamConfig& cfg, int threads, std::vector<
                                 int32_t lp[2] = {0, 0};
                                 int ls[2] = {0, 0};
                                 bool have = true;
-                                for (int x = 0; x < 2 && have; ++x) have = last_key_of(cfg.bam_files()[files[x]], prev[x], &lp[x], &ls[x]);
+                                for (int x = 0; x < 2 && have; ++x) have = last_key_of(cfg.bam_files()[files[x]], prev[x], ex, &lp[x], &ls[x]);
                                 if (have && (lp[0] != lp[1] || ls[0] != ls[1])) emitted_last = (lp[0] > lp[1] || (lp[0] == lp[1] && ls[0] > ls[1])) ? 0 : 1;
                                 // (equal last keys as well: what happened in front of THAT tie decides -- left as a fresh queue would have it)
                             }
@@ -966,15 +998,24 @@ size_t produce_sharded_on_device(const BamConfig& cfg, int threads, std::vector<
     *unsupported = false;
     size_t n = 0;
     for (size_t x : n_of) n += x;
+    if (ex)
+        for (uint64_t x : excluded_of) ex->dropped += x;
     return n;
 }
 
-size_t produce_on_device(const BamConfig& cfg, const std::string& chr, int threads, std::vector<std::string>* targets, bdx_ctx* ctx,
+size_t produce_on_device(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, bdx_ctx* ctx,
                          bool* unsupported) {
     if (unsupported) *unsupported = false;
     const size_t nb = cfg.num_bams();
     if (nb == 0) throw std::runtime_error("BamMerger created with no input streams!");
-    if (nb == 1) return decode_on_device(cfg, 0, chr, threads, targets, ctx, 0, unsupported, nullptr);
+    uint64_t excluded = 0;   // (added to ex->dropped only when the device path came through: the host reader that takes over counts afresh)
+    if (nb == 1) {
+        bool un = false;
+        const size_t n1 = decode_on_device(cfg, 0, chr, ex, &excluded, threads, targets, ctx, 0, unsupported ? &un : nullptr, nullptr);
+        if (unsupported) *unsupported = un;
+        if (ex && !un) ex->dropped += excluded;
+        return n1;
+    }
     // several files: each decoded into its decoder's own columns, the merge order worked out from three of them, one gather in HBM
     if (nb > 16) { if (unsupported) *unsupported = true; return 0; }
     const bool timing = getenv("BDX_TIMING") != nullptr;
@@ -992,7 +1033,7 @@ size_t produce_on_device(const BamConfig& cfg, const std::string& chr, int threa
     size_t total = 0;
     for (size_t b = 0; b < nb; ++b) {
         bool un = false;
-        n[b] = decode_on_device(cfg, b, chr, threads, b == 0 ? targets : nullptr, nullptr, device, &un, &decs[b]);
+        n[b] = decode_on_device(cfg, b, chr, ex, &excluded, threads, b == 0 ? targets : nullptr, nullptr, device, &un, &decs[b]);
         if (un) {
             for (auto& f : fetched) if (f.valid()) f.wait();
             if (unsupported) *unsupported = true;
@@ -1025,6 +1066,7 @@ size_t produce_on_device(const BamConfig& cfg, const std::string& chr, int threa
     const double t_merge = since();
     const int rc = bdx_merge_decoded(ctx, decs.data(), (int)nb, src_file.data(), src_index.data(), total);
     if (rc != BDX_OK) throw std::runtime_error(std::string("bdx_merge_decoded: ") + bdx_strerror(rc) + " (" + bdx_last_error(ctx) + ")");
+    if (ex) ex->dropped += excluded;
     if (timing)
         fprintf(stderr, "[bdx timing] %zu files decoded on the GPU in %.3f s, their keys fetched in %.3f s, merge order in %.3f s, gather in %.3f s\n", nb, t_dec,
                 t_keys - t_dec, t_merge - t_keys, since() - t_merge);
@@ -1052,7 +1094,7 @@ int region_tid(const BamConfig& cfg, const std::string& chr) {
     return parse_region(rd, chr, tid, beg, end) ? tid : -1;
 }
 
-void produce_merged_by_columns(const BamConfig& cfg, const std::string& chr, int threads, ReadStream& out) {
+void produce_merged_by_columns(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, ReadStream& out) {
     const LibraryResolver libs(cfg);
     const size_t nb = cfg.num_bams();
     if (nb == 0) throw std::runtime_error("BamMerger created with no input streams!");
@@ -1060,6 +1102,7 @@ void produce_merged_by_columns(const BamConfig& cfg, const std::string& chr, int
     for (size_t b = 0; b < nb; ++b) {
         ColumnReader rd(cfg.bam_files()[b], std::max(1, threads), &libs);
         RecordFilter f;
+        if (ex) f.exclude = ex->mask();
         if (!chr.empty() && !parse_region(rd, chr, f.only_tid, f.beg, f.end))
             throw std::runtime_error("Failed to parse bam region '" + chr + "' in file " + cfg.bam_files()[b] + ". ");
         rd.start(f);
@@ -1069,6 +1112,7 @@ void produce_merged_by_columns(const BamConfig& cfg, const std::string& chr, int
         while (const ColumnChunk* ch = rd.next())
             if (ch->size()) w.append_range(*ch, 0, ch->size(), (uint8_t)b);
         w.finish();
+        if (ex) ex->dropped += rd.excluded();
     }
     std::vector<const int32_t*> tid(nb), pos(nb);
     std::vector<const uint16_t*> flag(nb);
@@ -1091,17 +1135,17 @@ void produce_merged_by_columns(const BamConfig& cfg, const std::string& chr, int
     }
 }
 
-void produce(const BamConfig& cfg, const std::string& chr, int threads, ReadStream& out) {
+void produce(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, ReadStream& out) {
     VectorSink sink(out);
-    produce_stream(cfg, chr, threads, &out.targets, sink);
+    produce_stream(cfg, chr, ex, threads, &out.targets, sink);
 }
 
-void collect_reads(const BamConfig& cfg, const std::string& chr, int threads, const std::vector<uint64_t>& wanted,
-                   std::vector<SupportRead>& out) {
+uint64_t collect_reads(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, const std::vector<uint64_t>& wanted,
+                       std::vector<SupportRead>& out) {
     out.assign(wanted.size(), SupportRead());
     size_t w = 0;
     static const char* nt16 = "=ACMGRSVTWYHKDBN";  // bam_nt16_rev_table
-    merge_streams(cfg, chr, threads, nullptr, [&](uint64_t index, const BamRecord& r, int, uint8_t lib) {
+    return merge_streams(cfg, chr, ex, threads, nullptr, [&](uint64_t index, const BamRecord& r, int, uint8_t lib) {
         if (w >= wanted.size() || wanted[w] != index) return;
         SupportRead& sr = out[w++];
         sr.tid = r.tid; sr.pos = r.pos; sr.l_qseq = r.l_qseq; sr.bdqual = r.bdqual; sr.lib = lib; sr.rev = (r.flag & 0x10) != 0;

@@ -9,6 +9,7 @@
 
 #include "bdx.h"
 #include "config.h"
+#include "exclude.h"
 
 namespace bdhost {
 
@@ -32,9 +33,10 @@ struct SupportRead {
 };
 
 // Second decode pass for the dumps: replays the merge and keeps the records whose stream index is in `wanted`
-// (sorted, unique); out[i] corresponds to wanted[i].
-void collect_reads(const BamConfig& cfg, const std::string& chr, int threads, const std::vector<uint64_t>& wanted,
-                   std::vector<SupportRead>& out);
+// (sorted, unique); out[i] corresponds to wanted[i].  The replay drops what the run's reader dropped (ex, may be null: --exclude) -- the
+// indices are positions in the masked stream -- and returns how many records that were.
+uint64_t collect_reads(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, const std::vector<uint64_t>& wanted,
+                       std::vector<SupportRead>& out);
 
 // Where the producer puts the merged stream: batches of SoA columns.  acquire() returns columns with room for at least
 // `capacity` records, submit(n) hands the first n back.  Two sinks exist: the GPU context's pinned staging ring
@@ -46,21 +48,23 @@ struct BatchSink {
 };
 
 // chr: empty = all sequences, otherwise the -o region in samtools syntax ("name", "name:beg" or "name:beg-end").
+// ex: null = no mask, otherwise the --exclude table (exclude.h): every reader below drops the records the rule of csrc/bdx_exclude.h
+// marks, behind its region test, and adds their number to ex->dropped.
 // Every BAM is decoded once, by `threads` threads in all (column_reader.h); several files are merged in the reference's
 // order (io/BamMerger.cpp:40-126).  Returns the number of records; targets receives the first file's sequence names.
-size_t produce_stream(const BamConfig& cfg, const std::string& chr, int threads, std::vector<std::string>* targets, BatchSink& sink,
+size_t produce_stream(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, BatchSink& sink,
                       size_t batch_records = 1u << 20);
 // The same stream for a configuration of ONE BAM, decoded on the GPU (bdx_bamdec_*, include/bdx.h): this side reads the file into
 // the decoder's pinned staging buffers (several threads), finds the BGZF members and submits them; inflate, record boundaries,
 // fields, RG -> library and the reader filter run in HBM, and the records land in ctx's resident store with the classifier
 // behind them.  Returns the number of records appended.  Throws std::runtime_error; `unsupported` (may be null) is set instead
 // when the file is one the device path leaves to the host reader (a record of more than 4 MiB), with nothing appended.
-size_t produce_on_device(const BamConfig& cfg, const std::string& chr, int threads, std::vector<std::string>* targets, bdx_ctx* ctx,
+size_t produce_on_device(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, bdx_ctx* ctx,
                          bool* unsupported);
 // One whole-genome run over several GPUs from ONE indexed BAM: rank r's thread decodes the chromosomes t with rank_of[t] == r on
 // devices[r], into bdx_dist_chromosome(ranks[r], t).  *unsupported: no index / several files -- nothing was appended, or a file the
 // device path gives up on (the caller then recreates the ranks and takes the host producer).
-size_t produce_sharded_on_device(const BamConfig& cfg, int threads, std::vector<std::string>* targets, const std::vector<bdx_dist*>& ranks,
+size_t produce_sharded_on_device(const BamConfig& cfg, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, const std::vector<bdx_dist*>& ranks,
                                  const std::vector<int>& devices, const std::vector<int>& rank_of, bool* unsupported);
 // the decoders produce_on_device used are kept (releasing them costs more than the run that follows): this releases them
 void release_device_decoders();
@@ -68,7 +72,7 @@ void release_device_decoders();
 void read_targets(const BamConfig& cfg, std::vector<std::string>& names, std::vector<uint32_t>& lengths);
 // the reference sequence an "-o" argument selects in the first BAM's header, as the producer parses it (-1: none)
 int region_tid(const BamConfig& cfg, const std::string& chr);
-void produce(const BamConfig& cfg, const std::string& chr, int threads, ReadStream& out);
+void produce(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, ReadStream& out);
 // BamMerger's order worked out from the files' (tid, pos, flag) columns alone: entry i of the merged stream is record src_index[i] of
 // file src_file[i] (what the device path hands to bdx_merge_decoded).  emitted_last (two files): the file that emitted the stream's last
 // record in FRONT of these -- a tie at the very first position goes to the other one, which has been waiting (1: as a queue filled afresh)
@@ -76,6 +80,6 @@ void merge_order(const std::vector<const int32_t*>& tid, const std::vector<const
                  const std::vector<size_t>& n, std::vector<uint8_t>& src_file, std::vector<uint32_t>& src_index, int threads = 1, int emitted_last = 1);
 // the same merged stream as produce(), by way of merge_order: every file decoded on its own, then permuted (bdx-dump-reads uses it to
 // hold the two merges against each other)
-void produce_merged_by_columns(const BamConfig& cfg, const std::string& chr, int threads, ReadStream& out);
+void produce_merged_by_columns(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, ReadStream& out);
 
 }  // namespace bdhost

@@ -35,12 +35,13 @@ VcfWriter::~VcfWriter() {
 }
 
 void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
-                      const std::vector<std::string>& samples, std::vector<VcfRecord> records) {
+                      const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude) {
     if (!f_) throw std::runtime_error("VCF output file '" + path_ + "' is already closed");
     FILE* f = f_;
     fprintf(f, "##fileformat=VCFv4.2\n##source=breakdancer-max-mi355x\n##command=");
     for (size_t i = 0; i < argv.size(); ++i) fprintf(f, "%s%s", i ? " " : "", argv[i].c_str());
     fprintf(f, "\n");
+    if (!exclude.empty()) fprintf(f, "##exclude=%s\n", exclude.c_str());
     for (size_t t = 0; t < contigs.size(); ++t)
         fprintf(f, "##contig=<ID=%s,length=%u>\n", contigs[t].c_str(), t < lengths.size() ? lengths[t] : 0u);
     fputs("##FILTER=<ID=PASS,Description=\"All filters passed\">\n"

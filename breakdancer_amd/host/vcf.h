@@ -38,9 +38,9 @@ public:
     VcfWriter(const VcfWriter&) = delete;
     VcfWriter& operator=(const VcfWriter&) = delete;
     // header + records, sorted by (chr1, pos1) with ties in row order; `contigs` are the reference sequences (names are also the
-    // records' CHROM / CHR2 values); the file is closed afterwards
+    // records' CHROM / CHR2 values); exclude: the --exclude file of the run ("": none) for the ##exclude= line; the file is closed afterwards
     void write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
-               const std::vector<std::string>& samples, std::vector<VcfRecord> records);
+               const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude = "");
 
 private:
     std::string path_;

@@ -499,6 +499,26 @@ int bdx_bamdec_host_ms(const bdx_bamdec* d, float* out, int n);
 int bdx_inflate_blocks(int device, const void* compressed, size_t bytes, const bdx_bgzf_block* blocks, size_t nblocks, void* out,
                        size_t out_bytes, uint32_t* status, float* kernel_ms);
 
+/* --exclude: a region mask inside the decoder's reader filter.  No counterpart in the reference (its -x drops a REGION after its reads
+ * have been counted).  The mask is a set of half-open, 0-based intervals [beg, end) per reference sequence (BED coordinates).  A record
+ * that passed the reader filter (primary, placed, the -o region) is dropped when tid >= 0 and pos lies in an interval of tid, or
+ * mtid >= 0 and mpos lies in an interval of mtid: only the start coordinates the record itself carries, so both mates of a consistent
+ * pair go together.  A dropped record does not exist for anything downstream; n_records of bdx_bamdec_progress / bdx_bamdec_finish keeps
+ * meaning kept records.  A tid / mtid beyond the mask's sequences, or with no interval, is never dropped.
+ *   bdx_bamdec_set_exclude  before the decoder's first submit; intervals in any order, they may overlap or touch (they are sorted and
+ *                           merged, touching ones too; beg == end is empty and ignored); the table is uploaded once and kept across
+ *                           bdx_bamdec_rearm; n == 0 removes the mask.  BDX_EINVAL: a null array with n > 0, tid < 0, beg < 0 or
+ *                           end < beg; BDX_ESTATE: after the first submit; BDX_ELIMIT: more than 2^24 merged intervals (a 128 MiB
+ *                           table) or a tid of 2^24 and beyond
+ *   bdx_bamdec_excluded     after bdx_bamdec_finish: records the mask dropped since the decoder's creation or its last bdx_bamdec_rearm
+ *   bdx_exclude_mask        kernel-level entry point for parity tests, and for callers of bdx_push / bdx_set_device_reads that filter
+ *                           their own columns: host arrays in, mask[i] = 1 where the rule drops record i; same argument errors */
+typedef struct bdx_interval { int32_t tid, beg, end; } bdx_interval;   /* 0-based, half-open */
+int bdx_bamdec_set_exclude(bdx_bamdec* d, const bdx_interval* iv, size_t n);
+int bdx_bamdec_excluded(const bdx_bamdec* d, uint64_t* n);
+int bdx_exclude_mask(int device, const int32_t* tid, const int32_t* pos, const int32_t* mtid, const int32_t* mpos, size_t n,
+                     const bdx_interval* iv, size_t niv, uint8_t* mask);
+
 /* bam2cfg's insert-size statistics of nlibs libraries on the GPU (perl/bam2cfg.pl:153-197; `bam2cfg --device`): library i's observations
  * are x[offsets[i] .. offsets[i + 1]).  mean_all / sd_all over all of them (n - 1); mean / sd over the n_kept that are not more than five
  * standard deviations above mean_all; sd_minus / sd_plus the one-sided deviations around mean (n_minus observations <= mean, n_plus above,
