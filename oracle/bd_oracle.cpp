@@ -290,7 +290,7 @@ double gamma_q(double a, double x) {
 }
 // cdf(complement(poisson(lambda), k)) = P(X > k) = P(k+1, lambda)   (Boost poisson.hpp)
 double poisson_upper_tail(double lambda, int k) {
-    if (lambda == 0) return 0;
+    if (!(lambda > 0)) return 0;  // a mean of zero or below: no mass above any k (the product's poisson_close says the same)
     if (k == 0) return -expm1(-lambda);
     return gamma_p((double)k + 1, lambda);
 }

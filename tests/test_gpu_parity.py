@@ -285,6 +285,69 @@ def test_degenerate_inputs_do_not_hang():
             bd.close()
 
 
+def _mixed_wave_case(big_last):
+    """two libraries (a read group each) on one chromosome: one cluster of 8,860 anomalous reads (FF, paired by name: 4,400 pairs
+    of lib1 -- a term with k > 4096, which the score kernel's whole wave sums -- and 30 of lib2) and 90 clusters of 3-12 pairs,
+    a third of them of lib1, a third of lib2, a third of both, 5,000 bp apart.  big_last mirrors the layout: the same cluster
+    spans and gaps in the opposite order, so the same covered length, region sizes and counts -- the same lambda for every term"""
+    small = [[(j % 2 if i % 3 == 2 else i % 3) for j in range(3 + (i * 7) % 10)] for i in range(90)]   # library of every pair
+    big = [0] * 4400 + [1] * 30
+    order = [(c, 4) for c in reversed(small)] + [(big, 40)] if big_last else [(big, 40)] + [(c, 4) for c in small]
+    pos, lib, name = [], [], []
+    at = 1000
+    for libs, step in order:
+        for p, l in enumerate(libs):
+            for mate in (0, 1):
+                pos.append(at + (2 * p + mate) * step)
+                lib.append(l)
+                name.append(len(name) // 2 + 1)
+        at = pos[-1] + 5000
+    n = len(pos)
+    pos = np.array(pos, np.int32)
+    st = dict(tid=np.zeros(n, np.int32), pos=pos, mtid=np.zeros(n, np.int32), mpos=pos + 5000, isize=np.full(n, 5100, np.int32),
+              flag=np.full(n, 0x1 | 0x40, np.uint16), qlen=np.full(n, 100, np.int32), bdqual=np.full(n, 60, np.uint8),
+              rg=["rg%d" % (l + 1) for l in lib], name_id=np.array(name, np.uint64))
+    cfg = "".join("readgroup:rg%d\tplatform:illumina\tmap:x.bam\treadlen:100.00\tlib:lib%d\tlower:310.00\tupper:490.00\tmean:400.00\tstd:30.00\n"
+                  % (i, i) for i in (1, 2))
+    return cfg, [st], ["c1"]
+
+
+@pytest.mark.parametrize("fisher", [0, 1])
+def test_long_and_short_terms_in_one_wave_of_the_score_kernel(fisher):
+    """k6_score_kernel holds one candidate per lane and evaluates the candidates' library terms turn by turn: here a wave of 64
+    candidates and a partial one of 27, candidates with one and with two terms side by side (the lanes whose candidate has no
+    second term sit the turn out), and one candidate whose lib1 term has k = 4,400 -- summed by all 64 lanes while the other
+    lanes' terms are short ones summed by their own lane.  With the large cluster first in position order its candidate is
+    lane 0 of the full wave, with the layout mirrored the last lane of the partial one: same terms, so the same bits"""
+    logp_big = []
+    for big_last in (False, True):
+        cfg, streams, targets = _mixed_wave_case(big_last)
+        assert len(streams[0]["pos"]) < 20000 and (np.diff(streams[0]["pos"]) >= 0).all()
+        run = oracle_case(cfg, streams, targets, make_opts(score_threshold=-1, min_read_pair=1, fisher=fisher))
+        assert run.nlibs == 2 and run.W < 5000
+        bd = product_from_oracle(run, support=True)
+        try:
+            svs, (li, lp), _ = bd.svs()
+            n = len(svs)
+            assert n > 64 and n % 64                                          # a full wave and a partial one
+            assert set(svs["lib_count"][:64].tolist()) == {1, 2}              # lanes with one and with two terms in one wave
+            big = int(np.argmax(svs["num_reads"]))
+            assert big == (n - 1 if big_last else 0)
+            first = int(svs["lib_count"][:big].sum())
+            assert svs["lib_count"][big] == 2 and lp[first:first + 2].tolist() == [4400, 30] and lp.max() == 4400 > 4096
+            compare(run, bd)
+            compare_support(run, bd)
+            assert np.isfinite(svs["logp"]).all() and svs["logp"][big] < -1.0  # (a term that underflowed would compare equal trivially)
+            logp_big.append(svs["logp"][big].tobytes())
+            if not big_last:
+                logp_small = svs["logp"][1:].copy()
+            else:  # and every small cluster's candidate, now in the other wave or another lane, keeps its bits as well
+                assert svs["logp"][:n - 1][::-1].tobytes() == logp_small.tobytes()
+        finally:
+            bd.close()
+    assert logp_big[0] == logp_big[1]
+
+
 @pytest.mark.parametrize("seed", range(24))
 def test_read_names_seen_more_than_twice(seed):
     """merged BAMs with clashing read names: triples, quadruples, duplicates across files and across accepted / rejected

@@ -73,6 +73,30 @@ def test_poisson_restatement_against_mpmath():
         assert abs(math.log(q) - want) <= 1e-12 * max(1.0, abs(want)), r
 
 
+def test_poisson_restatement_on_the_edge_vectors():
+    """the same three rules the kernel holds in test_gpu_poisson.py, on the same file: 1e-10 relative on log p where p is a normal
+    double (1e-6, north_star's bound, in the `outer` family: max(k, lambda) above 8192); p below the smallest normal double where
+    the reference's is; p = 0 where the reference's rounds to zero.  With 1e-10 on either side, the 1e-9 runner.compare holds the
+    product's logp to against this function follows from the two"""
+    v = json.load(open(os.path.join(GOLDEN, "poisson_edge_vectors.json")))["poisson"]
+    assert {r["family"] for r in v} == {"switch", "limit", "k0", "floor", "grid", "random", "underflow", "outer"}
+    L = oracle_lib()
+    worst = {}
+    for r in v:
+        p = L.bdo_poisson_upper_tail(float.fromhex(r["lambda_hex"]), r["k"])
+        assert 0.0 <= p <= 1.0, (r, p)
+        if r["band"] == "normal":
+            want = float(r["logp"])
+            err = abs(math.log(p) - want) / max(1.0, abs(want)) if p > 0 else math.inf
+            worst[r["family"]] = max(worst.get(r["family"], 0.0), err)
+            assert err <= (1e-6 if r["family"] == "outer" else 1e-10), (r, p, err)
+        elif r["band"] == "denormal":
+            assert p < 2.0 ** -1022, (r, p)
+        else:
+            assert p == 0.0, (r, p)
+    print("worst relative error on log p per family:", worst)
+
+
 CFG = ("readgroup:rg1\tplatform:illumina\tmap:x.bam\treadlen:90.00\tlib:lib1\tnum:10001\tlower:277.03\tupper:525.50\tmean:467.59\tstd:31.91\tSWnormality:minus infinity\texe:samtools view\n"
        "readgroup:rg2\tplatform:illumina\tmap:x.bam\treadlen:90.00\tlib:lib1\tnum:10001\tlower:277.03\tupper:525.50\tmean:467.59\tstd:31.91\n"
        "readgroup:rg3\tmapqual:10\tplatform:illumina\tmap:y.bam\treadlen:90.00\tlib:lib2\tnum:10001\tlower:311.36\tupper:532.53\tmean:475.76\tstd:28.67\n"
