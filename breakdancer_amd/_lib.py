@@ -58,7 +58,11 @@ EXPORTS = ["bdx_opts_default", "bdx_create", "bdx_destroy", "bdx_strerror", "bdx
            "bdx_dist_world", "bdx_dist_chromosome", "bdx_dist_run", "bdx_dist_result", "bdx_dist_set_collect_support", "bdx_dist_get_phase_ms", "bdx_dist_phase_name", "bdx_dist_prepare", "bdx_dist_reset_reads", "bdx_dist_get_exchange", "bdx_dist_get_collectives", "bdx_dist_set_debug", "bdx_dist_owner", "bdx_dist_plan",
            "bdx_bamdec_create", "bdx_bamdec_destroy", "bdx_bamdec_last_error", "bdx_bamdec_acquire", "bdx_bamdec_submit", "bdx_bamdec_progress",
            "bdx_bamdec_finish", "bdx_bamdec_rearm", "bdx_bamdec_fetch", "bdx_bamdec_stats", "bdx_bamdec_host_ms", "bdx_merge_decoded", "bdx_append_decoded", "bdx_inflate_blocks", "bdx_insert_size_stats",
-           "bdx_count_junction_pairs", "bdx_bamdec_set_exclude", "bdx_bamdec_excluded", "bdx_exclude_mask"]
+           "bdx_count_junction_pairs", "bdx_bamdec_set_exclude", "bdx_bamdec_excluded", "bdx_exclude_mask", "bdx_count_site_pairs"]
+
+# bdx_site: 1-based positions, (tid1, pos1) <= (tid2, pos2); bit f of flag_mask: ReadFlag f supports the site
+SITE_DTYPE = np.dtype([("tid1", "<i4"), ("pos1", "<i4"), ("tid2", "<i4"), ("pos2", "<i4"), ("flag_mask", "<u4")])
+SITE_FLAGS = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 5) | (1 << 8)   # BDX_SITE_FLAGS: the anomalous classes
 
 REGION_REC_DTYPE = np.dtype([("tid", "<i4"), ("start", "<i4"), ("end", "<i4"), ("n_reads", "<u4"), ("rev_reads", "<u4"),
                              ("nonctx_reads", "<u4"), ("normal_read_pairs", "<u4"), ("max_qlen", "<i4"), ("first_read", "<u4")])
@@ -129,5 +133,6 @@ def load():
     L.bdx_set_collect_support.argtypes = [vp, C.c_int]
     L.bdx_get_sv_support.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.bdx_count_junction_pairs.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_int, vp]
+    L.bdx_count_site_pairs.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int, vp]
     _lib = L
     return L

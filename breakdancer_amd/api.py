@@ -284,6 +284,23 @@ class BreakDancer:
                   "bdx_count_junction_pairs")
         return out
 
+    def count_site_pairs(self, sites, window, by_library=False):
+        """Alternate-supporting read pairs of the last run at given SV sites (bdx_count_site_pairs; the rule is in include/bdx.h):
+        `sites` is an array of _lib.SITE_DTYPE, or a sequence of (tid1, pos1, tid2, pos2, flag_mask) with 1-based positions,
+        (tid1, pos1) <= (tid2, pos2) and bit f of flag_mask set when ReadFlag f supports the site.  A passing record whose flag is in the
+        mask counts, once per pair by its lower mate, when it starts within `window` of one end and its mate within `window` of the
+        other.  Returns an (n, nkeys) uint32 array: per library with by_library, else per BAM file."""
+        if isinstance(sites, np.ndarray) and sites.dtype == L.SITE_DTYPE:
+            s = np.ascontiguousarray(sites)
+        else:
+            rows = [tuple(int(v) for v in r) for r in sites]
+            s = np.array(rows, dtype=L.SITE_DTYPE) if rows else np.zeros(0, dtype=L.SITE_DTYPE)
+        nkeys = self.nlibs if by_library else self.nbams
+        out = np.zeros((len(s), nkeys), np.uint32)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.bdx_count_site_pairs(self.h, p(s), len(s), int(window), int(bool(by_library)), p(out)), "bdx_count_site_pairs")
+        return out
+
     def set_stage_timing(self, on=True):
         """HIP events between the stages (compact / regions / join timings); costs a few microseconds per event."""
         self._chk(self.lib.bdx_set_stage_timing(self.h, int(on)), "bdx_set_stage_timing")

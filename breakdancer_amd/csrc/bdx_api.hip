@@ -260,6 +260,8 @@ struct bdx_ctx {
     // ---- bdx_count_junction_pairs ----
     size_t cls_n = (size_t)-1;        // reads the class bytes in b_cls describe (set by a completed pass 1; -1: none)
     DevBuf b_jq, b_jc;                // its queries and counts
+    // ---- bdx_count_site_pairs ----
+    DevBuf b_sq, b_sc;                // its sites and counts
 };
 
 namespace {
@@ -526,7 +528,7 @@ void bdx_destroy(bdx_ctx* c) {
                       &c->b_parts, &c->b_kdens, &c->b_rs, &c->b_slot, &c->b_members, &c->b_own, &c->b_lib_stage,
                       &c->b_cn_stage, &c->b_t_lambda, &c->b_t_k, &c->b_ws6, &c->b_ins, &c->b_member_ids,
                       &c->b_sv_out, &c->b_lib_index_out, &c->b_lib_pairs_out, &c->b_cn_key_out, &c->b_cn_value_out, &c->b_ltail_out, &c->b_sv_key,
-                      &c->b_jq, &c->b_jc};
+                      &c->b_jq, &c->b_jc, &c->b_sq, &c->b_sc};
     for (DevBuf* b : bufs) b->release();
     PinBuf* pins[] = {&c->h_p1, &c->h_cnt, &c->h_counts, &c->h_regs, &c->h_pk, &c->h_groups, &c->h_terms, &c->h_flags, &c->h_hs_rec, &c->h_hs_aux, &c->h_hs_lists, &c->h_printed, &c->h_counts0, &c->h_counts2,
                       &c->h_sv_out, &c->h_lib_index, &c->h_lib_pairs, &c->h_cn_key, &c->h_cn_value, &c->h_ltail_dev};
@@ -2254,6 +2256,43 @@ int bdx_count_junction_pairs(bdx_ctx* c, const int32_t* tid, const int32_t* pos_
     return BDX_OK;
 }
 
+int bdx_count_site_pairs(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, int by_library, uint32_t* counts) {
+    if (!c) return BDX_EINVAL;
+    NOT_WHILE_SIZING(c);
+    if (c->cls_n != c->n && !(c->ran && c->n == 0)) return fail(c, BDX_ESTATE, "no run has classified the reads this context holds");
+    if (n == 0) return BDX_OK;
+    if (!sites || !counts) return fail(c, BDX_EINVAL, "null array");
+    if (window < 0 || window > (1 << 30)) return fail(c, BDX_EINVAL, "window < 0 or window > 2^30");
+    if (n > ((size_t)1 << 31)) return fail(c, BDX_ELIMIT, "more than 2^31 sites in one call");
+    for (size_t i = 0; i < n; ++i) {
+        const bdx_site& s = sites[i];
+        if (s.tid1 < 0 || s.tid2 < 0 || s.pos1 < 1 || s.pos2 < 1)
+            return fail(c, BDX_EINVAL, "site " + std::to_string(i) + ": tid < 0 or pos < 1");
+        if (s.tid1 > s.tid2 || (s.tid1 == s.tid2 && s.pos1 > s.pos2))
+            return fail(c, BDX_EINVAL, "site " + std::to_string(i) + ": not normalised, (tid1, pos1) > (tid2, pos2)");
+        if (s.flag_mask == 0 || (s.flag_mask & ~BDX_SITE_FLAGS))
+            return fail(c, BDX_EINVAL, "site " + std::to_string(i) + ": flag_mask is 0 or has a bit outside the anomalous classes");
+    }
+    const int nkeys = by_library ? c->nlibs : c->nbams;
+    // (a context with one library / one file never copies the respective column: every read is key 0 there)
+    const uint8_t* key = nkeys > 1 ? (by_library ? c->d.lib : c->d.bam) : nullptr;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cbytes = n * (size_t)nkeys * 4;
+    HIPCHK(c, c->b_sq.ensure(n * sizeof(bdx_site)));
+    HIPCHK(c, c->b_sc.ensure(cbytes));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->b_sq.p, sites, n * sizeof(bdx_site), hipMemcpyHostToDevice, s));
+    KsParams p{};
+    p.tid = c->d.tid; p.pos = c->d.pos; p.mtid = c->d.mtid; p.mpos = c->d.mpos; p.flag = c->d.flag; p.key = key;
+    p.cls = c->b_cls.as<uint8_t>(); p.n = c->n;
+    p.sites = c->b_sq.as<KsSite>(); p.nq = (uint32_t)n; p.nkeys = nkeys; p.window = window; p.counts = c->b_sc.as<uint32_t>();
+    launch_ks(p, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(counts, p.counts, cbytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return BDX_OK;
+}
+
 int bdx_set_process_option(const char* name, int value) {
     if (!name) return BDX_EINVAL;
     if (!strcmp(name, "pin_malloc")) { PinBuf::registered_switch().store(value == 0); return BDX_OK; }
@@ -2263,7 +2302,7 @@ int bdx_set_process_option(const char* name, int value) {
 int bdx_warm_up(int device) {
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
     warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k8(nullptr);
-    warm_k9(nullptr); warm_kx(nullptr);
+    warm_k9(nullptr); warm_kx(nullptr); warm_ks(nullptr);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? BDX_OK : BDX_EHIP;
 }
 

@@ -201,8 +201,27 @@ struct K8Params {
     uint32_t* counts;                   // [nq][nkeys]
 };
 
+// KS (ks_sites.hip): alternate-supporting pairs at given SV sites, per site and key (bdx_count_site_pairs)
+struct KsSite {                         // = bdx_site (include/bdx.h)
+    int32_t tid1, pos1, tid2, pos2;     // 1-based positions, (tid1, pos1) <= (tid2, pos2)
+    uint32_t flag_mask;                 // bit f: ReadFlag f supports the site
+};
+struct KsParams {
+    const int32_t *tid, *pos, *mtid, *mpos;   // the resident store, sorted by (tid, pos)
+    const uint16_t* flag;               // SAM flags
+    const uint8_t* key;                 // library or source-file column; read only when nkeys > 1
+    const uint8_t* cls;                 // K1's class bytes
+    uint64_t n;
+    const KsSite* sites;
+    uint32_t nq;
+    int nkeys;                          // 1..255
+    int32_t window;                     // 0..2^30
+    uint32_t* counts;                   // [nq][nkeys]
+};
+
 // launchers (host side, defined in the .hip files)
 void launch_k8(const K8Params& p, hipStream_t s);
+void launch_ks(const KsParams& p, hipStream_t s);
 void launch_k1(const K1Params& p, int grid, size_t lds, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 size_t k1_lds_bytes(int nlibs, int nbams, int nkeys);
 void launch_finalize(const FinalizeParams& p, hipStream_t s, bool second_level = true);

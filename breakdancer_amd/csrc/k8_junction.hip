@@ -8,7 +8,7 @@
 // scanned as one when they overlap; otherwise separately, and then a read of the first window cannot reach b, nor one of the second a.
 //
 // One wavefront per query.  The store is sorted by (tid, pos) (BamMerger's order, which every stage relies on): a window's first record
-// is found by a 64-ary search -- the 64 lanes probe 64 evenly spaced records and one ballot says how many lie in front, ~5 rounds of
+// is found by a 64-ary search (bdx_wave_search.h) -- the 64 lanes probe 64 evenly spaced records and one ballot says how many lie in front, ~5 rounds of
 // one load each for 2^27 records --, then the lanes stride the window 64 records at a time until a record lies behind it.  Counts per
 // key: one ballot + popcount per step with one key; per-wave LDS counters otherwise (at most 255 keys).
 #include <hip/hip_runtime.h>
@@ -16,35 +16,13 @@
 #include "../../include/bdx.h"
 #include "bdx_dev.h"
 #include "bdx_shard.h"
+#include "bdx_wave_search.h"
 
 namespace bdx {
 
 namespace {
 
 constexpr int kK8Waves = 4;
-
-// first index in [0, n) whose (tid, pos) is not below (t, p); the answer is wave-uniform
-__device__ uint64_t k8_lower_bound(const int32_t* __restrict__ tid, const int32_t* __restrict__ pos, uint64_t n, int32_t t, int64_t p) {
-    const int lane = lane_id();
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t len = hi - lo;
-        const bool last = len <= 64;
-        // (len > 64: lane l probes lo + len * (l + 1) / 65, strictly increasing and inside [lo, hi))
-        const uint64_t idx = last ? lo + (uint64_t)lane : lo + len * (uint64_t)(lane + 1) / 65;
-        bool below = false;
-        if (idx < hi) {
-            const int32_t ti = tid[idx];
-            below = ti < t || (ti == t && (int64_t)pos[idx] < p);
-        }
-        const int c = popc64(ballot64(below));
-        if (last) return lo + (uint64_t)c;
-        const uint64_t lo0 = lo;
-        if (c > 0) lo = lo0 + len * (uint64_t)c / 65 + 1;
-        if (c < 64) hi = lo0 + len * (uint64_t)(c + 1) / 65;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ bool k8_covers(int64_t s, int64_t L, int64_t p) { return s + 1 <= p && p + 1 <= s + L; }
 
@@ -70,7 +48,7 @@ __global__ __launch_bounds__(kK8Waves * 64) void k8_junction_kernel(K8Params p) 
         for (int wi = 0; wi < nwin; ++wi) {
             const int64_t wlo = (wi == 0 ? a : b) + 1 - lm, whi = (wi == 0 && !merged ? a : b) - 1;
             const bool test_a = wi == 0, test_b = merged || wi == 1;
-            for (uint64_t base = k8_lower_bound(p.tid, p.pos, p.n, t, wlo);; base += 64) {
+            for (uint64_t base = wave_lower_bound(p.tid, p.pos, p.n, t, wlo);; base += 64) {
                 const uint64_t i = base + (uint64_t)lane;
                 bool in = i < p.n;
                 int64_t s = 0;

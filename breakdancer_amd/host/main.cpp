@@ -34,6 +34,7 @@
 #include "exclude.h"
 #include "options.h"
 #include "producer.h"
+#include "sites.h"
 #include "vcf.h"
 
 using namespace bdhost;
@@ -177,20 +178,90 @@ void report_result(int status) {
 
 int run(int argc, char** argv);
 
+// The contexts a finished run left behind: the single context, or the ranks of a sharded run (each holds its chromosomes' records).
+struct RunContexts {
+    bdx_ctx* ctx;
+    const std::vector<bdx_dist*>& ranks;
+    const std::vector<int>& rank_of;   // (sharded runs) chromosome -> rank
+    int only_tid;                      // >= 0: the -o chromosome, the only one the run read
+    bool held(int t) const { return t >= 0 && (only_tid < 0 || t == only_tid) && (ranks.empty() || (size_t)t < rank_of.size()); }
+};
+
+// Counts over the resident records, one item per query: on the single context all at once, or -- a sharded run -- item i on the rank that
+// holds chromosome item_tid[i], every rank on its own context and on a thread of its own.  count(context, the items' indices, their
+// counts [items][ns]) returns a bdx status.
+template <class F>
+void count_on_ranks(const RunContexts& rc, const std::vector<int32_t>& item_tid, size_t ns, const char* what, std::vector<uint32_t>& counts, F count) {
+    const size_t nq = item_tid.size();
+    counts.assign(nq * ns, 0);
+    if (!nq) return;
+    if (rc.ranks.empty()) {
+        std::vector<size_t> all(nq);
+        for (size_t i = 0; i < nq; ++i) all[i] = i;
+        check(rc.ctx, count(rc.ctx, all, counts.data()), what);
+        return;
+    }
+    const size_t world = rc.ranks.size();
+    std::vector<std::vector<size_t>> mine(world);
+    for (size_t i = 0; i < nq; ++i) mine[(size_t)rc.rank_of[item_tid[i]]].push_back(i);
+    std::vector<std::string> errs(world);
+    std::vector<std::thread> th;
+    for (size_t r = 0; r < world; ++r) {
+        if (mine[r].empty()) continue;
+        th.emplace_back([&, r] {
+            const std::vector<size_t>& m = mine[r];
+            std::vector<uint32_t> c(m.size() * ns);
+            // (one context per rank, the same for every chromosome: asking for the last sequence passes the feeding-order check whatever was fed)
+            bdx_ctx* rctx = bdx_dist_chromosome(rc.ranks[r], (int)rc.rank_of.size() - 1);
+            const int st = rctx ? count(rctx, m, c.data()) : BDX_EINTERNAL;
+            if (st != BDX_OK) {
+                errs[r] = std::string(what) + " on rank " + std::to_string(r) + ": " + bdx_strerror(st) + (rctx ? std::string(" (") + bdx_last_error(rctx) + ")" : "");
+                return;
+            }
+            for (size_t j = 0; j < m.size(); ++j) std::copy(c.begin() + j * ns, c.begin() + (j + 1) * ns, counts.begin() + m[j] * ns);
+        });
+    }
+    for (auto& t : th) t.join();
+    for (auto const& e : errs)
+        if (!e.empty()) throw std::runtime_error(e);
+}
+
+// DR of --vcf and --sites-vcf records: the normal pairs covering the record's junctions, counted on the GPU over the records the run holds
+// (K8).  A same-chromosome record is one query over both junctions (a pair counts once); a CTX record two, added.  DR is unknown with -t
+// (no read carries the normal-pair bit) and for a junction on a chromosome the run did not read (the -o chromosome only).
+void fill_dr(const Options& opts, const RunContexts& rc, size_t ns, std::vector<VcfRecord>& out) {
+    const bool by_lib = opts.o.cn_lib != 0;
+    std::vector<int32_t> q_tid, q_a, q_b;
+    std::vector<size_t> q_row;
+    for (size_t k = 0; k < out.size(); ++k) {
+        VcfRecord& r = out[k];
+        r.dr.assign(ns, -1);
+        if (opts.o.transchr_rearrange || !rc.held(r.chr1) || !rc.held(r.chr2) || r.pos1 < 1 || r.pos2 < 1) continue;
+        r.dr.assign(ns, 0);
+        if (r.chr1 == r.chr2) {
+            q_tid.push_back(r.chr1); q_a.push_back(std::min(r.pos1, r.pos2)); q_b.push_back(std::max(r.pos1, r.pos2)); q_row.push_back(k);
+        } else {
+            q_tid.push_back(r.chr1); q_a.push_back(r.pos1); q_b.push_back(r.pos1); q_row.push_back(k);
+            q_tid.push_back(r.chr2); q_a.push_back(r.pos2); q_b.push_back(r.pos2); q_row.push_back(k);
+        }
+    }
+    std::vector<uint32_t> counts;
+    count_on_ranks(rc, q_tid, ns, "bdx_count_junction_pairs", counts, [&](bdx_ctx* c, const std::vector<size_t>& m, uint32_t* cnt) {
+        std::vector<int32_t> t(m.size()), a(m.size()), b(m.size());
+        for (size_t j = 0; j < m.size(); ++j) { t[j] = q_tid[m[j]]; a[j] = q_a[m[j]]; b[j] = q_b[m[j]]; }
+        return bdx_count_junction_pairs(c, t.data(), a.data(), b.data(), m.size(), by_lib ? 1 : 0, cnt);
+    });
+    for (size_t i = 0; i < q_tid.size(); ++i)
+        for (size_t k = 0; k < ns; ++k) out[q_row[i]].dr[k] += counts[i * ns + k];
+}
+
 // --vcf: one record per printed row (svs[rows[k]] is row k + 1 of the table).  DV: the dominant type's pairs of the sample (library with
-// -a, else BAM file); DR: the normal pairs covering the call's junctions, counted on the GPU over the records the run holds -- on the
-// single context, or per rank of a sharded run on the rank that holds the chromosome.  A same-chromosome call is one query over both
-// junctions (a pair counts once); a CTX call two, added.  DR is unknown with -t (no read carries the normal-pair bit) and for a junction
-// on a chromosome the run did not read (only_tid >= 0: the -o chromosome).
+// -a, else BAM file); DR: fill_dr.
 std::vector<VcfRecord> vcf_records(const Options& opts, const BamConfig& cfg, const std::vector<bdx_sv>& svs, const std::vector<size_t>& rows,
-                                   const std::vector<int32_t>& li, const std::vector<int32_t>& lp, bdx_ctx* ctx, const std::vector<bdx_dist*>& ranks,
-                                   const std::vector<int>& rank_of, int only_tid) {
+                                   const std::vector<int32_t>& li, const std::vector<int32_t>& lp, const RunContexts& rc) {
     const bool by_lib = opts.o.cn_lib != 0;
     const size_t ns = by_lib ? cfg.num_libs() : cfg.num_bams();
     std::vector<VcfRecord> out(rows.size());
-    std::vector<int32_t> q_tid, q_a, q_b;
-    std::vector<size_t> q_row;
-    auto held = [&](int t) { return t >= 0 && (only_tid < 0 || t == only_tid) && (ranks.empty() || (size_t)t < rank_of.size()); };
     for (size_t k = 0; k < rows.size(); ++k) {
         const bdx_sv& s = svs[rows[k]];
         VcfRecord& r = out[k];
@@ -206,50 +277,44 @@ std::vector<VcfRecord> vcf_records(const Options& opts, const BamConfig& cfg, co
             const size_t key = by_lib ? lib : cfg.library_config(lib).bam_file_index;
             if (key < ns) r.dv[key] += lp[s.lib_begin + i];
         }
-        r.dr.assign(ns, -1);
-        const bool same = s.chr[0] == s.chr[1];
-        if (opts.o.transchr_rearrange || !held(s.chr[0]) || !held(s.chr[1]) || s.pos[0] < 1 || s.pos[1] < 1) continue;
-        r.dr.assign(ns, 0);
-        if (same) {
-            q_tid.push_back(s.chr[0]); q_a.push_back(std::min(s.pos[0], s.pos[1])); q_b.push_back(std::max(s.pos[0], s.pos[1])); q_row.push_back(k);
-        } else {
-            for (int e = 0; e < 2; ++e) { q_tid.push_back(s.chr[e]); q_a.push_back(s.pos[e]); q_b.push_back(s.pos[e]); q_row.push_back(k); }
-        }
     }
-    const size_t nq = q_tid.size();
-    if (!nq) return out;
-    std::vector<uint32_t> counts(nq * ns, 0);
-    if (ranks.empty()) {
-        check(ctx, bdx_count_junction_pairs(ctx, q_tid.data(), q_a.data(), q_b.data(), nq, by_lib ? 1 : 0, counts.data()), "bdx_count_junction_pairs");
-    } else {   // every rank counts the queries of its chromosomes on its own context, on a thread of its own
-        const size_t world = ranks.size();
-        std::vector<std::vector<size_t>> mine(world);
-        for (size_t i = 0; i < nq; ++i) mine[(size_t)rank_of[q_tid[i]]].push_back(i);
-        std::vector<std::string> errs(world);
-        std::vector<std::thread> th;
-        for (size_t r = 0; r < world; ++r) {
-            if (mine[r].empty()) continue;
-            th.emplace_back([&, r] {
-                const std::vector<size_t>& m = mine[r];
-                std::vector<int32_t> t(m.size()), a(m.size()), b(m.size());
-                for (size_t j = 0; j < m.size(); ++j) { t[j] = q_tid[m[j]]; a[j] = q_a[m[j]]; b[j] = q_b[m[j]]; }
-                std::vector<uint32_t> c(m.size() * ns);
-                // (one context per rank, the same for every chromosome: asking for the last sequence passes the feeding-order check whatever was fed)
-                bdx_ctx* rc = bdx_dist_chromosome(ranks[r], (int)rank_of.size() - 1);
-                const int st = rc ? bdx_count_junction_pairs(rc, t.data(), a.data(), b.data(), m.size(), by_lib ? 1 : 0, c.data()) : BDX_EINTERNAL;
-                if (st != BDX_OK) {
-                    errs[r] = std::string("bdx_count_junction_pairs on rank ") + std::to_string(r) + ": " + bdx_strerror(st) + (rc ? std::string(" (") + bdx_last_error(rc) + ")" : "");
-                    return;
-                }
-                for (size_t j = 0; j < m.size(); ++j) std::copy(c.begin() + j * ns, c.begin() + (j + 1) * ns, counts.begin() + m[j] * ns);
-            });
-        }
-        for (auto& t : th) t.join();
-        for (auto const& e : errs)
-            if (!e.empty()) throw std::runtime_error(e);
+    fill_dr(opts, rc, ns, out);
+    return out;
+}
+
+// --sites-vcf: one record per kept line of the --sites table, as the file gave it.  DV: the pairs of the site's type with a mate starting
+// within `window` of each end, counted on the GPU over the records the run holds (KS, bdx_count_site_pairs) -- a sharded run's sites on the
+// rank that holds tid1, where a pair's lower mate lives, CTX included; DR: fill_dr.  Both are unknown for a site with an end on a
+// chromosome the run did not read.
+std::vector<VcfRecord> site_records(const Options& opts, const BamConfig& cfg, const SiteTable& table, int32_t window, const RunContexts& rc) {
+    const bool by_lib = opts.o.cn_lib != 0;
+    const size_t ns = by_lib ? cfg.num_libs() : cfg.num_bams();
+    std::vector<VcfRecord> out(table.sites.size());
+    std::vector<bdx_site> q;
+    std::vector<int32_t> q_tid;
+    std::vector<size_t> q_row;
+    for (size_t k = 0; k < table.sites.size(); ++k) {
+        const SiteLine& s = table.sites[k];
+        VcfRecord& r = out[k];
+        r.row = k + 1;
+        r.chr1 = s.chr1; r.pos1 = s.pos1; r.chr2 = s.chr2; r.pos2 = s.pos2;
+        r.type = s.type;
+        r.has_size = s.has_size;
+        r.size = (int)std::max<long long>(-0x7FFFFFFF, std::min<long long>(s.size, 0x7FFFFFFF));
+        r.dv.assign(ns, -1);
+        if (!rc.held(s.chr1) || !rc.held(s.chr2)) continue;
+        r.dv.assign(ns, 0);
+        q.push_back(s.site); q_tid.push_back(s.site.tid1); q_row.push_back(k);
     }
-    for (size_t i = 0; i < nq; ++i)
-        for (size_t k = 0; k < ns; ++k) out[q_row[i]].dr[k] += counts[i * ns + k];
+    std::vector<uint32_t> counts;
+    count_on_ranks(rc, q_tid, ns, "bdx_count_site_pairs", counts, [&](bdx_ctx* c, const std::vector<size_t>& m, uint32_t* cnt) {
+        std::vector<bdx_site> mine(m.size());
+        for (size_t j = 0; j < m.size(); ++j) mine[j] = q[m[j]];
+        return bdx_count_site_pairs(c, mine.data(), m.size(), window, by_lib ? 1 : 0, cnt);
+    });
+    for (size_t i = 0; i < q.size(); ++i)
+        for (size_t k = 0; k < ns; ++k) out[q_row[i]].dv[k] = counts[i * ns + k];
+    fill_dr(opts, rc, ns, out);
     return out;
 }
 
@@ -350,6 +415,28 @@ int run(int argc, char** argv) {
             read_targets(cfg, names, lengths);
             read_exclude_bed(opts.exclude, names, exclude_table);
             exclude = &exclude_table;
+        }
+        // --sites: likewise -- the output is opened and the table parsed here, a malformed line fails with FILE:LINE before the GPU is touched
+        std::unique_ptr<VcfWriter> sites_vcf;
+        SiteTable site_table;
+        int32_t sites_window = opts.sites_window;
+        if (!opts.sites.empty()) {
+            sites_vcf.reset(new VcfWriter(opts.sites_vcf));
+            std::vector<std::string> names;
+            std::vector<uint32_t> lengths;
+            read_targets(cfg, names, lengths);
+            std::vector<std::pair<std::string, uint32_t>> type_masks;
+            for (const char* t : kSiteTypes) type_masks.emplace_back(t, opts.sv_flag_mask(t));
+            read_sites(opts.sites, names, type_masks, site_table);
+            if (sites_window < 0) {   // how far a supporting mate can start from a breakpoint it brackets: the largest library cutoff
+                double ub = -1.0;
+                for (size_t i = 0; i < cfg.num_libs(); ++i) {
+                    const double u = cfg.library_config(i).uppercutoff;
+                    if (std::isfinite(u)) ub = std::max(ub, std::ceil(u));
+                }
+                if (ub < 0) throw std::runtime_error("--sites: no library has a finite uppercutoff, give --sites-window");
+                sites_window = (int32_t)std::min(ub, 1073741824.0);
+            }
         }
         // Decode threads: the work is CPU-bound on zlib (~375 MB/s of inflated bytes per core), so what counts is the number of
         // cores this process may really use -- the cgroup's CPU quota when there is one (a container with "16 CPUs" on a
@@ -547,12 +634,22 @@ int run(int argc, char** argv) {
         for (size_t i = 0; i < svs.size(); ++i)
             if (svs[i].printed) printed_rows.push_back(i);
         // (--vcf: the junction counts run before the trimmer starts, which must not run beside another call on the context)
-        std::vector<VcfRecord> vcf_rows;
-        if (vcf) {
-            const auto tv = now();
+        std::vector<VcfRecord> vcf_rows, site_rows;
+        if (vcf || sites_vcf) {
             const int only_tid = opts.chr.empty() ? -1 : region_tid(cfg, opts.chr);   // (the producer has parsed the same argument)
-            vcf_rows = vcf_records(opts, cfg, svs, printed_rows, li, lp, ctx, ranks, rank_of, only_tid);
-            if (timing) fprintf(stderr, "[bdx timing] --vcf: junction counts of %zu rows %.4f s\n", printed_rows.size(), secs(tv, now()));
+            const RunContexts rc{ctx, ranks, rank_of, only_tid};
+            if (vcf) {
+                const auto tv = now();
+                vcf_rows = vcf_records(opts, cfg, svs, printed_rows, li, lp, rc);
+                if (timing) fprintf(stderr, "[bdx timing] --vcf: junction counts of %zu rows %.4f s\n", printed_rows.size(), secs(tv, now()));
+            }
+            if (sites_vcf) {
+                const auto tv = now();
+                site_rows = site_records(opts, cfg, site_table, sites_window, rc);
+                if (timing)
+                    fprintf(stderr, "[bdx timing] --sites: pair and junction counts of %zu sites (window %d, %zu lines on unknown sequences ignored) %.4f s\n",
+                            site_table.sites.size(), sites_window, site_table.unknown_lines, secs(tv, now()));
+            }
         }
 
         // (a large run's pinned result tables go back while the table is printed: the process's end is that much shorter.  BDX_TRIM=0: kept)
@@ -691,7 +788,7 @@ int run(int argc, char** argv) {
                 }
             }
         }
-        if (vcf) {
+        if (vcf || sites_vcf) {
             std::vector<std::string> contigs;
             std::vector<uint32_t> lengths;
             read_targets(cfg, contigs, lengths);
@@ -703,8 +800,13 @@ int run(int argc, char** argv) {
                     const size_t p = b.rfind("/");
                     samples.push_back(p != std::string::npos ? b.substr(p + 1) : b);
                 }
-            vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(vcf_rows), opts.exclude);
+            if (vcf) vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(vcf_rows), opts.exclude);
             vcf.reset();
+            if (sites_vcf) {
+                const VcfSites info{opts.sites, sites_window};
+                sites_vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(site_rows), opts.exclude, &info);
+            }
+            sites_vcf.reset();
         }
         if (timing) {
             if (exclude) print_exclude_timing(*exclude);

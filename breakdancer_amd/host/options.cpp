@@ -62,6 +62,9 @@ void print_usage(const bdx_opts& o) {
     }
     fprintf(stderr, "       --vcf FILE     write the printed calls as VCF with per-sample genotypes (GT:GQ:PL:DR:DV)\n");
     fprintf(stderr, "       --exclude FILE drop read pairs with a mate starting in a region of this BED file (centromeres, gaps, pile-ups)\n");
+    fprintf(stderr, "       --sites FILE   genotype the SV sites of this table (the tool's own output columns) over the records the run holds\n");
+    fprintf(stderr, "       --sites-vcf FILE   the VCF the --sites genotypes are written to (GT:GQ:PL:DR:DV; required with --sites)\n");
+    fprintf(stderr, "       --sites-window INT how far from a breakpoint a supporting read may start [the largest library uppercutoff]\n");
     fprintf(stderr, "\n");
 }
 
@@ -70,9 +73,11 @@ void print_usage(const bdx_opts& o) {
 Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
-    // (the reference's letters parse exactly as with getopt; --vcf and --exclude are the long options)
-    enum { kVcf = 256, kExclude };
-    static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude}, {nullptr, 0, nullptr, 0}};
+    // (the reference's letters parse exactly as with getopt; the long options are this tool's own)
+    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow };
+    static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude},
+                                         {"sites", required_argument, nullptr, kSites}, {"sites-vcf", required_argument, nullptr, kSitesVcf},
+                                         {"sites-window", required_argument, nullptr, kSitesWindow}, {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
         if (c == kVcf) {
@@ -81,6 +86,24 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
         }
         if (c == kExclude) {
             exclude = optarg;
+            continue;
+        }
+        if (c == kSites) {
+            sites = optarg;
+            continue;
+        }
+        if (c == kSitesVcf) {
+            sites_vcf = optarg;
+            continue;
+        }
+        if (c == kSitesWindow) {
+            char* end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < 0 || v > (1L << 30)) {
+                fprintf(stderr, "--sites-window takes an integer from 0 to 2^30, not '%s'.\n", optarg);
+                exit(1);
+            }
+            sites_window = (int)v;
             continue;
         }
         const Row* row = nullptr;
@@ -99,6 +122,10 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
             if (argc != 3) throw std::runtime_error("When using -R, no other options are allowed");
             return;
         }
+    }
+    if (sites.empty() != sites_vcf.empty() || (sites.empty() && sites_window >= 0)) {
+        fprintf(stderr, "--sites FILE and --sites-vcf FILE go together (and --sites-window with them).\n");
+        exit(1);
     }
     o.chr_restricted = chr.empty() ? 0 : 1;
     if (optind == argc) {
@@ -129,6 +156,14 @@ std::string Options::sv_type(int flag) const {
         case BDX_ARP_CTX: return "CTX";
         default: return "";
     }
+}
+
+// (the inverse of sv_type by construction: the two cannot drift)
+uint32_t Options::sv_flag_mask(const std::string& type) const {
+    uint32_t mask = 0;
+    for (int f = 0; f < BDX_NUM_FLAGS; ++f)
+        if (((BDX_SITE_FLAGS >> f) & 1u) && !type.empty() && sv_type(f) == type) mask |= 1u << f;
+    return mask;
 }
 
 }  // namespace bdhost

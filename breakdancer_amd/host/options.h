@@ -1,5 +1,6 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
-// (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf and --exclude.
+// (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf, --exclude and --sites / --sites-vcf /
+// --sites-window.
 #pragma once
 #include <string>
 #include <vector>
@@ -17,6 +18,9 @@ struct Options {
     std::string dump_BED;        // -g
     std::string vcf;             // --vcf: the printed calls as VCF with per-sample genotypes (vcf.h)
     std::string exclude;         // --exclude: a BED file of regions whose read pairs the readers drop (exclude.h)
+    std::string sites;           // --sites: a table of SV sites to genotype over the records the run holds (sites.h) ...
+    std::string sites_vcf;       // --sites-vcf: ... and the VCF they are written to (one needs the other)
+    int sites_window = -1;       // --sites-window: how far from a breakpoint a supporting read may start (-1: from the libraries' cutoffs)
     bdx_opts o;                  // numeric options in the C-ABI layout
     std::vector<std::string> orig_argv;
     int device = 0;              // env BDX_DEVICE
@@ -24,6 +28,8 @@ struct Options {
     // parses argv; prints usage to stderr and exits 1 like the reference when no config is given
     Options(int argc, char** argv);
     std::string sv_type(int flag) const;  // Options.cpp:105-119
+    // the inverse of sv_type: bit f set when ReadFlag f (an anomalous class) prints as `type`; 0: none does under this run's -l
+    uint32_t sv_flag_mask(const std::string& type) const;
 };
 
 }  // namespace bdhost

@@ -35,13 +35,15 @@ VcfWriter::~VcfWriter() {
 }
 
 void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
-                      const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude) {
+                      const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude,
+                      const VcfSites* sites) {
     if (!f_) throw std::runtime_error("VCF output file '" + path_ + "' is already closed");
     FILE* f = f_;
     fprintf(f, "##fileformat=VCFv4.2\n##source=breakdancer-max-mi355x\n##command=");
     for (size_t i = 0; i < argv.size(); ++i) fprintf(f, "%s%s", i ? " " : "", argv[i].c_str());
     fprintf(f, "\n");
     if (!exclude.empty()) fprintf(f, "##exclude=%s\n", exclude.c_str());
+    if (sites) fprintf(f, "##sites=%s\n##sites_window=%d\n", sites->file.c_str(), sites->window);
     for (size_t t = 0; t < contigs.size(); ++t)
         fprintf(f, "##contig=<ID=%s,length=%u>\n", contigs[t].c_str(), t < lengths.size() ? lengths[t] : 0u);
     fputs("##FILTER=<ID=PASS,Description=\"All filters passed\">\n"
@@ -55,16 +57,21 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
           "##INFO=<ID=CHR2,Number=1,Type=String,Description=\"Chromosome of the second breakpoint (Chr2)\">\n"
           "##INFO=<ID=POS2,Number=1,Type=Integer,Description=\"Position of the second breakpoint (Pos2)\">\n"
           "##INFO=<ID=END,Number=1,Type=Integer,Description=\"End position of the variant (Pos2; same chromosome, Pos2 >= Pos1 only)\">\n"
-          "##INFO=<ID=SVLEN,Number=1,Type=Integer,Description=\"Difference in length between REF and ALT alleles (-Size; DEL and INS only)\">\n"
-          "##INFO=<ID=ORI1,Number=1,Type=String,Description=\"Reads on the + and - strand at the first breakpoint (Orientation1)\">\n"
-          "##INFO=<ID=ORI2,Number=1,Type=String,Description=\"Reads on the + and - strand at the second breakpoint (Orientation2)\">\n"
-          "##INFO=<ID=NREADS,Number=1,Type=Integer,Description=\"Read pairs supporting the call (num_Reads)\">\n"
-          "##INFO=<ID=BDAF,Number=1,Type=Float,Description=\"BreakDancer allele frequency (Allele_frequency)\">\n"
-          "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+          "##INFO=<ID=SVLEN,Number=1,Type=Integer,Description=\"Difference in length between REF and ALT alleles (-Size; DEL and INS only)\">\n",
+          f);
+    if (!sites)
+        fputs("##INFO=<ID=ORI1,Number=1,Type=String,Description=\"Reads on the + and - strand at the first breakpoint (Orientation1)\">\n"
+              "##INFO=<ID=ORI2,Number=1,Type=String,Description=\"Reads on the + and - strand at the second breakpoint (Orientation2)\">\n"
+              "##INFO=<ID=NREADS,Number=1,Type=Integer,Description=\"Read pairs supporting the call (num_Reads)\">\n"
+              "##INFO=<ID=BDAF,Number=1,Type=Float,Description=\"BreakDancer allele frequency (Allele_frequency)\">\n",
+              f);
+    fputs("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
           "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: second-smallest PL, capped at 99\">\n"
           "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods (binomial, alt-read probability 0.01/0.5/0.99)\">\n"
-          "##FORMAT=<ID=DR,Number=1,Type=Integer,Description=\"Normal read pairs whose fragment covers a breakpoint junction\">\n"
-          "##FORMAT=<ID=DV,Number=1,Type=Integer,Description=\"Read pairs supporting the call (the dominant type's pairs)\">\n",
+          "##FORMAT=<ID=DR,Number=1,Type=Integer,Description=\"Normal read pairs whose fragment covers a breakpoint junction\">\n",
+          f);
+    fputs(sites ? "##FORMAT=<ID=DV,Number=1,Type=Integer,Description=\"Read pairs of the site's type with one mate starting within sites_window of each breakpoint\">\n"
+                : "##FORMAT=<ID=DV,Number=1,Type=Integer,Description=\"Read pairs supporting the call (the dominant type's pairs)\">\n",
           f);
     fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT");
     for (auto const& s : samples) fprintf(f, "\t%s", s.c_str());
@@ -74,13 +81,16 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
     auto name = [&](int t) { return t >= 0 && (size_t)t < contigs.size() ? contigs[t] : std::to_string(t); };
     for (auto const& r : records) {
         const std::string type = r.type.empty() ? "." : r.type;
-        fprintf(f, "%s\t%d\tBDX%zu\tN\t%s\t%d\tPASS\tIMPRECISE;SVTYPE=%s;CHR2=%s;POS2=%d", name(r.chr1).c_str(), r.pos1, r.row,
-                r.type.empty() ? "." : ("<" + r.type + ">").c_str(), r.score, type.c_str(), name(r.chr2).c_str(), r.pos2);
+        const std::string qual = sites ? "." : std::to_string(r.score);
+        fprintf(f, "%s\t%d\t%s%zu\tN\t%s\t%s\tPASS\tIMPRECISE;SVTYPE=%s;CHR2=%s;POS2=%d", name(r.chr1).c_str(), r.pos1, sites ? "SITE" : "BDX", r.row,
+                r.type.empty() ? "." : ("<" + r.type + ">").c_str(), qual.c_str(), type.c_str(), name(r.chr2).c_str(), r.pos2);
         if (r.chr2 == r.chr1 && r.pos2 >= r.pos1) fprintf(f, ";END=%d", r.pos2);
-        if (r.type == "DEL" || r.type == "INS") fprintf(f, ";SVLEN=%lld", -(long long)r.size);
-        fprintf(f, ";ORI1=%s;ORI2=%s;NREADS=%d;BDAF=", r.ori1.c_str(), r.ori2.c_str(), r.nreads);
-        if (std::isfinite(r.af)) fprintf(f, "%.6g", (double)r.af);
-        else fputs(".", f);
+        if ((r.type == "DEL" || r.type == "INS") && r.has_size) fprintf(f, ";SVLEN=%lld", -(long long)r.size);
+        if (!sites) {
+            fprintf(f, ";ORI1=%s;ORI2=%s;NREADS=%d;BDAF=", r.ori1.c_str(), r.ori2.c_str(), r.nreads);
+            if (std::isfinite(r.af)) fprintf(f, "%.6g", (double)r.af);
+            else fputs(".", f);
+        }
         fputs("\tGT:GQ:PL:DR:DV", f);
         for (size_t k = 0; k < samples.size(); ++k) {
             const int64_t dr = k < r.dr.size() ? r.dr[k] : -1, dv = k < r.dv.size() ? r.dv[k] : 0;
@@ -90,8 +100,10 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
                 fprintf(f, "\t%s:%d:%lld,%lld,%lld:", kGt[g.gt], g.gq, (long long)g.pl[0], (long long)g.pl[1], (long long)g.pl[2]);
             else
                 fputs("\t./.:.:.:", f);
-            if (dr < 0) fprintf(f, ".:%lld", (long long)dv);
-            else fprintf(f, "%lld:%lld", (long long)dr, (long long)dv);
+            if (dr < 0) fputs(".:", f);
+            else fprintf(f, "%lld:", (long long)dr);
+            if (dv < 0) fputs(".", f);
+            else fprintf(f, "%lld", (long long)dv);
         }
         fputs("\n", f);
     }

@@ -1,6 +1,8 @@
 // --vcf: the printed calls as VCFv4.2 with per-sample genotypes (GT:GQ:PL:DR:DV).  No counterpart in the reference, whose table
 // carries the supporting pairs of a call (DV) but not the normal pairs that cover its breakpoints (DR): those are counted on the GPU
 // over the run's resident records (bdx_count_junction_pairs).
+// --sites-vcf: the same writer for given sites (sites.h) -- there DV is counted on the GPU as well (bdx_count_site_pairs), a record has
+// no score, orientation counts, NREADS or BDAF, and its ID is SITE<k>.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -27,7 +29,14 @@ struct VcfRecord {
     std::string ori1, ori2, type;
     int size = 0, score = 0, nreads = 0;
     float af = 0;
-    std::vector<int64_t> dr, dv;     // per sample; dr < 0: unknown ('.')
+    std::vector<int64_t> dr, dv;     // per sample; < 0: unknown ('.')
+    bool has_size = true;            // (a site: the table it came from had a numeric Size column; no SVLEN without)
+};
+
+// what makes an output a --sites-vcf one: the records are given sites (ID SITE<row>, QUAL '.', INFO without ORI1 / ORI2 / NREADS / BDAF)
+struct VcfSites {
+    std::string file;                // --sites, for the ##sites= line
+    int32_t window = 0;              // the window the pairs were counted with, for ##sites_window=
 };
 
 class VcfWriter {
@@ -38,9 +47,11 @@ public:
     VcfWriter(const VcfWriter&) = delete;
     VcfWriter& operator=(const VcfWriter&) = delete;
     // header + records, sorted by (chr1, pos1) with ties in row order; `contigs` are the reference sequences (names are also the
-    // records' CHROM / CHR2 values); exclude: the --exclude file of the run ("": none) for the ##exclude= line; the file is closed afterwards
+    // records' CHROM / CHR2 values); exclude: the --exclude file of the run ("": none) for the ##exclude= line; sites: non-null for a
+    // --sites-vcf output; the file is closed afterwards
     void write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
-               const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude = "");
+               const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude = "",
+               const VcfSites* sites = nullptr);
 
 private:
     std::string path_;

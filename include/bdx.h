@@ -540,6 +540,32 @@ int bdx_insert_size_stats(int device, const double* x, const uint32_t* offsets, 
 int bdx_count_junction_pairs(bdx_ctx* ctx, const int32_t* tid, const int32_t* pos_a, const int32_t* pos_b, size_t n,
                              int by_library, uint32_t* counts);
 
+/* Alternate-supporting read pairs at GIVEN SV sites: no counterpart in the reference (the DV / GT input of --sites; the run's own calls
+ * get their supporting pairs from the region walk).  The rule, written down here once:
+ *   A site is (tid1, pos1, tid2, pos2, flag_mask): positions 1-based as the table prints them, (tid1, pos1) <= (tid2, pos2)
+ *   lexicographically; bit f of flag_mask is set when ReadFlag f supports the site's type -- only the anomalous classes BDX_ARP_FF,
+ *   BDX_ARP_LARGE_INSERT, BDX_ARP_SMALL_INSERT, BDX_ARP_RF, BDX_ARP_RR, BDX_ARP_CTX (BDX_SITE_FLAGS), at least one.
+ *   A record is NEAR P on T when tid == T and |pos + 1 - P| <= window; its mate when mtid == T and |mpos + 1 - P| <= window (64-bit
+ *   arithmetic).  Record i of the resident store counts for a site when
+ *     1. cls[i] & BDX_CLS_PASS and bit BDX_CLS_FLAG(cls[i]) of flag_mask is set (the flag after the pass-2 remaps -l and RR->FF, as the
+ *        walk sees it);
+ *     2. it is its pair's lower mate, so that each pair counts once: (tid, pos) < (mtid, mpos) lexicographically, or the two are equal
+ *        and SAM flag bit 0x40 (first in pair) is set;
+ *     3. forward: it is near pos1 on tid1 and its mate near pos2 on tid2; or reverse: it is near pos2 on tid2 and its mate near pos1 on
+ *        tid1 (possible only when the windows overlap: tid1 == tid2 and pos2 - pos1 <= 2 window).  A record matching both ways counts once.
+ *   Only what the record itself carries is looked at (as in --exclude's rule): not the mate's own record, its quality, or whether it
+ *   survived a filter.  The count is therefore NOT the walk's num_Reads, which also wants both mates inside accepted regions.
+ * counts[i * nkeys + k]: the records of key k (library with by_library, else BAM file; nkeys = nlibs / nbams; a key index out of range
+ * counts as 0) that count for site i.  After bdx_run, or on a rank's context (bdx_dist_chromosome) after bdx_dist_run: that rank's
+ * chromosomes -- a pair's lower mate lives on tid1.  A chromosome the context holds no reads of, or beyond the header, counts 0.
+ * BDX_ESTATE before a run has classified the reads the context holds (or while a sizing pass is in flight); n == 0 is BDX_OK even with
+ * null pointers; BDX_EINVAL for a null array with n > 0, tid1 < 0 or tid2 < 0, pos1 < 1 or pos2 < 1, a site that is not normalised,
+ * flag_mask 0 or with a bit outside BDX_SITE_FLAGS, window < 0 or window > 2^30; BDX_ELIMIT above 2^31 sites.  Not beside another call
+ * on the same context (bdx_trim_results included). */
+#define BDX_SITE_FLAGS ((1u << BDX_ARP_FF) | (1u << BDX_ARP_LARGE_INSERT) | (1u << BDX_ARP_SMALL_INSERT) | (1u << BDX_ARP_RF) | (1u << BDX_ARP_RR) | (1u << BDX_ARP_CTX))
+typedef struct bdx_site { int32_t tid1, pos1, tid2, pos2; uint32_t flag_mask; } bdx_site;
+int bdx_count_site_pairs(bdx_ctx* ctx, const bdx_site* sites, size_t n, int32_t window, int by_library, uint32_t* counts); /* [n][nkeys] */
+
 /* device the context is bound to and the HIP stream it launches on (as void*), for callers that time it */
 int bdx_device(const bdx_ctx* ctx);
 void* bdx_stream(const bdx_ctx* ctx);
