@@ -164,6 +164,18 @@ class BreakDancer:
         self._chk(self.lib.bdx_use_name_check(self.h, 1 if on else 0), "bdx_use_name_check")
         return self
 
+    def mark_duplicates(self, on=True):
+        """duplicate read pairs get SAM flag 0x400 on the GPU before the classifier reads the flags (bdx_set_mark_duplicates; the rule is in
+        include/bdx.h); while the context holds no reads"""
+        self._chk(self.lib.bdx_set_mark_duplicates(self.h, 1 if on else 0), "bdx_set_mark_duplicates")
+        return self
+
+    def duplicates(self):
+        """(records marked, groups of two or more) of the last run (bdx_get_duplicates)"""
+        m, g = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.lib.bdx_get_duplicates(self.h, C.byref(m), C.byref(g)), "bdx_get_duplicates")
+        return m.value, g.value
+
     def push_reads(self, arrs):
         b, keep = make_batch(arrs)
         self._keep.append(keep)  # the H2D copies are asynchronous: the arrays must outlive them (released by run())
@@ -345,6 +357,22 @@ class BreakDancer:
         self.lib.bdx_get_timings(self.h, ms.ctypes.data_as(C.c_void_p), 12)
         return dict(zip(("classify", "compact", "regions", "join", "readback", "walk", "score", "total", "final_wait", "merge",
                          "combine_scores"), ms.tolist()))
+
+
+def mark_duplicates(tid, pos, mtid, mpos, flag, lib, name_key, device=0):
+    """bdx_mark_duplicates on host arrays: (bool mask of the records the rule marks, groups of two or more)"""
+    lb = L.load()
+    cols = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((tid, np.int32), (pos, np.int32), (mtid, np.int32), (mpos, np.int32),
+                                                            (flag, np.uint16), (lib, np.uint8), (name_key, np.uint64))]
+    n = len(cols[0])
+    if any(len(c) != n for c in cols):
+        raise ValueError("the columns differ in length")
+    out = np.zeros(n, np.uint8)
+    groups = C.c_uint64(0)
+    rc = lb.bdx_mark_duplicates(device, *[c.ctypes.data_as(C.c_void_p) for c in cols], n, out.ctypes.data_as(C.c_void_p), C.byref(groups))
+    if rc != 0:
+        raise BdxError("bdx_mark_duplicates: %s" % lb.bdx_strerror(rc).decode())
+    return out.astype(bool), groups.value
 
 
 def poisson_log_upper_tail(lam, k, device=0):

@@ -109,6 +109,15 @@ struct PinBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// KD's scratch: the mark bits, the long-run bits and the counters (1/4 B per read, kept); what only runs longer than kDupT need is
+// allocated from their candidates' count and handed back when the marks are made
+struct KdScratch {
+    DevBuf bits, longbits, cnt;
+    DevBuf work, wrun, starts, pre, cbase, table, multi;
+    void release_long() { work.release(); wrun.release(); starts.release(); pre.release(); cbase.release(); table.release(); multi.release(); }
+    void release() { bits.release(); longbits.release(); cnt.release(); release_long(); }
+};
+
 constexpr int kNumStages = 12;
 constexpr int kK1MaxGrid = 8192;  // measured best on MI355X (tools/k1_probe.hip; again at the end of round 2: 2048 74.6 us, 4096 70.9,
                                   // 8192 69.9, 12288 72.5, 16384 73.4): 256 CUs x 32 workgroups queued, 4 independent waves each
@@ -262,6 +271,11 @@ struct bdx_ctx {
     DevBuf b_jq, b_jc;                // its queries and counts
     // ---- bdx_count_site_pairs ----
     DevBuf b_sq, b_sc;                // its sites and counts
+    // ---- bdx_set_mark_duplicates ----
+    bool mark_dup = false;            // KD marks duplicates in the flag column at the head of pass 1; pass 1 then does not start behind arriving batches
+    bool dup_done = false;            // KD has run over this load (nothing can be appended to it any more)
+    uint64_t dup_marked = 0, dup_groups = 0;
+    KdScratch kd;
 };
 
 namespace {
@@ -368,6 +382,8 @@ int enqueue_batch(bdx_ctx* c, const bdx_batch& b, bool lazy_keys) {
         if (rc != BDX_OK) return rc;
     }
     const size_t o = c->n, n = b.n;
+    if (c->mark_dup && c->dup_done && o)
+        return fail(c, BDX_ESTATE, "duplicates of this load are marked already: reads cannot be appended behind a run (bdx_reset_reads starts the next load)");
     hipStream_t s = c->copy_stream;
     if (o == 0) {  // a fresh store: pass 1 runs as the reads arrive
         c->key_segs.clear();
@@ -375,7 +391,7 @@ int enqueue_batch(bdx_ctx* c, const bdx_batch& b, bool lazy_keys) {
         if (tiles <= 0xFFFFFFFFull) {
             const int rc = pass1_prepare(c, (uint32_t)tiles);
             if (rc != BDX_OK) return rc;
-            c->k1_live = true;
+            c->k1_live = !c->mark_dup;   // (duplicates are marked over the whole store before K1 reads a flag)
         }
     }
     // (one stream: splitting the columns over two copy streams measured 10.8 ms against 9.1 ms for 15 M records)
@@ -420,6 +436,7 @@ int enqueue_batch(bdx_ctx* c, const bdx_batch& b, bool lazy_keys) {
     c->copy_pending = true;
     c->n += n;
     c->ran = false;
+    if (o == 0) c->dup_done = false;
     if (c->k1_live) {
         const uint32_t full = (uint32_t)(c->n / kTile);
         if (full >= c->k1_done + kStreamTilesMin) {
@@ -530,6 +547,7 @@ void bdx_destroy(bdx_ctx* c) {
                       &c->b_sv_out, &c->b_lib_index_out, &c->b_lib_pairs_out, &c->b_cn_key_out, &c->b_cn_value_out, &c->b_ltail_out, &c->b_sv_key,
                       &c->b_jq, &c->b_jc, &c->b_sq, &c->b_sc};
     for (DevBuf* b : bufs) b->release();
+    c->kd.release();
     PinBuf* pins[] = {&c->h_p1, &c->h_cnt, &c->h_counts, &c->h_regs, &c->h_pk, &c->h_groups, &c->h_terms, &c->h_flags, &c->h_hs_rec, &c->h_hs_aux, &c->h_hs_lists, &c->h_printed, &c->h_counts0, &c->h_counts2,
                       &c->h_sv_out, &c->h_lib_index, &c->h_lib_pairs, &c->h_cn_key, &c->h_cn_value, &c->h_ltail_dev};
     for (PinBuf* b : pins) b->release();
@@ -618,6 +636,7 @@ int bdx_reset_reads(bdx_ctx* c) {
     }
     c->n = 0;
     c->ran = false;
+    c->dup_done = false;
     c->cls_n = (size_t)-1;
     c->k1_live = false;
     c->k1_done = 0;
@@ -642,6 +661,7 @@ int bdx_set_device_reads(bdx_ctx* c, const bdx_batch* b) {
     c->cap = b->n;
     c->adopted = true;
     c->ran = false;
+    c->dup_done = false;
     c->cls_n = (size_t)-1;
     c->k1_live = false;
     c->key_segs.clear();
@@ -701,6 +721,104 @@ float ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_cl
 // K1 + finalize: class bytes, per-tile tables, *local* pass-1 counters
 int do_pass1(bdx_ctx* c, uint32_t na_cap = 0, bool wait = true, bool defer_second = false);
 int wait_pass1(bdx_ctx* c);
+
+
+// The segment table of the name keys (read lengths, second hashes) that the caller's pinned batches still hold (bdx_push), in b_seg:
+// [ns + 1] segment begins | [ns] key pointers | [ns] read-length pointers | [ns] second-hash pointers, each biased by -begin; a segment
+// that was copied points into the resident column.  *ns = 0: every key is in the resident column.
+int upload_key_segs(bdx_ctx* c, size_t* ns_out) {
+    *ns_out = 0;
+    bool any_host = false;
+    for (auto const& sg : c->key_segs) any_host |= sg.host != nullptr;
+    if (!any_host || c->adopted) return BDX_OK;
+    const size_t ns = c->key_segs.size();
+    std::vector<uint64_t> tab(4 * ns + 1);
+    for (size_t i = 0; i < ns; ++i) {
+        const bdx_ctx::KeySeg& sg = c->key_segs[i];
+        tab[i] = sg.begin;
+        tab[ns + 1 + i] = (uint64_t)(uintptr_t)(sg.host ? sg.host - sg.begin : c->d.key);
+        tab[2 * ns + 1 + i] = (uint64_t)(uintptr_t)(sg.host ? sg.host_qlen - sg.begin : c->d.qlen);
+        tab[3 * ns + 1 + i] = (uint64_t)(uintptr_t)(sg.host ? sg.host_check - sg.begin : c->d.check);
+    }
+    tab[ns] = c->n;
+    HIPCHK(c, c->b_seg.ensure(tab.size() * 8));
+    HIPCHK(c, hipMemcpyAsync(c->b_seg.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (tab is a local; this path is PCIe-bound anyway)
+    *ns_out = ns;
+    return BDX_OK;
+}
+
+// KD over columns in HBM: scan, the table for the runs longer than kDupT (sized from the work list's count, which the host reads), then
+// the marks into `flag` (the words that change) and / or `mask` (a byte per record).  The counts are added to *marked / *groups.
+int kd_run(bdx_ctx* c, KdParams p, KdScratch& k, uint16_t* flag, uint8_t* mask, hipStream_t s, uint64_t* marked, uint64_t* groups) {
+    if (!p.n) return BDX_OK;
+    const size_t nwords = (p.n + 63) / 64;
+    HIPCHK(c, k.bits.ensure(nwords * 8));
+    HIPCHK(c, k.longbits.ensure(nwords * 8));
+    HIPCHK(c, k.cnt.ensure(sizeof(KdCounts)));
+    p.bits = k.bits.as<uint64_t>(); p.longbits = k.longbits.as<uint64_t>(); p.cnt = k.cnt.as<KdCounts>();
+    HIPCHK(c, hipMemsetAsync(p.cnt, 0, sizeof(KdCounts), s));
+    launch_kd_scan(p, s);
+    HIPCHK(c, hipGetLastError());
+    KdCounts h{};
+    HIPCHK(c, hipMemcpyAsync(&h, p.cnt, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    if (h.nwork) {
+        if (h.nwork > (1u << 30)) return fail(c, BDX_ELIMIT, "more than 2^30 duplicate candidates in runs too long for direct comparison");
+        uint64_t slots = 1024;
+        while (slots < 2 * (uint64_t)h.nwork) slots <<= 1;
+        HIPCHK(c, k.work.ensure((size_t)h.nwork * 4));
+        HIPCHK(c, k.wrun.ensure((size_t)h.nwork * 4));
+        HIPCHK(c, k.starts.ensure(nwords * 8));
+        HIPCHK(c, k.pre.ensure(nwords * 4));
+        HIPCHK(c, k.cbase.ensure((size_t)kd_chunks(p.n) * 4));
+        HIPCHK(c, k.table.ensure(slots * 4));
+        HIPCHK(c, k.multi.ensure(slots * 4));
+        p.work = k.work.as<uint32_t>(); p.wrun = k.wrun.as<uint32_t>(); p.starts = k.starts.as<uint64_t>();
+        p.pre = k.pre.as<uint32_t>(); p.cbase = k.cbase.as<uint32_t>();
+        p.table = k.table.as<uint32_t>(); p.multi = k.multi.as<uint32_t>(); p.tmask = slots - 1;
+        launch_kd_long(p, h.nwork, s);
+        HIPCHK(c, hipGetLastError());
+    }
+    launch_kd_apply(p, flag, mask, s);
+    HIPCHK(c, hipGetLastError());
+    if (h.nwork) {
+        HIPCHK(c, hipMemcpyAsync(&h, p.cnt, sizeof(h), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
+        if (h.nlist != h.nwork) return fail(c, BDX_EINTERNAL, "duplicate marking: the work list does not hold the candidates that were counted");
+        k.release_long();   // (the stream has drained)
+    }
+    *marked += h.marked; *groups += h.groups;
+    return BDX_OK;
+}
+
+// bdx_set_mark_duplicates: KD over the store at the head of a pass 1 that starts from tile 0, once per load
+int mark_duplicates(bdx_ctx* c) {
+    if (c->dup_done) return BDX_OK;   // (nothing was appended since: enqueue_batch and the gathers refuse that)
+    c->dup_marked = 0; c->dup_groups = 0;
+    hipStream_t s = c->stream;
+    if (c->adopted && (const void*)c->d.flag != c->b_flag.p) {   // the caller's arrays are const: a private copy of the flag column takes the marks
+        HIPCHK(c, c->b_flag.ensure(c->n * 2));
+        HIPCHK(c, hipMemcpyAsync(c->b_flag.p, c->d.flag, c->n * 2, hipMemcpyDeviceToDevice, s));
+        c->d.flag = c->b_flag.as<uint16_t>();
+    }
+    KdParams p{};
+    p.tid = c->d.tid; p.pos = c->d.pos; p.mtid = c->d.mtid; p.mpos = c->d.mpos; p.flag = c->d.flag;
+    p.lib = c->nlibs > 1 ? c->d.lib : nullptr;   // (with one library the column is not copied)
+    p.key = c->d.key; p.n = c->n;
+    size_t ns = 0;
+    int rc = upload_key_segs(c, &ns);
+    if (rc != BDX_OK) return rc;
+    if (ns) {
+        p.nseg = (int)ns;
+        p.seg_begin = c->b_seg.as<uint64_t>();
+        p.seg_ptr = (const uint64_t* const*)(c->b_seg.as<uint64_t>() + ns + 1);
+    }
+    rc = kd_run(c, p, c->kd, (uint16_t*)c->d.flag, nullptr, s, &c->dup_marked, &c->dup_groups);
+    if (rc != BDX_OK) return rc;
+    c->dup_done = true;
+    return BDX_OK;
+}
 
 // Start of a pass 1: per-tile tables laid out for tiles_cap tiles, counters and tables at their start values.
 int pass1_prepare(bdx_ctx* c, uint32_t tiles_cap) {
@@ -791,6 +909,10 @@ int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second) {
         if (rc != BDX_OK) return rc;
     }
     c->k1_live = false;  // (consumed: a repeated run classifies everything again)
+    if (c->mark_dup && c->k1_done == 0) {   // classification starts from tile 0: the marks are in the flag column before K1 reads it
+        const int rc = mark_duplicates(c);
+        if (rc != BDX_OK) return rc;
+    }
     const uint32_t tstride = c->tstride;
     const bool time_k1 = (c->stage_timing || c->seq % kK1EventPeriod == 0) && c->k1_done == 0 && ntiles > 0;
     {
@@ -955,22 +1077,10 @@ int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepa
         }
         if (sz) return BDX_OK;
         {   // name keys the caller's pinned batches still hold (bdx_push): one segment per batch
-            bool any_host = false;
-            for (auto const& sg : c->key_segs) any_host |= sg.host != nullptr;
-            if (any_host && !c->adopted) {
-                const size_t ns = c->key_segs.size();
-                std::vector<uint64_t> tab(4 * ns + 1);
-                for (size_t i = 0; i < ns; ++i) {
-                    const bdx_ctx::KeySeg& sg = c->key_segs[i];
-                    tab[i] = sg.begin;
-                    tab[ns + 1 + i] = (uint64_t)(uintptr_t)(sg.host ? sg.host - sg.begin : c->d.key);
-                    tab[2 * ns + 1 + i] = (uint64_t)(uintptr_t)(sg.host ? sg.host_qlen - sg.begin : c->d.qlen);
-                    tab[3 * ns + 1 + i] = (uint64_t)(uintptr_t)(sg.host ? sg.host_check - sg.begin : c->d.check);
-                }
-                tab[ns] = c->n;
-                HIPCHK(c, c->b_seg.ensure(tab.size() * 8));
-                HIPCHK(c, hipMemcpyAsync(c->b_seg.p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
-                HIPCHK(c, hipStreamSynchronize(s));  // (tab is a local; this path is PCIe-bound anyway)
+            size_t ns = 0;
+            const int rc = upload_key_segs(c, &ns);
+            if (rc != BDX_OK) return rc;
+            if (ns) {
                 k2.nseg = (int)ns;
                 k2.seg_begin = c->b_seg.as<uint64_t>();
                 k2.seg_ptr = (const uint64_t* const*)(c->b_seg.as<uint64_t>() + ns + 1);
@@ -2146,6 +2256,58 @@ int bdx_use_name_check(bdx_ctx* c, int on) {
     }
     if (!c->use_check) c->d.check = nullptr;
     return BDX_OK;
+}
+
+int bdx_set_mark_duplicates(bdx_ctx* c, int on) {
+    if (!c) return BDX_EINVAL;
+    if ((on != 0) == c->mark_dup) return BDX_OK;
+    if (c->n) return fail(c, BDX_ESTATE, "duplicate marking is switched while the context holds no reads");
+    c->mark_dup = on != 0;
+    c->k1_live = false;
+    c->dup_done = false;
+    c->dup_marked = 0; c->dup_groups = 0;
+    return BDX_OK;
+}
+
+int bdx_get_duplicates(const bdx_ctx* c, uint64_t* n_marked, uint64_t* n_groups) {
+    if (!c) return BDX_EINVAL;
+    if (!c->ran) return BDX_ESTATE;
+    const bool have = c->mark_dup && c->dup_done;
+    if (n_marked) *n_marked = have ? c->dup_marked : 0;
+    if (n_groups) *n_groups = have ? c->dup_groups : 0;
+    return BDX_OK;
+}
+
+int bdx_mark_duplicates(int device, const int32_t* tid, const int32_t* pos, const int32_t* mtid, const int32_t* mpos, const uint16_t* flag,
+                        const uint8_t* lib, const uint64_t* name_key, size_t n, uint8_t* mask, uint64_t* n_groups) {
+    if (n_groups) *n_groups = 0;
+    if (n == 0) return BDX_OK;
+    if (!tid || !pos || !mtid || !mpos || !flag || !lib || !name_key || !mask) return BDX_EINVAL;
+    if (n >= ((size_t)1 << 32)) return BDX_ELIMIT;
+    if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
+    DevBuf col[7], out;
+    KdScratch k;
+    const void* src[7] = {tid, pos, mtid, mpos, flag, lib, name_key};
+    const size_t esz[7] = {4, 4, 4, 4, 2, 1, 8};
+    int rc = BDX_OK;
+    for (int i = 0; i < 7 && rc == BDX_OK; ++i) {
+        if (col[i].ensure(n * esz[i]) != hipSuccess) rc = BDX_ENOMEM;
+        else if (hipMemcpy(col[i].p, src[i], n * esz[i], hipMemcpyHostToDevice) != hipSuccess) rc = BDX_EHIP;
+    }
+    if (rc == BDX_OK && out.ensure(n) != hipSuccess) rc = BDX_ENOMEM;
+    if (rc == BDX_OK) {
+        KdParams p{};
+        p.tid = col[0].as<int32_t>(); p.pos = col[1].as<int32_t>(); p.mtid = col[2].as<int32_t>(); p.mpos = col[3].as<int32_t>();
+        p.flag = col[4].as<uint16_t>(); p.lib = col[5].as<uint8_t>(); p.key = col[6].as<uint64_t>(); p.n = n;
+        uint64_t marked = 0, groups = 0;
+        rc = kd_run(nullptr, p, k, nullptr, out.as<uint8_t>(), nullptr, &marked, &groups);
+        if (rc == BDX_OK && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(mask, out.p, n, hipMemcpyDeviceToHost) != hipSuccess)) rc = BDX_EHIP;
+        if (rc == BDX_OK && n_groups) *n_groups = groups;
+    }
+    for (DevBuf& b : col) b.release();
+    out.release();
+    k.release();
+    return rc;
 }
 
 int bdx_set_debug(bdx_ctx* c, const char* name, int value) {

@@ -530,6 +530,7 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
     }
     if (sink) {
         if (sink->adopted) return bad(BDX_ESTATE);
+        if (sink->n && sink->mark_dup && sink->dup_done) return bad(BDX_ESTATE);   // (a load whose duplicates are marked takes no more reads)
         if (sink->n == 0 && p->expected_bytes) {   // (a record takes 50-150 bytes of BAM; a store that is too small grows)
             // ... plus room for what the batches in flight could hold at most (36 bytes is the smallest record): the store must be able to
             // take them before their record counts are known, and growing it means waiting for the device and copying the columns
@@ -538,12 +539,13 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
             if (sink->cap < want && alloc_reads(sink, want) != BDX_OK) return bad(BDX_ENOMEM);
             mark("sink store");
         }
+        if (sink->n == 0) sink->dup_done = false;
         if (sink->n == 0 && sink->cap) {   // pass 1 runs as the records arrive
             sink->key_segs.clear();
             const uint64_t tiles = (sink->cap + kTile - 1) / kTile;
             if (tiles <= 0xFFFFFFFFull) {
                 if (pass1_prepare(sink, (uint32_t)tiles) != BDX_OK) return bad(BDX_EHIP);
-                sink->k1_live = true;
+                sink->k1_live = !sink->mark_dup;   // (duplicates are marked over the whole store before K1 reads a flag)
             }
         }
         mark("pass-1 tables");
@@ -1018,6 +1020,7 @@ int gather_decoded(bdx_ctx* c, bdx_bamdec* const* decs, int k, const uint8_t* sr
     if (!c || !decs || k < 1 || k > kMaxGatherSources || (n && (!src_file || !src_index))) return BDX_EINVAL;
     if (c->adopted) return fail(c, BDX_ESTATE, "the context's reads are not its own");
     if (base + n > 0xFFFFFFFFull - 1024) return fail(c, BDX_ELIMIT, "one context holds at most 2^32 - 1 reads");
+    if (base && c->mark_dup && c->dup_done) return fail(c, BDX_ESTATE, "duplicates of this load are marked already: reads cannot be appended behind a run");
     HIPCHK(c, hipSetDevice(c->device));
     GatherSources src{};
     src.k = k;
@@ -1059,6 +1062,7 @@ int gather_decoded(bdx_ctx* c, bdx_bamdec* const* decs, int k, const uint8_t* sr
     c->n = (size_t)(base + n);
     c->ran = false;
     c->k1_live = false;
+    if (!base) c->dup_done = false;
     if (!base) c->key_segs.clear();
     return BDX_OK;
 }

@@ -219,6 +219,36 @@ struct KsParams {
     uint32_t* counts;                   // [nq][nkeys]
 };
 
+// KD (kd_markdup.hip): duplicate marking over the resident store (bdx_set_mark_duplicates, bdx_mark_duplicates)
+constexpr int kDupT = 64;               // neighbours a record looks at each way; runs of more records go through the table
+struct KdCounts {
+    unsigned long long marked, groups;  // records that got 0x400; groups of two or more
+    uint32_t nwork, nlist;              // candidates of runs longer than kDupT (counted by kd_scan); work-list entries appended so far
+};
+struct KdParams {
+    const int32_t *tid, *pos, *mtid, *mpos;
+    const uint16_t* flag;
+    const uint8_t* lib;                 // null: one library
+    const uint64_t* key;                // name keys (nseg == 0) ...
+    int nseg;                           // ... or K2Params' segments: keys the caller's pinned batches still hold
+    const uint64_t* seg_begin;
+    const uint64_t* const* seg_ptr;
+    uint64_t n;
+    uint64_t* bits;                     // [(n + 63) / 64] one bit per record: it is marked
+    uint64_t* longbits;                 // likewise: it is a candidate of a run longer than kDupT
+    KdCounts* cnt;                      // zeroed by the caller
+    // only for a count of long-run candidates that is not zero, sized from it:
+    uint32_t *work, *wrun;              // [nwork] the work list (record indices) and the entries' run ids
+    uint64_t* starts;                   // [(n + 63) / 64] one bit per record: it starts a run
+    uint32_t *pre, *cbase;              // [(n + 63) / 64], [kd_chunks(n)]: run starts before each word in its chunk, before each chunk
+    uint32_t *table, *multi;            // [tmask + 1] each: the table (work-list indices) and its "group has a loser" words
+    uint64_t tmask;
+};
+uint32_t kd_chunks(uint64_t n);
+void launch_kd_scan(const KdParams& p, hipStream_t s);
+void launch_kd_long(const KdParams& p, uint32_t nwork, hipStream_t s);
+void launch_kd_apply(const KdParams& p, uint16_t* flag, uint8_t* mask, hipStream_t s);
+
 // launchers (host side, defined in the .hip files)
 void launch_k8(const K8Params& p, hipStream_t s);
 void launch_ks(const KsParams& p, hipStream_t s);

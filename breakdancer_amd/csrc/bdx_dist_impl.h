@@ -606,6 +606,23 @@ int bdx_dist_set_debug(bdx_dist* d, const char* name, int value) {
     return rc;
 }
 
+// bdx_set_mark_duplicates for this rank's reads: a chromosome lives whole on one rank, so every run of equal (tid, pos) does too
+int bdx_dist_set_mark_duplicates(bdx_dist* d, int on) {
+    if (!d || !d->reads) return BDX_EINVAL;
+    const int rc = bdx_set_mark_duplicates(d->reads, on);
+    return rc == BDX_OK ? rc : dfail(d, rc, d->reads->err);
+}
+
+int bdx_dist_get_duplicates(const bdx_dist* d, uint64_t* n_marked, uint64_t* n_groups) {
+    if (!d || !d->reads) return BDX_EINVAL;
+    if (!d->ran) return BDX_ESTATE;
+    const bdx_ctx* c = d->reads;
+    const bool have = c->mark_dup && c->dup_done;
+    if (n_marked) *n_marked = have ? c->dup_marked : 0;
+    if (n_groups) *n_groups = have ? c->dup_groups : 0;
+    return BDX_OK;
+}
+
 int bdx_dist_get_exchange(const bdx_dist* d, uint64_t* ctx_records_sent, uint64_t* ctx_records_received, uint64_t* gathered_bytes,
                           float* ms_total, float* ms_exchange) {
     if (!d) return BDX_EINVAL;

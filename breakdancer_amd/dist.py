@@ -172,6 +172,18 @@ class DistRun:
         return dict(ctx_records_sent=sent.value, ctx_records_received=recv.value, gathered_bytes=gathered.value, ms_total=ms_total.value,
                     ms_exchange=ms_x.value)
 
+    def mark_duplicates(self, on=True):
+        """duplicate marking on this rank's reads (bdx_dist_set_mark_duplicates); before the chromosomes are fed"""
+        self.lib.bdx_dist_set_mark_duplicates.argtypes = [C.c_void_p, C.c_int]
+        self._chk(self.lib.bdx_dist_set_mark_duplicates(self.h, 1 if on else 0), "bdx_dist_set_mark_duplicates")
+
+    def duplicates(self):
+        """(records marked, groups of two or more) among this rank's reads in the last run (bdx_dist_get_duplicates)"""
+        m, g = C.c_uint64(0), C.c_uint64(0)
+        self.lib.bdx_dist_get_duplicates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.bdx_dist_get_duplicates(self.h, C.byref(m), C.byref(g)), "bdx_dist_get_duplicates")
+        return m.value, g.value
+
     def set_debug(self, name, value=1):
         """a test / measurement switch for this rank's contexts, the result context included (bdx_dist_set_debug)"""
         self.lib.bdx_dist_set_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int]

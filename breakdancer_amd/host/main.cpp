@@ -469,6 +469,7 @@ int run(int argc, char** argv) {
             ctx_ready = std::async(std::launch::async, [&] {
                 int rc = bdx_create(&ctx, &opts.o, libs.data(), nlibs, nbams, 0, cfg.max_read_window_size(), opts.device);
                 if (rc == BDX_OK) rc = bdx_use_name_check(ctx, 1);   // mates are joined on two hashes of the read name
+                if (rc == BDX_OK && opts.mark_dup) rc = bdx_set_mark_duplicates(ctx, 1);
                 return rc;
             });
         // resident store sized from the compressed files (a record takes 50-150 bytes of BAM; a store that is too small
@@ -492,6 +493,9 @@ int run(int argc, char** argv) {
             int rc = bdx_dist_create_threads(ranks.data(), &opts.o, libs.data(), nlibs, nbams, ntids, cfg.max_read_window_size(), devices.data(), world);
             if (rc != BDX_OK) throw std::runtime_error(std::string("bdx_dist_create_threads: ") + bdx_strerror(rc));
             const auto t_created = now();
+            if (opts.mark_dup)
+                for (bdx_dist* r : ranks)
+                    if (bdx_dist_set_mark_duplicates(r, 1) != BDX_OK) throw std::runtime_error(std::string("bdx_dist_set_mark_duplicates: ") + bdx_dist_last_error(r));
             if (want_dumps)   // -g / -d: the supporting reads come with the result (gathered compact records, walked read by read on rank 0)
                 for (bdx_dist* r : ranks) bdx_dist_set_collect_support(r, 1);
             std::vector<uint64_t> weight(lengths.begin(), lengths.end());  // chromosomes -> ranks by sequence length
@@ -573,6 +577,18 @@ int run(int argc, char** argv) {
             check(ctx, bdx_run(ctx), "bdx_run");
         }
         const auto t_ran = now();
+        uint64_t dup_marked = 0, dup_groups = 0;   // --mark-dup: over all ranks
+        if (opts.mark_dup) {
+            if (sharded) {
+                for (bdx_dist* r : ranks) {
+                    uint64_t m = 0, g = 0;
+                    if (bdx_dist_get_duplicates(r, &m, &g) != BDX_OK) throw std::runtime_error(std::string("bdx_dist_get_duplicates: ") + bdx_dist_last_error(r));
+                    dup_marked += m; dup_groups += g;
+                }
+            } else {
+                check(ctx, bdx_get_duplicates(ctx, &dup_marked, &dup_groups), "bdx_get_duplicates");
+            }
+        }
 
         bdx_summary sum;
         check(ctx, bdx_get_summary(ctx, &sum), "bdx_get_summary");
@@ -800,21 +816,22 @@ int run(int argc, char** argv) {
                     const size_t p = b.rfind("/");
                     samples.push_back(p != std::string::npos ? b.substr(p + 1) : b);
                 }
-            if (vcf) vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(vcf_rows), opts.exclude);
+            if (vcf) vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(vcf_rows), opts.exclude, nullptr, opts.mark_dup);
             vcf.reset();
             if (sites_vcf) {
                 const VcfSites info{opts.sites, sites_window};
-                sites_vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(site_rows), opts.exclude, &info);
+                sites_vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(site_rows), opts.exclude, &info, opts.mark_dup);
             }
             sites_vcf.reset();
         }
         if (timing) {
             if (exclude) print_exclude_timing(*exclude);
+            if (opts.mark_dup) fprintf(stderr, "[bdx timing] --mark-dup: marked %llu duplicate records in %llu groups\n", (unsigned long long)dup_marked, (unsigned long long)dup_groups);
             float ms[8] = {0};
             bdx_get_timings(ctx, ms, 8);
-            fprintf(stderr, "[bdx timing] reads=%zu decode+merge+stream=%.3fs (%s, single pass, records classified "
-                            "as they are produced) bdx_run=%.4fs format=%.3fs total=%.3fs\n",
+            fprintf(stderr, "[bdx timing] reads=%zu decode+merge+stream=%.3fs (%s, single pass, %s) bdx_run=%.4fs format=%.3fs total=%.3fs\n",
                     n_reads, secs(t_start, t_decoded), device_decoded || sharded_on_device ? "BGZF inflate and record decode on the GPU" : "host decode threads",
+                    opts.mark_dup ? "records marked and classified inside bdx_run" : "records classified as they are produced",
                     secs(t_decoded, t_ran), secs(t_ran, now()), secs(t_start, now()));
             fprintf(stderr, "[bdx timing] inside bdx_run (ms): classify kernel %.3f, host waits for its share of the groups %.3f, host walk %.3f, "
                             "final wait + scores %.3f, whole call %.3f\n", ms[0], ms[4], ms[5], ms[6], ms[7]);

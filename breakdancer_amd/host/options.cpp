@@ -65,6 +65,7 @@ void print_usage(const bdx_opts& o) {
     fprintf(stderr, "       --sites FILE   genotype the SV sites of this table (the tool's own output columns) over the records the run holds\n");
     fprintf(stderr, "       --sites-vcf FILE   the VCF the --sites genotypes are written to (GT:GQ:PL:DR:DV; required with --sites)\n");
     fprintf(stderr, "       --sites-window INT how far from a breakpoint a supporting read may start [the largest library uppercutoff]\n");
+    fprintf(stderr, "       --mark-dup     flag duplicate read pairs (same library, positions and strands of both mates) on the GPU; they are ignored like reads with SAM flag 0x400\n");
     fprintf(stderr, "\n");
 }
 
@@ -74,10 +75,11 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
     // (the reference's letters parse exactly as with getopt; the long options are this tool's own)
-    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow };
+    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup };
     static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude},
                                          {"sites", required_argument, nullptr, kSites}, {"sites-vcf", required_argument, nullptr, kSitesVcf},
-                                         {"sites-window", required_argument, nullptr, kSitesWindow}, {nullptr, 0, nullptr, 0}};
+                                         {"sites-window", required_argument, nullptr, kSitesWindow}, {"mark-dup", no_argument, nullptr, kMarkDup},
+                                         {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
         if (c == kVcf) {
@@ -86,6 +88,10 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
         }
         if (c == kExclude) {
             exclude = optarg;
+            continue;
+        }
+        if (c == kMarkDup) {
+            mark_dup = true;
             continue;
         }
         if (c == kSites) {

@@ -1,6 +1,6 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
-// (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf, --exclude and --sites / --sites-vcf /
-// --sites-window.
+// (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf, --exclude, --sites / --sites-vcf /
+// --sites-window and --mark-dup.
 #pragma once
 #include <string>
 #include <vector>
@@ -20,6 +20,7 @@ struct Options {
     std::string exclude;         // --exclude: a BED file of regions whose read pairs the readers drop (exclude.h)
     std::string sites;           // --sites: a table of SV sites to genotype over the records the run holds (sites.h) ...
     std::string sites_vcf;       // --sites-vcf: ... and the VCF they are written to (one needs the other)
+    bool mark_dup = false;       // --mark-dup: duplicate read pairs get SAM flag 0x400 on the GPU before pass 1 (bdx_set_mark_duplicates)
     int sites_window = -1;       // --sites-window: how far from a breakpoint a supporting read may start (-1: from the libraries' cutoffs)
     bdx_opts o;                  // numeric options in the C-ABI layout
     std::vector<std::string> orig_argv;

@@ -36,7 +36,7 @@ VcfWriter::~VcfWriter() {
 
 void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                       const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude,
-                      const VcfSites* sites) {
+                      const VcfSites* sites, bool mark_dup) {
     if (!f_) throw std::runtime_error("VCF output file '" + path_ + "' is already closed");
     FILE* f = f_;
     fprintf(f, "##fileformat=VCFv4.2\n##source=breakdancer-max-mi355x\n##command=");
@@ -44,6 +44,7 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
     fprintf(f, "\n");
     if (!exclude.empty()) fprintf(f, "##exclude=%s\n", exclude.c_str());
     if (sites) fprintf(f, "##sites=%s\n##sites_window=%d\n", sites->file.c_str(), sites->window);
+    if (mark_dup) fprintf(f, "##mark_dup=1\n");
     for (size_t t = 0; t < contigs.size(); ++t)
         fprintf(f, "##contig=<ID=%s,length=%u>\n", contigs[t].c_str(), t < lengths.size() ? lengths[t] : 0u);
     fputs("##FILTER=<ID=PASS,Description=\"All filters passed\">\n"

@@ -48,10 +48,10 @@ public:
     VcfWriter& operator=(const VcfWriter&) = delete;
     // header + records, sorted by (chr1, pos1) with ties in row order; `contigs` are the reference sequences (names are also the
     // records' CHROM / CHR2 values); exclude: the --exclude file of the run ("": none) for the ##exclude= line; sites: non-null for a
-    // --sites-vcf output; the file is closed afterwards
+    // --sites-vcf output; mark_dup: the run marked duplicates (--mark-dup), for the ##mark_dup=1 line; the file is closed afterwards
     void write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude = "",
-               const VcfSites* sites = nullptr);
+               const VcfSites* sites = nullptr, bool mark_dup = false);
 
 private:
     std::string path_;

@@ -566,6 +566,39 @@ int bdx_count_junction_pairs(bdx_ctx* ctx, const int32_t* tid, const int32_t* po
 typedef struct bdx_site { int32_t tid1, pos1, tid2, pos2; uint32_t flag_mask; } bdx_site;
 int bdx_count_site_pairs(bdx_ctx* ctx, const bdx_site* sites, size_t n, int32_t window, int by_library, uint32_t* counts); /* [n][nkeys] */
 
+/* Duplicate marking: no counterpart in the reference, which only ignores reads that already carry SAM flag 0x400
+ * (io/IlluminaPEReadClassifier.cpp:66-74; K1 restates that).  The rule, written down here once:
+ *   RUNS        the store is cut into runs: maximal stretches of consecutive records with equal (tid, pos).  For coordinate-sorted input a
+ *               run is all records that start at one position; the rule is defined for any input this way (no sortedness is asked for).
+ *   CANDIDATES  a record with flag & 0x1, none of 0x4, 0x8, 0x100, 0x400, 0x800, tid >= 0 and mtid >= 0.  A record that already carries
+ *               0x400 stays as it is and competes with nobody.
+ *   KEY         K = (lib, tid, pos, flag & 0x10, mtid, mpos, flag & 0x20, flag & 0x40): the library, not the file (one library spread over
+ *               two BAMs is one library); the first-in-pair bit keeps the two mates of a pair that start at one place with one strand apart.
+ *   GROUPS      the candidates of one run with equal K.  In a group of two or more the record with the smallest (name_key, store index)
+ *               survives and every other record gets 0x400.  Groups of one, and non-candidates, are untouched.
+ * Only what the record itself carries is looked at (as in --exclude's and --sites' rules): not CIGAR or unclipped ends, base qualities, or
+ * the mate's own record -- position-and-strand marking in the manner of samtools rmdup.  Both mates of a pair carry one name_key and the
+ * group seen from the mate's end mirrors the group seen from this end (mates in the store and consistent), so both ends keep the same pair.
+ * Two different pairs whose name keys collide inside one group fall to the index and may keep different pairs at the two ends.
+ *   bdx_set_mark_duplicates  while the context holds no reads (BDX_ESTATE otherwise); default off.  With it on, pass 1 does not start
+ *                            behind arriving batches: the marking kernel (KD, csrc/kd_markdup.hip) runs over the whole store at the head
+ *                            of pass 1, once per load -- a repeated bdx_run gives the same table and counts --, and everything downstream
+ *                            sees the marked flag column.  The marks are defined per load: once a run has marked it, bdx_push,
+ *                            bdx_submit_batch, a decoder and bdx_append_decoded refuse to append (BDX_ESTATE) until bdx_reset_reads.  Reads adopted with bdx_set_device_reads stay unchanged: the context marks a
+ *                            private copy of their flag column (2 B per read)
+ *   bdx_get_duplicates       after a run (BDX_ESTATE before): records that got 0x400, and groups of two or more.  Either pointer may be NULL
+ *   bdx_dist_*               the same for a rank's reads (a chromosome lives whole on one rank, so every run does); the getter returns this
+ *                            rank's sums, after bdx_dist_run
+ *   bdx_mark_duplicates      kernel-level entry point on host arrays (parity tests; callers that filter their own columns): mask[i] = 1
+ *                            where the rule marks record i, *n_groups (may be NULL) = groups of two or more.  n == 0 is BDX_OK; a null
+ *                            array with n > 0 is BDX_EINVAL; BDX_ELIMIT from 2^32 records */
+int bdx_set_mark_duplicates(bdx_ctx* ctx, int on);
+int bdx_get_duplicates(const bdx_ctx* ctx, uint64_t* n_marked, uint64_t* n_groups);
+int bdx_dist_set_mark_duplicates(bdx_dist* d, int on);
+int bdx_dist_get_duplicates(const bdx_dist* d, uint64_t* n_marked, uint64_t* n_groups);
+int bdx_mark_duplicates(int device, const int32_t* tid, const int32_t* pos, const int32_t* mtid, const int32_t* mpos, const uint16_t* flag,
+                        const uint8_t* lib, const uint64_t* name_key, size_t n, uint8_t* mask, uint64_t* n_groups);
+
 /* device the context is bound to and the HIP stream it launches on (as void*), for callers that time it */
 int bdx_device(const bdx_ctx* ctx);
 void* bdx_stream(const bdx_ctx* ctx);
