@@ -7,9 +7,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <sys/mman.h>
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/bdx.h"
+#include "bdx_buf.h"
 #include "bdx_dev.h"
 #include "bdx_k3.h"
 #include "bdx_shard.h"
@@ -33,89 +34,12 @@ using namespace bdx;
 
 namespace {
 
-// BDX_ALLOC_TRACE=1: every allocation of a context's buffers with its size and duration on stderr
-inline bool alloc_trace() { static const bool on = getenv("BDX_ALLOC_TRACE") != nullptr; return on; }
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t b) {
-        if (b <= bytes) return hipSuccess;
-        const auto t0 = std::chrono::steady_clock::now();
-        const bool had = p != nullptr;
-        if (p) (void)hipFree(p);   // (waits for the device to go idle: steady-state code must not get here)
-        p = nullptr;
-        bytes = 0;
-        size_t want = b + b / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (alloc_trace()) fprintf(stderr, "[bdx alloc] device %12zu B %8.1f us%s\n", want, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), had ? " (regrown: hipFree first)" : "");
-        if (e == hipSuccess) bytes = want;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    template <class T> T* as() const { return (T*)p; }
-};
-
-struct PinBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    // A large buffer is anonymous memory on transparent huge pages, registered with the runtime (hipHostRegister): 0.02 s per 0.5 GB
-    // against hipHostMalloc's 0.09-0.11 -- pinning is paid per page -- and a quarter less to hand back when the process ends
-    // (tools/pin_probe.hip, profiles/r05_pin_probe.txt); the device sees it at the same address.  Small buffers -- the words the host
-    // polls, the records kernels and host exchange mid-run -- stay with hipHostMalloc (fine-grained by default).  bdx_set_process_option("pin_malloc", 1): all of them.
-    void* map_base = nullptr;
-    size_t map_len = 0;
-    static std::atomic<bool>& registered_switch() { static std::atomic<bool> on{true}; return on; }   // bdx_set_process_option("pin_malloc", 1) turns it off
-    static bool use_registered() { return registered_switch().load(std::memory_order_relaxed); }
-    hipError_t ensure(size_t b) {
-        if (b <= bytes) return hipSuccess;
-        release();
-        size_t want = b + b / 8 + 256;
-        const auto t0 = std::chrono::steady_clock::now();
-        hipError_t e = hipErrorOutOfMemory;
-        constexpr size_t kHuge = (size_t)2 << 20;
-        if (want >= 2 * kHuge && use_registered()) {
-            const size_t len = (want + kHuge - 1) & ~(kHuge - 1);
-            void* base = mmap(nullptr, len + kHuge, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-            if (base != MAP_FAILED) {
-                void* al = (void*)(((uintptr_t)base + kHuge - 1) & ~(uintptr_t)(kHuge - 1));
-                (void)madvise(al, len, MADV_HUGEPAGE);
-                for (size_t o = 0; o < len; o += 4096) ((volatile char*)al)[o] = 0;   // (faulted in before it is pinned: one fault per huge page)
-                void* dev = nullptr;
-                if (hipHostRegister(al, len, hipHostRegisterMapped) == hipSuccess && hipHostGetDevicePointer(&dev, al, 0) == hipSuccess && dev == al) {
-                    p = al; map_base = base; map_len = len + kHuge; want = len; e = hipSuccess;
-                } else {
-                    (void)hipHostUnregister(al);
-                    (void)hipGetLastError();
-                    munmap(base, len + kHuge);
-                }
-            }
-        }
-        if (e != hipSuccess) {
-            e = hipHostMalloc(&p, want, hipHostMallocDefault);
-            // (small buffers hold the words the host polls and the counters kernels report: a block the allocator hands out again may still
-            // hold another context's ready word -- the same sequence number -- and a poll would return before the kernel has run)
-            if (e == hipSuccess && want <= ((size_t)1 << 20)) memset(p, 0, want);
-        }
-        if (alloc_trace()) fprintf(stderr, "[bdx alloc] pinned %12zu B %8.1f us%s\n", want, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), map_base ? " (registered huge pages)" : "");
-        if (e == hipSuccess) bytes = want; else p = nullptr;
-        return e;
-    }
-    void release() {
-        if (p && map_base) { (void)hipHostUnregister(p); munmap(map_base, map_len); }
-        else if (p) (void)hipHostFree(p);
-        p = nullptr; bytes = 0; map_base = nullptr; map_len = 0;
-    }
-    template <class T> T* as() const { return (T*)p; }
-};
-
 // KD's scratch: the mark bits, the long-run bits and the counters (1/4 B per read, kept); what only runs longer than kDupT need is
 // allocated from their candidates' count and handed back when the marks are made
 struct KdScratch {
     DevBuf bits, longbits, cnt;
     DevBuf work, wrun, starts, pre, cbase, table, multi;
     void release_long() { work.release(); wrun.release(); starts.release(); pre.release(); cbase.release(); table.release(); multi.release(); }
-    void release() { bits.release(); longbits.release(); cnt.release(); release_long(); }
 };
 
 constexpr int kNumStages = 12;
@@ -126,8 +50,11 @@ constexpr uint32_t kK1EventPeriod = 4;  // K1 is bracketed by HIP events on ever
 }  // namespace
 
 struct bdx_ctx {
+    // Order of release: members go in reverse order of declaration, so the two streams are declared FIRST and destroyed LAST, behind
+    // every buffer and event that is used on them (bdx_destroy synchronises both before anything goes).
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
+    Stream copy_stream;                 // H2D copies of the batches; the classifier follows each batch on `stream` behind ev_copy
     bdx_opts opts{};
     std::vector<bdx_lib> libs;
     int nlibs = 0, nbams = 0, ntids = 0, nkeys = 0, w0 = 0;
@@ -170,7 +97,7 @@ struct bdx_ctx {
     bool rows_packed = false;         // ... as SvWire rows (48 bytes: what a single-context run's table kernel writes over PCIe), not SvOut
     uint32_t n_sv_total = 0, n_groups_total = 0, n_terms_total = 0, n_cn_total = 0;
     PinBuf h_counts0, h_counts2, h_sv_out, h_lib_index, h_lib_pairs, h_cn_key, h_cn_value, h_ltail_dev;
-    hipEvent_t ev_groups = nullptr, ev_regions = nullptr;
+    Event ev_groups, ev_regions;
     int big_walk_mode = -1;           // BDX_BIG_WALK=1 / 0: components of 5..64 regions always / never walked on the device; default: when
                                       // the host's share is large enough to matter (see do_k6)
     int64_t last_big_groups = -1;     // groups of such components in the previous run of this context (device + host share)
@@ -228,7 +155,7 @@ struct bdx_ctx {
     const uint32_t* rpk = nullptr;
     std::vector<GroupPart> parts;
     WalkResult walk;
-    WalkScratch* walk_scratch = nullptr;
+    std::unique_ptr<WalkScratch, void (*)(WalkScratch*)> walk_scratch{nullptr, walk_scratch_free};
     uint32_t n_printed = 0;
     uint32_t n_sv_host = 0;
     // enqueue-ahead: a context that has just run an input of the same size sizes the later stages from that run's count of
@@ -243,11 +170,10 @@ struct bdx_ctx {
     bool region_of_fused = false;
     uint32_t join_table_clean = 0;    // slots of the direct join table already set to -1 (by K2), 0 = none
     float stage_ms[kNumStages] = {0};
-    hipEvent_t ev[8] = {nullptr};
+    Event ev[8];
 
     // ---- streamed input (bdx_push / bdx_acquire_batch + bdx_submit_batch) ----
-    hipStream_t copy_stream = nullptr;  // H2D copies of the batches; the classifier follows each batch on `stream` behind ev_copy
-    hipEvent_t ev_copy = nullptr;
+    Event ev_copy;
     bool copy_pending = false;          // copies enqueued since the last run: `stream` has to wait for ev_copy
     // pass 1 as the reads arrive: the tile tables are laid out for k1_cap_tiles tiles and tiles [0, k1_done) are classified
     bool k1_live = false;
@@ -255,7 +181,7 @@ struct bdx_ctx {
     struct Stage {                      // one pinned staging buffer of the ring
         PinBuf buf;
         size_t cap = 0;
-        hipEvent_t done = nullptr;
+        Event done;
         bool busy = false;
     };
     Stage ring[4];
@@ -302,6 +228,12 @@ int hipfail(bdx_ctx* c, hipError_t e, const char* what) {
         hipError_t _e = (expr);                             \
         if (_e != hipSuccess) return hipfail(ctx, _e, #expr); \
     } while (0)
+// the same for a call that returns a BDX_* status
+#define BDX_TRY(expr)                      \
+    do {                                   \
+        const int _rc = (expr);            \
+        if (_rc != BDX_OK) return _rc;     \
+    } while (0)
 
 size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 
@@ -339,8 +271,8 @@ int alloc_reads(bdx_ctx* c, size_t cap) {
         if (c->n) HIPCHK(c, hipMemcpyAsync(nb.p, col.b->p, c->n * col.esz, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         col.b->release();
-        *col.b = nb;
-        *col.slot = nb.p;
+        *col.b = std::move(nb);
+        *col.slot = col.b->p;
     }
     c->cap = cap;
     return BDX_OK;
@@ -378,8 +310,7 @@ constexpr uint32_t kStreamTilesMin = 4096;  // classify behind a batch only once
 // travel: K2 fetches the keys of the anomalous reads (about 1 %) straight from there.
 int enqueue_batch(bdx_ctx* c, const bdx_batch& b, bool lazy_keys) {
     if (c->n + b.n > c->cap) {
-        const int rc = alloc_reads(c, std::max(c->n + b.n, c->cap * 2));
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(alloc_reads(c, std::max(c->n + b.n, c->cap * 2)));
     }
     const size_t o = c->n, n = b.n;
     if (c->mark_dup && c->dup_done && o)
@@ -389,8 +320,7 @@ int enqueue_batch(bdx_ctx* c, const bdx_batch& b, bool lazy_keys) {
         c->key_segs.clear();
         const uint64_t tiles = (c->cap + kTile - 1) / kTile;
         if (tiles <= 0xFFFFFFFFull) {
-            const int rc = pass1_prepare(c, (uint32_t)tiles);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(pass1_prepare(c, (uint32_t)tiles));
             c->k1_live = !c->mark_dup;   // (duplicates are marked over the whole store before K1 reads a flag)
         }
     }
@@ -442,8 +372,7 @@ int enqueue_batch(bdx_ctx* c, const bdx_batch& b, bool lazy_keys) {
         if (full >= c->k1_done + kStreamTilesMin) {
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copy, 0));
             c->copy_pending = false;
-            const int rc = pass1_classify(c, full, false);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(pass1_classify(c, full, false));
         }
     }
     return BDX_OK;
@@ -486,21 +415,21 @@ int bdx_create(bdx_ctx** out, const bdx_opts* opts, const bdx_lib* libs, int nli
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return BDX_EHIP;
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
-    bdx_ctx* c = new (std::nothrow) bdx_ctx;
+    std::unique_ptr<bdx_ctx> c(new (std::nothrow) bdx_ctx);   // (a failure below frees what the context holds by then)
     if (!c) return BDX_ENOMEM;
     c->device = device;
     c->opts = *opts;
     c->libs.assign(libs, libs + nlibs);
     c->nlibs = nlibs; c->nbams = nbams; c->ntids = ntids; c->nkeys = nkeys; c->w0 = max_read_window_size0;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return BDX_EHIP; }
+    if (c->stream.create(hipStreamNonBlocking) != hipSuccess) return BDX_EHIP;
     for (auto& e : c->ev)
-        if (hipEventCreate(&e) != hipSuccess) { delete c; return BDX_EHIP; }
-    if (hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) { delete c; return BDX_EHIP; }
-    if (hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming) != hipSuccess) { delete c; return BDX_EHIP; }
+        if (e.create() != hipSuccess) return BDX_EHIP;
+    if (c->copy_stream.create(hipStreamNonBlocking) != hipSuccess) return BDX_EHIP;
+    if (c->ev_copy.create(hipEventDisableTiming) != hipSuccess) return BDX_EHIP;
     for (auto& st : c->ring)
-        if (hipEventCreateWithFlags(&st.done, hipEventDisableTiming) != hipSuccess) { delete c; return BDX_EHIP; }
-    if (hipEventCreateWithFlags(&c->ev_groups, hipEventDisableTiming) != hipSuccess) { delete c; return BDX_EHIP; }
-    if (hipEventCreateWithFlags(&c->ev_regions, hipEventDisableTiming) != hipSuccess) { delete c; return BDX_EHIP; }
+        if (st.done.create(hipEventDisableTiming) != hipSuccess) return BDX_EHIP;
+    if (c->ev_groups.create(hipEventDisableTiming) != hipSuccess) return BDX_EHIP;
+    if (c->ev_regions.create(hipEventDisableTiming) != hipSuccess) return BDX_EHIP;
     std::vector<DevLib> dl(nlibs);
     for (int i = 0; i < nlibs; ++i) {
         dl[i].upper = libs[i].uppercutoff;
@@ -513,50 +442,18 @@ int bdx_create(bdx_ctx** out, const bdx_opts* opts, const bdx_lib* libs, int nli
     if (c->b_libs.ensure(nlibs * sizeof(DevLib)) != hipSuccess ||
         hipMemcpy(c->b_libs.p, dl.data(), nlibs * sizeof(DevLib), hipMemcpyHostToDevice) != hipSuccess ||
         c->b_lib_mean.ensure(nlibs * 4) != hipSuccess ||
-        hipMemcpy(c->b_lib_mean.p, means.data(), nlibs * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        bdx_destroy(c);
+        hipMemcpy(c->b_lib_mean.p, means.data(), nlibs * 4, hipMemcpyHostToDevice) != hipSuccess)
         return BDX_EHIP;
-    }
-    *out = c;
+    *out = c.release();
     return BDX_OK;
 }
 
+// What is about ORDER; the buffers, events and streams themselves go with the context's members (see the head of bdx_ctx).
 void bdx_destroy(bdx_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& st : c->ring) {
-        st.buf.release();
-        if (st.done) (void)hipEventDestroy(st.done);
-    }
-    c->b_seg.release();
-    c->b_lb.release();
-    if (c->ev_copy) (void)hipEventDestroy(c->ev_copy);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    DevBuf* bufs[] = {&c->b_tid, &c->b_pos, &c->b_mtid, &c->b_mpos, &c->b_isize, &c->b_flag, &c->b_qlen, &c->b_mapq, &c->b_lib,
-                      &c->b_bam, &c->b_key, &c->b_check, &c->b_c_check, &c->b_x_check, &c->b_groups, &c->b_libs, &c->b_cls, &c->b_stash, &c->b_chunk_tot, &c->b_tile_tot, &c->b_tile_pre, &c->b_tile_mono,
-                      &c->b_blk_cnt, &c->b_cnt, &c->b_p1, &c->b_c_tid, &c->b_c_pos, &c->b_c_isize,
-                      &c->b_c_meta, &c->b_c_key, &c->b_c_idx, &c->b_c_nn, &c->b_c_pk, &c->b_cand, &c->b_pre_q, &c->b_pre_rev,
-                      &c->b_pre_nonctx, &c->b_c_first, &c->b_c_maxq, &c->b_c_rid, &c->b_region_of,
-                      &c->b_counts, &c->b_bcnt, &c->b_boff, &c->b_bcur, &c->b_e_key, &c->b_e_idx, &c->b_partner, &c->b_t_key,
-                      &c->b_t_idx, &c->b_x_key, &c->b_x_order, &c->b_x_region,
-                      &c->b_x_meta, &c->b_x_isize, &c->b_x_n, &c->b_fold, &c->b_lib_mean, &c->b_pair_lo, &c->b_sv_src, &c->b_dlists, &c->b_ltail, &c->b_r_rec, &c->b_r_pk, &c->b_out_deg,
-                      &c->b_parts, &c->b_kdens, &c->b_rs, &c->b_slot, &c->b_members, &c->b_own, &c->b_lib_stage,
-                      &c->b_cn_stage, &c->b_t_lambda, &c->b_t_k, &c->b_ws6, &c->b_ins, &c->b_member_ids,
-                      &c->b_sv_out, &c->b_lib_index_out, &c->b_lib_pairs_out, &c->b_cn_key_out, &c->b_cn_value_out, &c->b_ltail_out, &c->b_sv_key,
-                      &c->b_jq, &c->b_jc, &c->b_sq, &c->b_sc};
-    for (DevBuf* b : bufs) b->release();
-    c->kd.release();
-    PinBuf* pins[] = {&c->h_p1, &c->h_cnt, &c->h_counts, &c->h_regs, &c->h_pk, &c->h_groups, &c->h_terms, &c->h_flags, &c->h_hs_rec, &c->h_hs_aux, &c->h_hs_lists, &c->h_printed, &c->h_counts0, &c->h_counts2,
-                      &c->h_sv_out, &c->h_lib_index, &c->h_lib_pairs, &c->h_cn_key, &c->h_cn_value, &c->h_ltail_dev};
-    for (PinBuf* b : pins) b->release();
-    if (c->walk_scratch) walk_scratch_free(c->walk_scratch);
-    for (auto& e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev_groups) (void)hipEventDestroy(c->ev_groups);
-    if (c->ev_regions) (void)hipEventDestroy(c->ev_regions);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -565,8 +462,7 @@ int bdx_reserve(bdx_ctx* c, size_t n_reads) {
     if (c->adopted) return fail(c, BDX_ESTATE, "reads were adopted from the caller");
     NOT_WHILE_SIZING(c);
     HIPCHK(c, hipSetDevice(c->device));
-    const int rc = alloc_reads(c, n_reads);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(alloc_reads(c, n_reads));
     // The buffers of the stages behind pass 1 as well, for the prior a first run sizes them by (1/32 of the reads anomalous, see
     // bdx_run): ~60 device and pinned allocations, 3-4 ms at 15 M reads, most of it page pinning -- here they happen while the
     // caller still decodes or copies, not inside its first bdx_run.  Small inputs size theirs exactly, when they run.
@@ -617,8 +513,7 @@ int bdx_submit_batch(bdx_ctx* c, size_t n) {
     stage_view(st, &v);  // the layout bdx_acquire_batch handed out
     if (n > v.capacity) return fail(c, BDX_EINVAL, "more records than the acquired batch holds");
     bdx_batch b{v.tid, v.pos, v.mtid, v.mpos, v.isize, v.flag, v.qlen, v.mapq, v.lib, v.bam, v.name_key, n, v.name_check};
-    const int rc = enqueue_batch(c, b, false);  // (the buffer is recycled: its name keys travel with the other columns)
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(enqueue_batch(c, b, false));  // (the buffer is recycled: its name keys travel with the other columns)
     HIPCHK(c, hipEventRecord(st.done, c->copy_stream));
     st.busy = true;
     return BDX_OK;
@@ -807,15 +702,13 @@ int mark_duplicates(bdx_ctx* c) {
     p.lib = c->nlibs > 1 ? c->d.lib : nullptr;   // (with one library the column is not copied)
     p.key = c->d.key; p.n = c->n;
     size_t ns = 0;
-    int rc = upload_key_segs(c, &ns);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(upload_key_segs(c, &ns));
     if (ns) {
         p.nseg = (int)ns;
         p.seg_begin = c->b_seg.as<uint64_t>();
         p.seg_ptr = (const uint64_t* const*)(c->b_seg.as<uint64_t>() + ns + 1);
     }
-    rc = kd_run(c, p, c->kd, (uint16_t*)c->d.flag, nullptr, s, &c->dup_marked, &c->dup_groups);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(kd_run(c, p, c->kd, (uint16_t*)c->d.flag, nullptr, s, &c->dup_marked, &c->dup_groups));
     c->dup_done = true;
     return BDX_OK;
 }
@@ -894,7 +787,7 @@ int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second) {
     c->regions.clear(); c->r_pk.clear(); c->parts.clear();
     c->reg = nullptr; c->nreg = 0; c->rpk = nullptr;
     c->walk.clear();
-    if (!c->walk_scratch) c->walk_scratch = walk_scratch_new();
+    if (!c->walk_scratch) c->walk_scratch.reset(walk_scratch_new());
     c->n_printed = 0;
     memset(&c->counts, 0, sizeof(c->counts));
     for (float& m : c->stage_ms) m = 0;
@@ -905,19 +798,16 @@ int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second) {
     }
     // a store that was filled from empty has its first tiles classified already; anything else starts from tile 0
     if (!(c->k1_live && c->k1_cap_tiles >= ntiles)) {
-        const int rc = pass1_prepare(c, ntiles);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(pass1_prepare(c, ntiles));
     }
     c->k1_live = false;  // (consumed: a repeated run classifies everything again)
     if (c->mark_dup && c->k1_done == 0) {   // classification starts from tile 0: the marks are in the flag column before K1 reads it
-        const int rc = mark_duplicates(c);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(mark_duplicates(c));
     }
     const uint32_t tstride = c->tstride;
     const bool time_k1 = (c->stage_timing || c->seq % kK1EventPeriod == 0) && c->k1_done == 0 && ntiles > 0;
     {
-        const int rc = pass1_classify(c, ntiles, time_k1);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(pass1_classify(c, ntiles, time_k1));
     }
     FinalizeParams fp{};
     fp.ntiles = ntiles; fp.tstride = tstride; fp.nblk = 0;
@@ -1078,8 +968,7 @@ int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepa
         if (sz) return BDX_OK;
         {   // name keys the caller's pinned batches still hold (bdx_push): one segment per batch
             size_t ns = 0;
-            const int rc = upload_key_segs(c, &ns);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(upload_key_segs(c, &ns));
             if (ns) {
                 k2.nseg = (int)ns;
                 k2.seg_begin = c->b_seg.as<uint64_t>();
@@ -1182,8 +1071,7 @@ int do_cut(bdx_ctx* c, int has_next, int32_t next_qlen, uint32_t next_nn, bool f
         c->region_of_fused = for_k6 && !c->bucketed_join && na <= kDirectJoinMax;
         launch_k3(k3, cp, c->b_p1.as<Pass1>(), na, c->opts.min_len, c->opts.seq_coverage_lim, nkeys, nn_base, tail, !c->region_of_fused, s);
         if (for_k6 && !k3.host_copy_later) {  // the region table is in pinned memory
-            const int rc = signal_ready(c, 3, c->ev_regions);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(signal_ready(c, 3, c->ev_regions));
         }
     }
     if (sz) return BDX_OK;
@@ -1305,8 +1193,7 @@ int do_k6(bdx_ctx* c, bool force_host, int part = 0, const Sizing* sz = nullptr,
         if (!a.cap) return BDX_OK;
         launch_k6_components(a, a.cap, s);
         if (!c->poll) {
-            const int rc = signal_ready(c, 1, c->ev_groups);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(signal_ready(c, 1, c->ev_groups));
         }
         if (!c->defer_walk) launch_k6_walk(a, a.cap, s);
         return BDX_OK;
@@ -1434,8 +1321,7 @@ int do_k6(bdx_ctx* c, bool force_host, int part = 0, const Sizing* sz = nullptr,
     }
     launch_k6_groups(a, na, s);
     if (!c->poll) {  // the host's share of the groups is complete
-        const int rc = signal_ready(c, 1, c->ev_groups);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(signal_ready(c, 1, c->ev_groups));
     }
     launch_k6_walk(a, na, s);
     return BDX_OK;
@@ -1521,8 +1407,7 @@ int do_k6_table(bdx_ctx* c) {
     c->rows_packed = a.wire_rows != 0;
     launch_k6_table(a, na, std::log(10), c->opts.score_threshold, c->opts.fisher ? 0 : 1, s);
     if (!a.flag_done) {  // (without polling: finish_table waits for the stream)
-        const int rc = signal_ready(c, 2, nullptr);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(signal_ready(c, 2, nullptr));
     }
     return BDX_OK;
 }
@@ -1619,7 +1504,7 @@ int host_walk(bdx_ctx* c, int32_t last_maxq, bool any_anomalous) {
     wi.regions = c->reg; wi.nregions = c->nreg; wi.r_pk = c->rpk; wi.parts = &c->parts; wi.last_maxq = last_maxq;
     wi.any_anomalous = any_anomalous;
     c->walk.clear();
-    if (!c->parts.empty()) greedy_walk(wi, c->walk_scratch, c->walk);
+    if (!c->parts.empty()) greedy_walk(wi, c->walk_scratch.get(), c->walk);
     return BDX_OK;
 }
 
@@ -1758,8 +1643,7 @@ int replay_reads(bdx_ctx* c, uint32_t ph) {
         for (int32_t& r : region_of)
             if (r >= 0) r += (int32_t)ph;
     std::vector<uint32_t> sup;
-    int rc = replay_arrays(c, na, key.data(), region_of.data(), meta.data(), isize.data(), ph, c->collect_support ? &sup : nullptr);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(replay_arrays(c, na, key.data(), region_of.data(), meta.data(), isize.data(), ph, c->collect_support ? &sup : nullptr));
     if (c->collect_support) {  // compact indices -> stream indices and flags
         std::vector<uint32_t> idx(na);
         HIPCHK(c, hipMemcpy(idx.data(), c->cp.idx, (size_t)na * 4, hipMemcpyDeviceToHost));
@@ -1787,10 +1671,8 @@ int bdx_run(bdx_ctx* c) {
     const bool force_host = c->host_walk_only || ph_opt || c->opts.min_read_pair < 1;
     // K2 .. K6 (first half) for c->na_alloc anomalous reads
     auto enqueue_middle = [&]() -> int {
-        int r = do_compact(c, 0, nullptr, true);
-        if (r != BDX_OK) return r;
-        r = do_cut(c, 0, 0, 0, true);
-        if (r != BDX_OK) return r;
+        BDX_TRY(do_compact(c, 0, nullptr, true));
+        BDX_TRY(do_cut(c, 0, 0, 0, true));
         if (!c->na_alloc) return BDX_OK;
         // the region table is final after K3: the host takes its copy while the device joins the mates
         Entries en{};
@@ -1805,11 +1687,9 @@ int bdx_run(bdx_ctx* c) {
                 en.counts = c->b_counts.as<StageCounts>(); en.nkeys2 = 2 * c->nkeys;
             }
         }
-        r = do_join_local(c, c->na_alloc, en, &c->b_p1.as<Pass1>()->n_anom, true);
-        if (r != BDX_OK) return r;
+        BDX_TRY(do_join_local(c, c->na_alloc, en, &c->b_p1.as<Pass1>()->n_anom, true));
         if (c->k3.host_copy_later && !c->poll) {  // the join kernel has forwarded the region table to pinned memory
-            r = signal_ready(c, 3, c->ev_regions);  // (polling: the next kernel, k6_pairs_kernel, sets the ready word itself)
-            if (r != BDX_OK) return r;
+            BDX_TRY(signal_ready(c, 3, c->ev_regions));  // (polling: the next kernel, k6_pairs_kernel, sets the ready word itself)
         }
         return do_k6(c, force_host);
     };
@@ -1836,41 +1716,30 @@ int bdx_run(bdx_ctx* c) {
     if (restored) {
         // restored pass-1 statistics (a cache written by an earlier run: ConfigLoader.cpp:19-23): the classifier still runs --
         // pass 2 needs its class bytes -- but window, densities, lambda and the printed counters come from the cache
-        rc = do_pass1(c);
-        if (rc != BDX_OK) return rc;
-        rc = set_pass1(c, c->ov_cnt.data(), c->ov_covered, window_from(c, c->ov_cnt.data(), c->ov_covered), true);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(do_pass1(c));
+        BDX_TRY(set_pass1(c, c->ov_cnt.data(), c->ov_covered, window_from(c, c->ov_cnt.data(), c->ov_covered), true));
         HIPCHK(c, hipMemcpyAsync(c->b_cnt.p, c->ov_cnt.data(), c->ov_cnt.size() * 4, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipMemcpyAsync(c->b_kdens.p, c->key_density.data(), c->key_density.size() * 4, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        rc = enqueue_middle();
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(enqueue_middle());
     } else if (guess) {
-        rc = do_pass1(c, guess, false, true);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(do_pass1(c, guess, false, true));
         c->na_alloc = guess;
-        rc = enqueue_middle();
-        if (rc != BDX_OK) return rc;
-        rc = wait_pass1(c);
-        if (rc != BDX_OK) return rc;
-        rc = set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(enqueue_middle());
+        BDX_TRY(wait_pass1(c));
+        BDX_TRY(set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false));
         if (c->p1.n_anom > guess) {  // more anomalous reads than guessed: the enqueued stages saw none; run them properly
             HIPCHK(c, hipStreamSynchronize(s));
             HIPCHK(c, hipMemcpy(&c->b_p1.as<Pass1>()->n_anom, &c->p1.n_anom, 4, hipMemcpyHostToDevice));
             HIPCHK(c, hipMemset(c->b_counts.p, 0, sizeof(StageCounts)));
             ++c->seq;  // fresh ready-words: the ones of the neutralised launches are already set
             c->na_alloc = c->p1.n_anom;
-            rc = enqueue_middle();
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(enqueue_middle());
         }
     } else {
-        rc = do_pass1(c);
-        if (rc != BDX_OK) return rc;
-        rc = set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false);
-        if (rc != BDX_OK) return rc;
-        rc = enqueue_middle();
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(do_pass1(c));
+        BDX_TRY(set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false));
+        BDX_TRY(enqueue_middle());
     }
     c->last_n = c->n;
     c->last_na = c->p1.n_anom;
@@ -1909,8 +1778,7 @@ int bdx_run(bdx_ctx* c) {
                                         // a walk of 20 k groups over 15 k regions was 46 us faster on its copy)
         if (c->counts.irregular) {  // a read name seen more than twice: the pair model does not hold (see bdx_walk_reads.cpp)
             t_h1 = std::chrono::steady_clock::now();
-            rc = replay_reads(c, ph);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(replay_reads(c, ph));
             const auto t_r = std::chrono::steady_clock::now();
             c->stage_ms[4] = ms_between(t_h0, t_h1); c->stage_ms[5] = ms_between(t_h1, t_r); c->stage_ms[7] = ms_between(t_begin, t_r);
             return BDX_OK;
@@ -1920,12 +1788,10 @@ int bdx_run(bdx_ctx* c) {
         c->last_big_groups = (int64_t)c->counts.n_groups + c->counts.n_groups_big;  // (the host's share: mostly such components)
     }
     t_h1 = std::chrono::steady_clock::now();
-    rc = host_walk(c, c->counts.last_maxq, na != 0);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(host_walk(c, c->counts.last_maxq, na != 0));
     const auto t_h2 = std::chrono::steady_clock::now();
     if (na) {
-        rc = do_k6_table(c);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(do_k6_table(c));
         rc = finish_table(c);
     } else {
         rc = finish_host_walk(c);
@@ -1933,8 +1799,7 @@ int bdx_run(bdx_ctx* c) {
     if (rc != BDX_OK) return rc;
     if (c->collect_support) {
         materialize(c);
-        rc = collect_support(c, ph);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(collect_support(c, ph));
     }
     const auto t_end = std::chrono::steady_clock::now();
     if (c->stage_timing) {
@@ -1983,8 +1848,7 @@ int bdx_stage_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, int
     if (c->stage < 2) return BDX_ESTATE;
     NOT_WHILE_SIZING(c);
     if (c->opts.min_len < 0) return fail(c, BDX_ELIMIT, "staged runs do not support a negative -s");
-    int rc = do_compact(c, nn_base, pk_base, false);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(do_compact(c, nn_base, pk_base, false));
     if (first_qlen) *first_qlen = 0;
     if (first_nn) *first_nn = 0;
     if (c->p1.n_anom) {  // the first anomalous read of this chromosome closes the previous chromosome's last candidate
@@ -2002,8 +1866,7 @@ int bdx_stage_regions(bdx_ctx* c, int has_next, int32_t next_qlen, uint32_t next
     if (!c) return BDX_EINVAL;
     if (c->stage < 2) return BDX_ESTATE;
     NOT_WHILE_SIZING(c);
-    int rc = do_cut(c, has_next, next_qlen, next_nn, false);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(do_cut(c, has_next, next_qlen, next_nn, false));
     return readback(c, false);
 }
 
@@ -2063,8 +1926,7 @@ int bdx_join_entries(bdx_ctx* c, size_t n, const uint64_t* key, const uint32_t* 
     Entries en{};
     en.key = c->b_x_key.as<uint64_t>(); en.region = c->b_x_region.as<int32_t>(); en.order = c->b_x_order.as<uint32_t>();
     en.meta = c->b_x_meta.as<uint32_t>(); en.isize = c->b_x_isize.as<int32_t>();
-    int rc = do_join_local(c, n32, en, c->b_x_n.as<uint32_t>(), false);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(do_join_local(c, n32, en, c->b_x_n.as<uint32_t>(), false));
     HIPCHK(c, hipMemcpyAsync(c->h_counts.p, c->b_counts.p, sizeof(StageCounts), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
@@ -2217,8 +2079,7 @@ int bdx_run_many(bdx_ctx* const* ctxs, size_t n, int in_flight) {
     const size_t workers = std::min<size_t>(n, (size_t)std::max(1, in_flight));
     if (workers <= 1) {
         for (size_t i = 0; i < n; ++i) {
-            const int rc = bdx_run(ctxs[i]);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(bdx_run(ctxs[i]));
         }
         return BDX_OK;
     }
@@ -2289,25 +2150,19 @@ int bdx_mark_duplicates(int device, const int32_t* tid, const int32_t* pos, cons
     KdScratch k;
     const void* src[7] = {tid, pos, mtid, mpos, flag, lib, name_key};
     const size_t esz[7] = {4, 4, 4, 4, 2, 1, 8};
-    int rc = BDX_OK;
-    for (int i = 0; i < 7 && rc == BDX_OK; ++i) {
-        if (col[i].ensure(n * esz[i]) != hipSuccess) rc = BDX_ENOMEM;
-        else if (hipMemcpy(col[i].p, src[i], n * esz[i], hipMemcpyHostToDevice) != hipSuccess) rc = BDX_EHIP;
+    for (int i = 0; i < 7; ++i) {
+        if (col[i].ensure(n * esz[i]) != hipSuccess) return BDX_ENOMEM;
+        if (hipMemcpy(col[i].p, src[i], n * esz[i], hipMemcpyHostToDevice) != hipSuccess) return BDX_EHIP;
     }
-    if (rc == BDX_OK && out.ensure(n) != hipSuccess) rc = BDX_ENOMEM;
-    if (rc == BDX_OK) {
-        KdParams p{};
-        p.tid = col[0].as<int32_t>(); p.pos = col[1].as<int32_t>(); p.mtid = col[2].as<int32_t>(); p.mpos = col[3].as<int32_t>();
-        p.flag = col[4].as<uint16_t>(); p.lib = col[5].as<uint8_t>(); p.key = col[6].as<uint64_t>(); p.n = n;
-        uint64_t marked = 0, groups = 0;
-        rc = kd_run(nullptr, p, k, nullptr, out.as<uint8_t>(), nullptr, &marked, &groups);
-        if (rc == BDX_OK && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(mask, out.p, n, hipMemcpyDeviceToHost) != hipSuccess)) rc = BDX_EHIP;
-        if (rc == BDX_OK && n_groups) *n_groups = groups;
-    }
-    for (DevBuf& b : col) b.release();
-    out.release();
-    k.release();
-    return rc;
+    if (out.ensure(n) != hipSuccess) return BDX_ENOMEM;
+    KdParams p{};
+    p.tid = col[0].as<int32_t>(); p.pos = col[1].as<int32_t>(); p.mtid = col[2].as<int32_t>(); p.mpos = col[3].as<int32_t>();
+    p.flag = col[4].as<uint16_t>(); p.lib = col[5].as<uint8_t>(); p.key = col[6].as<uint64_t>(); p.n = n;
+    uint64_t marked = 0, groups = 0;
+    BDX_TRY(kd_run(nullptr, p, k, nullptr, out.as<uint8_t>(), nullptr, &marked, &groups));
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(mask, out.p, n, hipMemcpyDeviceToHost) != hipSuccess) return BDX_EHIP;
+    if (n_groups) *n_groups = groups;
+    return BDX_OK;
 }
 
 int bdx_set_debug(bdx_ctx* c, const char* name, int value) {
@@ -2368,13 +2223,11 @@ int bdx_classify(const bdx_opts* opts, const bdx_lib* libs, int nlibs, const bdx
     for (int i = 0; i < nlibs; ++i) nbams = std::max(nbams, libs[i].bam_index + 1);
     for (size_t i = 0; i < b->n; ++i) nbams = std::max(nbams, (int)b->bam[i] + 1);
     bdx_ctx* c = nullptr;
-    int rc = bdx_create(&c, opts, libs, nlibs, nbams, 0, 100000000, device);
-    if (rc != BDX_OK) return rc;
-    rc = bdx_push(c, b);
-    if (rc == BDX_OK) rc = bdx_run(c);
-    if (rc == BDX_OK) rc = bdx_get_read_class(c, cls_out, b->n);
-    bdx_destroy(c);
-    return rc;
+    BDX_TRY(bdx_create(&c, opts, libs, nlibs, nbams, 0, 100000000, device));
+    std::unique_ptr<bdx_ctx, void (*)(bdx_ctx*)> owner(c, bdx_destroy);
+    BDX_TRY(bdx_push(c, b));
+    BDX_TRY(bdx_run(c));
+    return bdx_get_read_class(c, cls_out, b->n);
 }
 
 int bdx_count_junction_pairs(bdx_ctx* c, const int32_t* tid, const int32_t* pos_a, const int32_t* pos_b, size_t n, int by_library,
@@ -2474,17 +2327,13 @@ int bdx_poisson_log_upper_tail(const double* lambda, const int32_t* k, double* o
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
     DevBuf bl, bk, bo;
     if (bl.ensure(n * 8) != hipSuccess || bk.ensure(n * 4) != hipSuccess || bo.ensure(n * 8) != hipSuccess) return BDX_ENOMEM;
-    int rc = BDX_OK;
     if (hipMemcpy(bl.p, lambda, n * 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(bk.p, k, n * 4, hipMemcpyHostToDevice) != hipSuccess)
-        rc = BDX_EHIP;
-    if (rc == BDX_OK) {
-        launch_k5(bl.as<double>(), bk.as<int32_t>(), bo.as<double>(), (uint32_t)n, nullptr);
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) rc = BDX_EHIP;
-    }
-    if (rc == BDX_OK && hipMemcpy(out, bo.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = BDX_EHIP;
-    bl.release(); bk.release(); bo.release();
-    return rc;
+        return BDX_EHIP;
+    launch_k5(bl.as<double>(), bk.as<int32_t>(), bo.as<double>(), (uint32_t)n, nullptr);
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return BDX_EHIP;
+    if (hipMemcpy(out, bo.p, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return BDX_EHIP;
+    return BDX_OK;
 }
 
 }  // extern "C"

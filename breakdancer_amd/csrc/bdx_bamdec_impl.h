@@ -50,24 +50,26 @@ struct BamPiece {
     bool wrapped = false;        // starts at the ring's front although its predecessor does not end at the ring's end
     bool records_done = false;   // its record stage has been enqueued
     int slot = 0;
-    hipEvent_t ev_inflated = nullptr, ev_records = nullptr;
+    Event ev_inflated, ev_records;   // (from the decoder's pool, and back to it when the piece is forgotten)
 };
 
 }  // namespace
 
 struct bdx_bamdec {
+    // Order of release: members go in reverse order of declaration, so the streams are declared FIRST and destroyed LAST, behind every
+    // buffer and event that is used on them (bdx_bamdec_destroy joins the two threads and synchronises the streams before anything goes).
     int device = 0;
     bdx_ctx* sink = nullptr;
     std::string err;
-    hipStream_t s_copy = nullptr, s_rec = nullptr;   // (the inflate launches and the record stages take turns on s_rec: bdx_bamdec_create)
+    Stream s_copy, s_rec;   // (the inflate launches and the record stages take turns on s_rec: bdx_bamdec_create)
     // A decoder that feeds a context copies on the context's copy stream; with the context's compute and side streams and the decoder's
     // own that makes four streams in all.  The HIP runtime spreads a process's streams over four hardware queues, and two streams on one
-    // queue run in order -- with six, the completion of a 0.3 ms copy waited behind a 19 ms inflate launch.
-    bool borrowed_copy = false;   // (the sink's copy stream: not the decoder's to destroy)
+    // queue run in order -- with six, the completion of a 0.3 ms copy waited behind a 19 ms inflate launch.  (s_copy only borrows the
+    // sink's copy stream: it is not the decoder's to destroy.)
     // pinned staging: one piece's compressed bytes and the caller's member table
     struct Staging {
         PinBuf h_comp, h_tab;
-        hipEvent_t ev_copied = nullptr;   // H2D of this buffer done
+        Event ev_copied;                  // H2D of this buffer done
         bool busy = false;
         size_t cap = 0;                   // table entries
         std::atomic<int> pinned{1};       // 0: the pinning thread has not got to this buffer yet (bdx_bamdec_params::piece_bytes), 1: ready
@@ -84,8 +86,8 @@ struct bdx_bamdec {
     struct Slot {
         DevBuf d_comp, d_blocks, d_status;
         PinBuf h_blocks;                  // the device-format table, built as the pieces arrive
-        hipEvent_t ev_copied = nullptr;   // all of the batch's bytes and its table are in HBM
-        hipEvent_t ev_free = nullptr;     // the batch's record stage is through (its device buffers are reusable)
+        Event ev_copied;                  // all of the batch's bytes and its table are in HBM
+        Event ev_free;                    // the batch's record stage is through (its device buffers are reusable)
         bool busy = false, open = false;
         size_t bytes = 0, nblk = 0, cap_blk = 0;
         uint64_t ulen = 0;
@@ -97,7 +99,7 @@ struct bdx_bamdec {
     size_t ring_bytes = 0;        // usable bytes (the allocation has kBamMargin more)
     uint64_t cursor = 0;
     std::deque<BamPiece> pieces;  // submitted, oldest first; dropped once their record stage is enqueued and a successor exists
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<Event> ev_pool;
     uint64_t n_pieces = 0;
     // where the feeding thread's time goes (bdx_bamdec_host_ms): [0] waiting for a staging buffer's copy, [1] pinning staging memory,
     // [2] waiting for a batch slot, [3] a slot's buffers, [4] the piece's copy calls, [5] a batch's launch, [6] a record stage's
@@ -106,7 +108,7 @@ struct bdx_bamdec {
     double host_ms[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // ([10] of [7]: sizing the later stages' buffers, [11] of [7]: classifier launches;
                                                                        //  [12] / [13]: the inflate kernel's own time by HIP events / its launches, bdx_bamdec_params::time_kernels)
     bool time_kernels = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> kz_events;   // (time_kernels) an event pair around every inflate launch, read by bdx_bamdec_finish
+    std::vector<std::pair<Event, Event>> kz_events;   // (time_kernels) an event pair around every inflate launch, read by bdx_bamdec_finish
     std::chrono::steady_clock::time_point t_armed = std::chrono::steady_clock::now();
     bool finished = false, any_submitted = false;
     // record stage scratch (one piece at a time on s_rec)
@@ -132,7 +134,7 @@ struct bdx_bamdec {
     uint64_t confirmed_seq = 0;
     uint64_t bound_in_flight = 0; // upper bound of the records of pieces whose compaction is not confirmed yet
     std::deque<std::pair<uint64_t, uint64_t>> bounds;  // (sequence, bound)
-    std::deque<std::pair<uint64_t, hipEvent_t>> rec_events;  // (sequence, records-done event) for the sink's classifier
+    std::deque<std::pair<uint64_t, Event>> rec_events;  // (sequence, records-done event) for the sink's classifier
     float ms_inflate = 0;
     uint64_t inflated_bytes = 0, compressed_bytes = 0;
     size_t expected_bytes = 0;    // compressed bytes the caller announced (0: unknown)
@@ -157,10 +159,10 @@ int bfail(bdx_bamdec* d, int code, const std::string& msg) {
         if (_e != hipSuccess) return bfail(d, BDX_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
-hipEvent_t bam_event(bdx_bamdec* d) {
-    if (!d->ev_pool.empty()) { hipEvent_t e = d->ev_pool.back(); d->ev_pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
+Event bam_event(bdx_bamdec* d) {   // (empty if none can be created)
+    Event e;
+    if (!d->ev_pool.empty()) { e = std::move(d->ev_pool.back()); d->ev_pool.pop_back(); }
+    else (void)e.create(hipEventDisableTiming);
     return e;
 }
 
@@ -203,7 +205,7 @@ int bam_own_reserve(bdx_bamdec* d, size_t cap, uint64_t keep_records) {
         BHIP(d, nb.ensure(cap * c.esz));
         if (keep_records && c.b->p) BHIP(d, hipMemcpy(nb.p, c.b->p, keep_records * c.esz, hipMemcpyDeviceToDevice));
         c.b->release();
-        *c.b = nb;
+        *c.b = std::move(nb);
     }
     d->own_cap = cap;
     return BDX_OK;
@@ -226,10 +228,10 @@ int bam_feed_classifier(bdx_bamdec* d, bool final) {
     bdx_ctx* c = d->sink;
     if (!c) return BDX_OK;
     BamTimer t7(d->host_ms[7]);
-    hipEvent_t latest = nullptr;
+    Event latest;
     while (!d->rec_events.empty() && d->rec_events.front().first <= d->confirmed_seq) {
-        if (latest) d->ev_pool.push_back(latest);
-        latest = d->rec_events.front().second;
+        if (latest) d->ev_pool.push_back(std::move(latest));
+        latest = std::move(d->rec_events.front().second);
         d->rec_events.pop_front();
     }
     if (d->confirmed > c->n) {
@@ -267,7 +269,7 @@ int bam_feed_classifier(bdx_bamdec* d, bool final) {
     }
     if (latest) {
         const hipError_t e = hipStreamWaitEvent(c->stream, latest, 0);
-        d->ev_pool.push_back(latest);
+        d->ev_pool.push_back(std::move(latest));
         if (e != hipSuccess) return bfail(d, BDX_EHIP, "hipStreamWaitEvent");
     }
     if (c->k1_live) {
@@ -329,8 +331,7 @@ int bam_record_stage(bdx_bamdec* d, BamPiece& p, const BamPiece* next, int is_la
         if (need > d->own_cap) {
             BHIP(d, hipStreamSynchronize(s));
             bam_poll(d);
-            const int rc = bam_own_reserve(d, std::max<size_t>((size_t)need, d->own_cap + d->own_cap / 2), d->confirmed);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(bam_own_reserve(d, std::max<size_t>((size_t)need, d->own_cap + d->own_cap / 2), d->confirmed));
         }
     }
     uint64_t avail_end = p.ring_end;
@@ -371,10 +372,10 @@ int bam_record_stage(bdx_bamdec* d, BamPiece& p, const BamPiece* next, int is_la
     d->bounds.emplace_back(p.seq, bound);
     d->bound_in_flight += bound;
     if (d->sink) {
-        hipEvent_t e = bam_event(d);
+        Event e = bam_event(d);
         if (!e) return bfail(d, BDX_EHIP, "hipEventCreate");
         BHIP(d, hipEventRecord(e, s));
-        d->rec_events.emplace_back(p.seq, e);
+        d->rec_events.emplace_back(p.seq, std::move(e));
     }
     p.records_done = true;
     return BDX_OK;
@@ -397,7 +398,7 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
     d->bam_index = (uint8_t)p->bam_index;
     d->filt.only_tid = p->only_tid; d->filt.beg = p->region_beg; d->filt.end = p->region_end; d->filt.n_targets = p->n_targets;
     d->filt.keep_all = (p->record_mode & 1) ? 1 : 0; d->filt.mapq_only = (p->record_mode & 2) ? 1 : 0;
-    auto bad = [&](int code) { bdx_bamdec_destroy(d); return code; };
+    std::unique_ptr<bdx_bamdec, void (*)(bdx_bamdec*)> owner(d, bdx_bamdec_destroy);   // (until the decoder is handed out: a failure below destroys it)
     static const bool create_trace = getenv("BDX_BAMDEC_TRACE") != nullptr;   // (where a decoder's set-up time goes, on stderr)
     const auto t_c0 = std::chrono::steady_clock::now();
     auto mark = [&](const char* what) {
@@ -414,18 +415,13 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
     // spreads a process's streams over four hardware queues, two streams on one queue run in order, and a copy's completion marker behind
     // a 30 ms inflate launch kept the feeder waiting for its staging buffers; the classifier, on the sink's stream, follows the record
     // stages through their events.
-    if (sink && sink->copy_stream) {
-        d->s_copy = sink->copy_stream;
-        d->borrowed_copy = true;
-    } else if (hipStreamCreateWithFlags(&d->s_copy, hipStreamNonBlocking) != hipSuccess) {
-        return bad(BDX_EHIP);
-    }
-    if (hipStreamCreateWithFlags(&d->s_rec, hipStreamNonBlocking) != hipSuccess) return bad(BDX_EHIP);
+    if (sink && sink->copy_stream) d->s_copy.borrow(sink->copy_stream);
+    else if (d->s_copy.create(hipStreamNonBlocking) != hipSuccess) return BDX_EHIP;
+    if (d->s_rec.create(hipStreamNonBlocking) != hipSuccess) return BDX_EHIP;
     for (auto& sl : d->slot)
-        if (hipEventCreateWithFlags(&sl.ev_copied, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&sl.ev_free, hipEventDisableTiming) != hipSuccess)
-            return bad(BDX_EHIP);
+        if (sl.ev_copied.create(hipEventDisableTiming) != hipSuccess || sl.ev_free.create(hipEventDisableTiming) != hipSuccess) return BDX_EHIP;
     for (auto& st : d->staging)
-        if (hipEventCreateWithFlags(&st.ev_copied, hipEventDisableTiming) != hipSuccess) return bad(BDX_EHIP);
+        if (st.ev_copied.create(hipEventDisableTiming) != hipSuccess) return BDX_EHIP;
     mark("streams and events");
     d->expected_bytes = p->expected_bytes;
     d->time_kernels = p->time_kernels != 0;
@@ -461,12 +457,12 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
         off[n] = (uint32_t)chars.size();
         if (d->d_rg_hash.ensure(std::max<size_t>(n, 1) * 8) != hipSuccess || d->d_rg_off.ensure(((size_t)n + 1) * 4) != hipSuccess ||
             d->d_rg_chars.ensure(std::max<size_t>(chars.size(), 1)) != hipSuccess || d->d_rg_lib.ensure(std::max<size_t>(n, 1)) != hipSuccess)
-            return bad(BDX_ENOMEM);
+            return BDX_ENOMEM;
         if ((n && hipMemcpy(d->d_rg_hash.p, hash.data(), (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) ||
             hipMemcpy(d->d_rg_off.p, off.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
             (!chars.empty() && hipMemcpy(d->d_rg_chars.p, chars.data(), chars.size(), hipMemcpyHostToDevice) != hipSuccess) ||
             (n && hipMemcpy(d->d_rg_lib.p, p->rg_lib, n, hipMemcpyHostToDevice) != hipSuccess))
-            return bad(BDX_EHIP);
+            return BDX_EHIP;
         d->rg.hash = d->d_rg_hash.as<uint64_t>(); d->rg.off = d->d_rg_off.as<uint32_t>(); d->rg.chars = d->d_rg_chars.as<char>();
         d->rg.lib = d->d_rg_lib.as<uint8_t>(); d->rg.n = n; d->rg.fallback = p->fallback_lib;
         d->rg.missing = p->missing_lib_plus1 > 0 ? (uint8_t)(p->missing_lib_plus1 - 1) : p->fallback_lib;
@@ -475,16 +471,16 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
     // ring of inflated bytes
     d->ring_bytes = p->ring_bytes ? p->ring_bytes : ((size_t)3 << 30);
     if (d->ring_bytes < ((size_t)1 << 20)) d->ring_bytes = (size_t)1 << 20;
-    if (d->d_ring.ensure(d->ring_bytes + kBamMargin + 64) != hipSuccess) return bad(BDX_ENOMEM);
+    if (d->d_ring.ensure(d->ring_bytes + kBamMargin + 64) != hipSuccess) return BDX_ENOMEM;
     d->ring_bytes = d->d_ring.bytes - kBamMargin - 64;
-    if (d->d_state.ensure(sizeof(PieceState)) != hipSuccess) return bad(BDX_ENOMEM);
+    if (d->d_state.ensure(sizeof(PieceState)) != hipSuccess) return BDX_ENOMEM;
     PieceState st{};
     st.next_start = p->first_record_offset;
-    if (hipMemcpy(d->d_state.p, &st, sizeof(st), hipMemcpyHostToDevice) != hipSuccess) return bad(BDX_EHIP);
-    if (d->h_progress.ensure(64) != hipSuccess) return bad(BDX_ENOMEM);
+    if (hipMemcpy(d->d_state.p, &st, sizeof(st), hipMemcpyHostToDevice) != hipSuccess) return BDX_EHIP;
+    if (d->h_progress.ensure(64) != hipSuccess) return BDX_ENOMEM;
     memset(d->h_progress.p, 0, 64);
     mark("ring and state");
-    if (sink && sink->adopted) return bad(BDX_ESTATE);   // (before the pinning threads start: a decoder that fails from here on is destroyed at once)
+    if (sink && sink->adopted) return BDX_ESTATE;   // (before the pinning threads start: a decoder that fails from here on is destroyed at once)
     // (behind the decoder's own pinned allocation: page pinning does not run in parallel with itself)
     if (p->piece_bytes && p->piece_blocks) {
         for (auto& st : d->staging) st.pinned.store(0);
@@ -529,14 +525,14 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
         });
     }
     if (sink) {
-        if (sink->adopted) return bad(BDX_ESTATE);
-        if (sink->n && sink->mark_dup && sink->dup_done) return bad(BDX_ESTATE);   // (a load whose duplicates are marked takes no more reads)
+        if (sink->adopted) return BDX_ESTATE;
+        if (sink->n && sink->mark_dup && sink->dup_done) return BDX_ESTATE;   // (a load whose duplicates are marked takes no more reads)
         if (sink->n == 0 && p->expected_bytes) {   // (a record takes 50-150 bytes of BAM; a store that is too small grows)
             // ... plus room for what the batches in flight could hold at most (36 bytes is the smallest record): the store must be able to
             // take them before their record counts are known, and growing it means waiting for the device and copying the columns
             const size_t in_flight = (size_t)kBamSlots * (d->batch_blocks + d->batch_blocks / 4 + 64) * 65536 / 36;
             const size_t want = std::min<size_t>(p->expected_bytes / 48 + ((size_t)1 << 20) + std::min<size_t>(in_flight, p->expected_bytes * 4), 0xFFFFFFFFull - 1024);
-            if (sink->cap < want && alloc_reads(sink, want) != BDX_OK) return bad(BDX_ENOMEM);
+            if (sink->cap < want && alloc_reads(sink, want) != BDX_OK) return BDX_ENOMEM;
             mark("sink store");
         }
         if (sink->n == 0) sink->dup_done = false;
@@ -544,7 +540,7 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
             sink->key_segs.clear();
             const uint64_t tiles = (sink->cap + kTile - 1) / kTile;
             if (tiles <= 0xFFFFFFFFull) {
-                if (pass1_prepare(sink, (uint32_t)tiles) != BDX_OK) return bad(BDX_EHIP);
+                if (pass1_prepare(sink, (uint32_t)tiles) != BDX_OK) return BDX_EHIP;
                 sink->k1_live = !sink->mark_dup;   // (duplicates are marked over the whole store before K1 reads a flag)
             }
         }
@@ -554,15 +550,15 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
         d->records_at_arm = sink->n;
         // (records this decoder appends come behind what the store already holds)
         st.n_kept = sink->n;
-        if (hipMemcpy(d->d_state.p, &st, sizeof(st), hipMemcpyHostToDevice) != hipSuccess) return bad(BDX_EHIP);
+        if (hipMemcpy(d->d_state.p, &st, sizeof(st), hipMemcpyHostToDevice) != hipSuccess) return BDX_EHIP;
     }
     if (!sink && p->expected_bytes) {   // (the decoder's own columns, sized like a sink's store: growing them waits for the device and copies)
         const size_t in_flight = (size_t)kBamSlots * (d->batch_blocks + d->batch_blocks / 4 + 64) * 65536 / 36;
         const size_t want = std::min<size_t>(p->expected_bytes / 48 + ((size_t)1 << 20) + std::min<size_t>(in_flight, p->expected_bytes * 4), 0xFFFFFFFFull - 1024);
-        if (bam_own_reserve(d, want, 0) != BDX_OK) return bad(BDX_ENOMEM);
+        if (bam_own_reserve(d, want, 0) != BDX_OK) return BDX_ENOMEM;
     }
     mark("done");
-    *out = d;
+    *out = owner.release();
     return BDX_OK;
 }
 
@@ -571,32 +567,8 @@ void bdx_bamdec_destroy(bdx_bamdec* d) {
     (void)hipSetDevice(d->device);
     if (d->presize_thread.joinable()) d->presize_thread.join();
     if (d->pin_thread.joinable()) d->pin_thread.join();   // (before anything is released: the thread may still be pinning staging buffers)
-    for (hipStream_t s : {d->s_copy, d->s_rec})
+    for (hipStream_t s : {(hipStream_t)d->s_copy, (hipStream_t)d->s_rec})
         if (s) (void)hipStreamSynchronize(s);
-    for (auto& sl : d->slot) {
-        sl.h_blocks.release(); sl.d_comp.release(); sl.d_blocks.release(); sl.d_status.release();
-        if (sl.ev_copied) (void)hipEventDestroy(sl.ev_copied);
-        if (sl.ev_free) (void)hipEventDestroy(sl.ev_free);
-    }
-    for (auto& st : d->staging) {
-        st.h_comp.release(); st.h_tab.release();
-        if (st.ev_copied) (void)hipEventDestroy(st.ev_copied);
-    }
-    for (auto& p : d->pieces) {
-        if (p.ev_inflated) (void)hipEventDestroy(p.ev_inflated);
-        if (p.ev_records) (void)hipEventDestroy(p.ev_records);
-    }
-    for (auto& e : d->rec_events) (void)hipEventDestroy(e.second);
-    for (hipEvent_t e : d->ev_pool) (void)hipEventDestroy(e);
-    for (auto& pr : d->kz_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    for (DevBuf* b : {&d->d_ring, &d->d_cb, &d->d_offs, &d->d_base, &d->d_scan, &d->d_state, &d->r_tid, &d->r_pos, &d->r_mtid, &d->r_mpos, &d->r_isize,
-                      &d->r_flag, &d->r_qlen, &d->r_mapq, &d->r_lib, &d->r_keep, &d->r_key, &d->r_check, &d->o_check, &d->d_ex_first, &d->d_ex_beg, &d->d_ex_end, &d->d_rg_hash, &d->d_rg_off, &d->d_rg_chars, &d->d_rg_lib,
-                      &d->o_tid, &d->o_pos, &d->o_mtid, &d->o_mpos, &d->o_isize, &d->o_flag, &d->o_qlen, &d->o_mapq, &d->o_lib, &d->o_bam, &d->o_key})
-        b->release();
-    d->h_progress.release();
-    if (d->borrowed_copy) d->s_copy = nullptr;
-    for (hipStream_t s : {d->s_copy, d->s_rec})
-        if (s) (void)hipStreamDestroy(s);
     delete d;
 }
 
@@ -672,10 +644,10 @@ int bam_launch_batch(bdx_bamdec* d, int si, bool last) {
     if (nblocks) BHIP(d, hipMemcpyAsync(sl.d_blocks.p, tb, nblocks * sizeof(BgzfBlock), hipMemcpyHostToDevice, d->s_copy));
     BHIP(d, hipEventRecord(sl.ev_copied, d->s_copy));
     BHIP(d, hipStreamWaitEvent(d->s_rec, sl.ev_copied, 0));
-    hipEvent_t kz0 = nullptr, kz1 = nullptr;
-    if (d->time_kernels && hipEventCreate(&kz0) == hipSuccess && hipEventCreate(&kz1) == hipSuccess) (void)hipEventRecord(kz0, d->s_rec);
+    Event kz0, kz1;
+    if (d->time_kernels && kz0.create() == hipSuccess && kz1.create() == hipSuccess) (void)hipEventRecord(kz0, d->s_rec);
     launch_kz_inflate(sl.d_comp.as<uint8_t>(), sl.d_blocks.as<BgzfBlock>(), (uint32_t)nblocks, d->d_ring.as<uint8_t>(), sl.d_status.as<uint32_t>(), d->s_rec);
-    if (kz0 && kz1) { (void)hipEventRecord(kz1, d->s_rec); d->kz_events.emplace_back(kz0, kz1); }
+    if (kz0 && kz1) { (void)hipEventRecord(kz1, d->s_rec); d->kz_events.emplace_back(std::move(kz0), std::move(kz1)); }
     p.ev_inflated = bam_event(d);
     if (!p.ev_inflated) return bfail(d, BDX_EHIP, "hipEventCreate");
     BHIP(d, hipEventRecord(p.ev_inflated, d->s_rec));
@@ -686,18 +658,16 @@ int bam_launch_batch(bdx_bamdec* d, int si, bool last) {
     while (d->batch_end_bytes.size() > 64) d->batch_end_bytes.pop_front();
     if (d->host_ms[8] == 0) d->host_ms[8] = ms_between(d->t_armed, std::chrono::steady_clock::now());
     d->inflated_bytes += ulen;
-    d->pieces.push_back(p);
+    d->pieces.push_back(std::move(p));
     d->cur_slot = (si + 1) % kBamSlots;
     if (d->pieces.size() >= 2) {
         BamPiece& prev = d->pieces[d->pieces.size() - 2];
         if (!prev.records_done) {
-            const int rc = bam_record_stage(d, prev, &d->pieces.back(), 0);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(bam_record_stage(d, prev, &d->pieces.back(), 0));
         }
     }
     if (last) {
-        const int rc = bam_record_stage(d, d->pieces.back(), nullptr, 1);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(bam_record_stage(d, d->pieces.back(), nullptr, 1));
         d->finished = true;
     }
     // forget batches whose ring bytes nobody can need any more: all but the last few
@@ -705,8 +675,8 @@ int bam_launch_batch(bdx_bamdec* d, int si, bool last) {
         BamPiece& f = d->pieces.front();
         // (a later batch that lands on its bytes waits for ev_records; once the event has completed that wait is void)
         if (hipEventQuery(f.ev_records) != hipSuccess) break;
-        d->ev_pool.push_back(f.ev_inflated);
-        d->ev_pool.push_back(f.ev_records);
+        d->ev_pool.push_back(std::move(f.ev_inflated));
+        d->ev_pool.push_back(std::move(f.ev_records));
         d->pieces.pop_front();
     }
     return BDX_OK;
@@ -782,8 +752,7 @@ int bdx_bamdec_submit(bdx_bamdec* d, size_t bytes, size_t nblocks, int last) {
     const size_t goal_blocks = std::min(d->batch_blocks, started == 0 ? std::max<size_t>(rb / 8, 1) : started == 1 ? std::max<size_t>(rb / 3, 1) : started == 2 ? std::max<size_t>(2 * rb / 3, 1) :
                                                          started == 3 ? rb : started == 4 ? 2 * rb : 4 * rb);
     if (last || sl.nblk >= goal_blocks || sl.bytes >= d->batch_bytes) {
-        rc = bam_launch_batch(d, d->cur_slot, last != 0);
-        if (rc != BDX_OK) return rc;
+        BDX_TRY(bam_launch_batch(d, d->cur_slot, last != 0));
     }
     bam_poll(d);
     return bam_feed_classifier(d, false);
@@ -806,12 +775,10 @@ int bdx_bamdec_finish(bdx_bamdec* d, uint64_t* n_records) {
     if (!d->finished) {
         // the caller stops early (a region read through the index): what has been submitted is decoded as far as its bytes go
         if (d->slot[d->cur_slot].open && d->slot[d->cur_slot].nblk) {
-            const int rc = bam_launch_batch(d, d->cur_slot, false);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(bam_launch_batch(d, d->cur_slot, false));
         }
         if (!d->pieces.empty() && !d->pieces.back().records_done) {
-            const int rc = bam_record_stage(d, d->pieces.back(), nullptr, 2);
-            if (rc != BDX_OK) return rc;
+            BDX_TRY(bam_record_stage(d, d->pieces.back(), nullptr, 2));
         }
         d->finished = true;
         d->held_staging = 0;   // (pieces acquired ahead and never submitted -- a caller that stopped early -- are dropped)
@@ -854,7 +821,6 @@ int bdx_bamdec_finish(bdx_bamdec* d, uint64_t* n_records) {
     for (auto& pr : d->kz_events) {   // (everything has been waited for above)
         float ms = 0;
         if (hipEventSynchronize(pr.second) == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) { d->host_ms[12] += ms; d->host_ms[13] += 1; }
-        (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
     }
     d->kz_events.clear();
     return BDX_OK;
@@ -868,7 +834,7 @@ int bdx_bamdec_rearm(bdx_bamdec* d, int32_t only_tid, int32_t region_beg, int32_
     if (!d) return BDX_EINVAL;
     if (!d->finished) return bfail(d, BDX_ESTATE, "bdx_bamdec_finish first");
     BHIP(d, hipSetDevice(d->device));
-    for (hipStream_t s : {d->s_copy, d->s_rec})
+    for (hipStream_t s : {(hipStream_t)d->s_copy, (hipStream_t)d->s_rec})
         if (s) BHIP(d, hipStreamSynchronize(s));
     d->filt.only_tid = only_tid; d->filt.beg = region_beg; d->filt.end = region_end;
     for (auto& st : d->staging) st.busy = false;
@@ -877,11 +843,11 @@ int bdx_bamdec_rearm(bdx_bamdec* d, int32_t only_tid, int32_t region_beg, int32_
     d->cur_slot = 0;
     d->cursor = 0;
     for (auto& p : d->pieces) {
-        if (p.ev_inflated) d->ev_pool.push_back(p.ev_inflated);
-        if (p.ev_records) d->ev_pool.push_back(p.ev_records);
+        if (p.ev_inflated) d->ev_pool.push_back(std::move(p.ev_inflated));
+        if (p.ev_records) d->ev_pool.push_back(std::move(p.ev_records));
     }
     d->pieces.clear();
-    for (auto& e : d->rec_events) d->ev_pool.push_back(e.second);
+    for (auto& e : d->rec_events) d->ev_pool.push_back(std::move(e.second));
     d->rec_events.clear();
     d->bounds.clear();
     d->bound_in_flight = 0;
@@ -977,29 +943,27 @@ int bdx_exclude_mask(int device, const int32_t* tid, const int32_t* pos, const i
     if (n && (!tid || !pos || !mtid || !mpos || !mask)) return BDX_EINVAL;
     std::vector<uint32_t> first;
     std::vector<int32_t> beg, end;
-    const int trc = exclude_table(iv, niv, first, beg, end);
-    if (trc != BDX_OK) return trc;
+    BDX_TRY(exclude_table(iv, niv, first, beg, end));
     if (n > 0xFFFFFFFFull) return BDX_ELIMIT;
     if (!n) return BDX_OK;
     if (beg.empty()) { memset(mask, 0, n); return BDX_OK; }
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
     DevBuf b_first, b_beg, b_end, b_cols, b_out;
-    auto done = [&](int code) { b_first.release(); b_beg.release(); b_end.release(); b_cols.release(); b_out.release(); return code; };
     if (b_first.ensure(first.size() * 4) != hipSuccess || b_beg.ensure(beg.size() * 4) != hipSuccess || b_end.ensure(end.size() * 4) != hipSuccess ||
         b_cols.ensure(n * 16) != hipSuccess || b_out.ensure(n) != hipSuccess)
-        return done(BDX_ENOMEM);
+        return BDX_ENOMEM;
     int32_t* c = b_cols.as<int32_t>();
     if (hipMemcpy(b_first.p, first.data(), first.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(b_beg.p, beg.data(), beg.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(b_end.p, end.data(), end.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c, tid, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c + n, pos, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c + 2 * n, mtid, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c + 3 * n, mpos, n * 4, hipMemcpyHostToDevice) != hipSuccess)
-        return done(BDX_EHIP);
+        return BDX_EHIP;
     const ExcludeMask m{b_first.as<uint32_t>(), b_beg.as<int32_t>(), b_end.as<int32_t>(), (int32_t)first.size() - 1};
     launch_kx_exclude(m, c, c + n, c + 2 * n, c + 3 * n, n, b_out.as<uint8_t>(), nullptr, nullptr);
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return done(BDX_EHIP);
-    if (hipMemcpy(mask, b_out.p, n, hipMemcpyDeviceToHost) != hipSuccess) return done(BDX_EHIP);
-    return done(BDX_OK);
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return BDX_EHIP;
+    if (hipMemcpy(mask, b_out.p, n, hipMemcpyDeviceToHost) != hipSuccess) return BDX_EHIP;
+    return BDX_OK;
 }
 
 int bdx_bamdec_stats(const bdx_bamdec* d, uint64_t* compressed_bytes, uint64_t* inflated_bytes, uint64_t* pieces, uint64_t* blocks_walked_twice) {
@@ -1037,10 +1001,8 @@ int gather_decoded(bdx_ctx* c, bdx_bamdec* const* decs, int k, const uint8_t* sr
     }
     if (n != total) return fail(c, BDX_EINVAL, "the merge order does not cover the decoders' records");
     if (!n) return BDX_OK;
-    const int rc = alloc_reads(c, (size_t)(base + n));   // (keeps what the store holds)
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(alloc_reads(c, (size_t)(base + n)));   // (keeps what the store holds)
     DevBuf d_file, d_index, d_err;
-    struct Release { DevBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } release{d_file, d_index, d_err};
     HIPCHK(c, d_file.ensure((size_t)n)); HIPCHK(c, d_index.ensure((size_t)n * 4)); HIPCHK(c, d_err.ensure(16));
     hipStream_t s = c->stream;
     hipError_t e = hipMemcpyAsync(d_file.p, src_file, (size_t)n, hipMemcpyHostToDevice, s);
@@ -1103,42 +1065,33 @@ int bdx_inflate_blocks(int device, const void* compressed, size_t bytes, const b
     }
     if (o > out_bytes) return BDX_EINVAL;
     DevBuf d_in, d_out, d_tb, d_st;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int rc = BDX_OK;
-    auto done = [&](int code) {
-        d_in.release(); d_out.release(); d_tb.release(); d_st.release();
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        return code;
-    };
+    DevBuf d_prof;   // BDX_KZ_PROF=<file>: the kernel's own clocks per member, for tools/bamdec_probe.py
+    Event e0, e1;
     if (d_in.ensure(bytes + 2048) != hipSuccess || d_out.ensure(o + 64) != hipSuccess || d_tb.ensure(std::max<size_t>(nblocks, 1) * sizeof(BgzfBlock)) != hipSuccess ||
         d_st.ensure(std::max<size_t>(nblocks, 1) * 4) != hipSuccess)
-        return done(BDX_ENOMEM);
+        return BDX_ENOMEM;
     if (hipMemset(d_in.p, 0, bytes + 2048) != hipSuccess || hipMemcpy(d_in.p, compressed, bytes, hipMemcpyHostToDevice) != hipSuccess ||
         (nblocks && hipMemcpy(d_tb.p, tb.data(), nblocks * sizeof(BgzfBlock), hipMemcpyHostToDevice) != hipSuccess))
-        return done(BDX_EHIP);
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return done(BDX_EHIP);
+        return BDX_EHIP;
+    if (e0.create() != hipSuccess || e1.create() != hipSuccess) return BDX_EHIP;
     (void)hipEventRecord(e0, nullptr);
-    // BDX_KZ_PROF=<file>: the kernel's own clocks per member, for tools/bamdec_probe.py
-    DevBuf d_prof;
     static const char* const prof_env = getenv("BDX_KZ_PROF");   // (tracing: read once per process)
     const char* prof_path = prof_env;
     if (prof_path && nblocks && (d_prof.ensure(nblocks * 64) != hipSuccess || hipMemset(d_prof.p, 0, nblocks * 64) != hipSuccess)) prof_path = nullptr;
     launch_kz_inflate(d_in.as<uint8_t>(), d_tb.as<BgzfBlock>(), (uint32_t)nblocks, d_out.as<uint8_t>(), d_st.as<uint32_t>(), nullptr,
                           prof_path ? d_prof.as<unsigned long long>() : nullptr);
     (void)hipEventRecord(e1, nullptr);
-    if (hipDeviceSynchronize() != hipSuccess) return done(BDX_EHIP);
+    if (hipDeviceSynchronize() != hipSuccess) return BDX_EHIP;
     if (kernel_ms) (void)hipEventElapsedTime(kernel_ms, e0, e1);
     if (prof_path && nblocks) {
         std::vector<unsigned long long> hp(nblocks * 8);
         if (hipMemcpy(hp.data(), d_prof.p, nblocks * 64, hipMemcpyDeviceToHost) == hipSuccess)
             if (FILE* f = fopen(prof_path, "wb")) { fwrite(hp.data(), 8, hp.size(), f); fclose(f); }
     }
-    d_prof.release();
     if ((o && hipMemcpy(out, d_out.p, o, hipMemcpyDeviceToHost) != hipSuccess) ||
         (nblocks && hipMemcpy(status, d_st.p, nblocks * 4, hipMemcpyDeviceToHost) != hipSuccess))
-        return done(BDX_EHIP);
-    return done(rc);
+        return BDX_EHIP;
+    return BDX_OK;
 }
 
 }  // extern "C"

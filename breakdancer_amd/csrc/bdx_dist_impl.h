@@ -278,6 +278,8 @@ struct ThreadComm : Comm {
 }  // namespace
 
 struct bdx_dist {
+    // Order of release: bdx_dist_destroy destroys the two contexts first (the streams everything here runs on are theirs: each is
+    // synchronised as its context goes); the buffers and the event below go with the members, behind them and before `comm`'s turn.
     int device = 0, ntids = 0, nlibs = 0, nbams = 0, nkeys = 0, w0 = 0;
     bdx_opts opts{};
     std::vector<bdx_lib> libs;
@@ -292,7 +294,7 @@ struct bdx_dist {
     DevBuf b_words, b_tab, b_send, b_recv, b_pack, b_all, b_nsend, b_nrecv, b_ntab, b_nflag, b_foreign, b_rg_rec, b_rg_pk, b_x, b_merge, b_chk, b_bucket;
     PinBuf h_words;                  // staging of the all-reduces' words (pinned: the copies either side of a collective are asynchronous)
     PinBuf h_tab;                    // what the small kernels report: per-chromosome tables, counts, ready words
-    hipEvent_t ev_side = nullptr;    // the name census runs on the context's second stream, beside the joins
+    Event ev_side;                   // the name census runs on the context's second stream, beside the joins
     uint32_t seq = 0;
     std::string err;
     uint64_t ctx_sent = 0, ctx_received = 0, gathered_bytes = 0;
@@ -355,9 +357,9 @@ int dist_create_common(bdx_dist** out, const bdx_opts* opts, const bdx_lib* libs
     d->comm = std::move(comm);
     int rc = bdx_create(&d->reads, opts, libs, nlibs, nbams, ntids, w0, device);
     if (rc == BDX_OK && d->comm->rank == 0) rc = bdx_create(&d->util, opts, libs, nlibs, nbams, ntids, w0, device);
-    if (rc != BDX_OK) { if (d->reads) bdx_destroy(d->reads); delete d; return rc; }
+    if (rc == BDX_OK && d->ev_side.create(hipEventDisableTiming) != hipSuccess) rc = BDX_EHIP;
+    if (rc != BDX_OK) { bdx_dist_destroy(d); return rc; }
     d->reads->force_direct_join = true;
-    if (hipEventCreateWithFlags(&d->ev_side, hipEventDisableTiming) != hipSuccess) { bdx_dist_destroy(d); return BDX_EHIP; }
     *out = d;
     return BDX_OK;
 }
@@ -469,12 +471,6 @@ void bdx_dist_destroy(bdx_dist* d) {
     (void)hipSetDevice(d->device);
     if (d->reads) bdx_destroy(d->reads);
     if (d->util) bdx_destroy(d->util);
-    for (DevBuf* b : {&d->b_words, &d->b_tab, &d->b_send, &d->b_recv, &d->b_pack, &d->b_all, &d->b_nsend, &d->b_nrecv, &d->b_ntab, &d->b_nflag, &d->b_foreign,
-                      &d->b_rg_rec, &d->b_rg_pk, &d->b_x, &d->b_merge, &d->b_chk, &d->b_bucket})
-        b->release();
-    d->h_tab.release();
-    d->h_words.release();
-    if (d->ev_side) (void)hipEventDestroy(d->ev_side);
     delete d;
 }
 
@@ -1057,8 +1053,7 @@ int DistRun::pass1_and_counts(std::vector<uint64_t>& v1) {
 // collective A, and what every rank derives from the sums: owners, prefixes, the window, what the one all-to-all will carry, the
 // limits that trip everywhere at once
 int DistRun::agree_statistics(std::vector<uint64_t>& v1, Stats* out) {
-    const int rc = exchange(kPhAllreduceStatistics, v1);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(exchange(kPhAllreduceStatistics, v1));
     Stats& A = *out;
     A.want_support = v1[W.flags];
     if (A.want_support != 0 && A.want_support != (uint64_t)world) return dfail(d, BDX_EINVAL, "bdx_dist_set_collect_support is set on some ranks only");
@@ -1178,8 +1173,7 @@ int DistRun::cut_regions(const Stats& A, std::vector<uint64_t>& v3) {
 
 // collective B, and what follows from it: genome-wide region ids, flush windows per rank
 int DistRun::agree_regions(const Stats& A, std::vector<uint64_t>& v3, Regions* out) {
-    const int rc = exchange(kPhAllreduceRegions, v3);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(exchange(kPhAllreduceRegions, v3));
     Regions& B = *out;
     B.rbase.assign(ntids + 1, 0);
     for (int t = 0; t < ntids; ++t) B.rbase[t + 1] = B.rbase[t] + v3[t];
@@ -1210,7 +1204,7 @@ int DistRun::seed_result(const Stats& A, const Regions& B) {
         U->replayed = false;
         U->sup_off.clear(); U->sup_idx.clear(); U->sup_flag.clear();
         U->collect_support = false;
-        if (!U->walk_scratch) U->walk_scratch = walk_scratch_new();
+        if (!U->walk_scratch) U->walk_scratch.reset(walk_scratch_new());
     }
     if (!B.NR && rank == 0) {
         U->regions.clear(); U->r_pk.clear(); U->reg = nullptr; U->nreg = 0; U->rpk = nullptr;
@@ -1405,8 +1399,7 @@ int DistRun::agree_packages(const Stats& A, const Regions& B, const TableCounts&
     std::vector<uint64_t> v5((size_t)world * TableCounts::kWords + 1, 0);
     if (st.rc == BDX_OK) mine.put(&v5[(size_t)rank * TableCounts::kWords]);
     v5[(size_t)world * TableCounts::kWords] = irregular;
-    const int rc = exchange(kPhAllreducePackages, v5);
-    if (rc != BDX_OK) return rc;
+    BDX_TRY(exchange(kPhAllreducePackages, v5));
     Summary& S = *out;
     for (int q = 0; q < world; ++q) S.of_rank.push_back(TableCounts::get(&v5[(size_t)q * TableCounts::kWords]));
     // some rank met a read name more than twice -- or the caller wants the reads behind every SV, which only the read-level walk knows

@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "../../include/bdx.h"
+#include "bdx_buf.h"
 
 namespace {
 
@@ -67,24 +68,16 @@ extern "C" int bdx_insert_size_stats(int device, const double* x, const uint32_t
     if (!x || !offsets || !out || nlibs < 1) return BDX_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
     const size_t n = offsets[nlibs];
-    double* dx = nullptr;
-    uint32_t* doff = nullptr;
-    bdx_insert_stats* dout = nullptr;
-    int rc = BDX_OK;
-    if (hipMalloc(&dx, std::max<size_t>(n, 1) * 8) != hipSuccess || hipMalloc(&doff, ((size_t)nlibs + 1) * 4) != hipSuccess ||
-        hipMalloc(&dout, (size_t)nlibs * sizeof(bdx_insert_stats)) != hipSuccess)
-        rc = BDX_ENOMEM;
-    if (rc == BDX_OK && ((n && hipMemcpy(dx, x, n * 8, hipMemcpyHostToDevice) != hipSuccess) ||
-                         hipMemcpy(doff, offsets, ((size_t)nlibs + 1) * 4, hipMemcpyHostToDevice) != hipSuccess))
-        rc = BDX_EHIP;
-    if (rc == BDX_OK) {
-        hipLaunchKernelGGL(kc_insert_stats_kernel, dim3((nlibs + 63) / 64), dim3(64), 0, nullptr, dx, doff, nlibs, dout);
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess ||
-            hipMemcpy(out, dout, (size_t)nlibs * sizeof(bdx_insert_stats), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = BDX_EHIP;
-    }
-    if (dx) (void)hipFree(dx);
-    if (doff) (void)hipFree(doff);
-    if (dout) (void)hipFree(dout);
-    return rc;
+    bdx::DevBuf dx, doff, dout;
+    if (dx.ensure(std::max<size_t>(n, 1) * 8) != hipSuccess || doff.ensure(((size_t)nlibs + 1) * 4) != hipSuccess ||
+        dout.ensure((size_t)nlibs * sizeof(bdx_insert_stats)) != hipSuccess)
+        return BDX_ENOMEM;
+    if ((n && hipMemcpy(dx.p, x, n * 8, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(doff.p, offsets, ((size_t)nlibs + 1) * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return BDX_EHIP;
+    hipLaunchKernelGGL(kc_insert_stats_kernel, dim3((nlibs + 63) / 64), dim3(64), 0, nullptr, dx.as<double>(), doff.as<uint32_t>(), nlibs, dout.as<bdx_insert_stats>());
+    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess ||
+        hipMemcpy(out, dout.p, (size_t)nlibs * sizeof(bdx_insert_stats), hipMemcpyDeviceToHost) != hipSuccess)
+        return BDX_EHIP;
+    return BDX_OK;
 }

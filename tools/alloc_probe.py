@@ -16,4 +16,4 @@ with tempfile.TemporaryDirectory(prefix="bdx_cli_") as td:
         print("== %s: wall %.3f s, rc %d" % (label, dt, p.returncode))
         err = p.stderr.decode().strip().splitlines()
         big = []
-        print("\n".join([l for l in err if "[bdx alloc]" not in l] + big[:80]))
+        print("\n".join([l for l in err if "[bdx alloc]" not in l and "[bdx free]" not in l] + big[:80]))
