@@ -42,6 +42,19 @@ struct KdScratch {
     void release_long() { work.release(); wrun.release(); starts.release(); pre.release(); cbase.release(); table.release(); multi.release(); }
 };
 
+// The buffers of the stages behind pass 1 (K2 compaction, K3 region cut, K4 join, K6 up to the table), apart from the context so that the
+// functions which size them (size_compact .. size_k6) can be handed these and nothing else of a context.  One DevBuf / PinBuf per array.
+struct StageBufs {
+    DevBuf b_c_tid, b_c_pos, b_c_isize, b_c_meta, b_c_key, b_c_check, b_c_idx, b_c_nn, b_c_pk;
+    DevBuf b_cand, b_pre_q, b_pre_rev, b_pre_nonctx, b_c_first, b_c_maxq, b_c_rid, b_region_of, b_lb;
+    DevBuf b_bcnt, b_boff, b_bcur, b_e_key, b_e_idx, b_partner, b_t_key, b_t_idx, b_pair_lo;
+    DevBuf b_groups;                  // (sharded runs) the join's pair groups, where they stay in HBM instead of pinned host memory
+    DevBuf b_r_rec, b_r_pk, b_out_deg, b_parts, b_rs, b_slot, b_members, b_own, b_lib_stage, b_cn_stage, b_t_lambda, b_t_k, b_ws6;
+    DevBuf b_sv_src, b_dlists, b_ltail, b_ins, b_member_ids;
+    DevBuf b_sv_out, b_lib_index_out, b_lib_pairs_out, b_cn_key_out, b_cn_value_out, b_ltail_out, b_sv_key;   // the final table where it stays in HBM
+    PinBuf h_regs, h_pk, h_groups, h_counts0, h_counts2, h_sv_out, h_lib_index, h_lib_pairs, h_cn_key, h_cn_value, h_ltail_dev;
+};
+
 constexpr int kNumStages = 12;
 constexpr int kK1MaxGrid = 8192;  // measured best on MI355X (tools/k1_probe.hip; again at the end of round 2: 2048 74.6 us, 4096 70.9,
                                   // 8192 69.9, 12288 72.5, 16384 73.4): 256 CUs x 32 workgroups queued, 4 independent waves each
@@ -66,24 +79,15 @@ struct bdx_ctx {
     bool adopted = false;
     DevBuf b_tid, b_pos, b_mtid, b_mpos, b_isize, b_flag, b_qlen, b_mapq, b_lib, b_bam, b_key, b_check;
     bool groups_in_hbm = false;       // (sharded runs) the join's pair groups stay in HBM instead of pinned host memory
-    bool defer_walk = false;          // (sharded runs over several ranks) do_k6 part 2 stops behind the components; the device walk (part 3) is
-                                      // enqueued once the host's share has left for rank 0, and runs beside the collectives and rank 0's walk
-    DevBuf b_groups;
     bool use_check = false;           // bdx_use_name_check: every batch carries a second hash of the read name, mates must agree in it too
 
     // stage buffers
-    DevBuf b_libs, b_cls, b_tile_tot, b_tile_pre, b_tile_mono, b_blk_cnt, b_cnt, b_p1, b_fold, b_stash, b_chunk_tot;
-    DevBuf b_c_tid, b_c_pos, b_c_isize, b_c_meta, b_c_key, b_c_check, b_c_idx, b_c_nn, b_c_pk;
-    DevBuf b_cand, b_pre_q, b_pre_rev, b_pre_nonctx, b_c_first, b_c_maxq, b_c_rid, b_region_of, b_counts;
-    DevBuf b_bcnt, b_boff, b_bcur, b_e_key, b_e_idx, b_partner, b_t_key, b_t_idx;
+    DevBuf b_libs, b_cls, b_tile_tot, b_tile_pre, b_tile_mono, b_blk_cnt, b_cnt, b_p1, b_fold, b_stash, b_chunk_tot, b_counts;
     DevBuf b_x_key, b_x_check, b_x_order, b_x_region, b_x_meta, b_x_isize, b_x_n;
-    DevBuf b_lib_mean;
-    DevBuf b_r_rec, b_r_pk, b_out_deg, b_parts, b_kdens, b_rs, b_slot, b_members, b_own, b_lib_stage, b_cn_stage,
-        b_t_lambda, b_t_k, b_ws6;
-    PinBuf h_p1, h_cnt, h_counts, h_regs, h_pk, h_groups, h_terms;
-    DevBuf b_sv_src, b_dlists, b_ltail, b_pair_lo;
+    DevBuf b_lib_mean, b_kdens;
+    PinBuf h_p1, h_cnt, h_counts, h_terms;
     PinBuf h_hs_rec, h_hs_aux, h_hs_lists, h_printed;
-    DevBuf b_ins, b_member_ids;
+    StageBufs sb;                     // K2 .. K6: what a sizing pass grows
     PinBuf h_flags;                   // [0] pass 1 ready, [1] host's groups ready, [2] final table ready, [3] region table ready (= run sequence number)
     uint32_t seq = 0;
     // test / measurement switches (bdx_set_debug): all off by default
@@ -96,10 +100,9 @@ struct bdx_ctx {
     bool materialized = true;         // c->walk holds the final table (false: it still sits in the pinned buffers only)
     bool rows_packed = false;         // ... as SvWire rows (48 bytes: what a single-context run's table kernel writes over PCIe), not SvOut
     uint32_t n_sv_total = 0, n_groups_total = 0, n_terms_total = 0, n_cn_total = 0;
-    PinBuf h_counts0, h_counts2, h_sv_out, h_lib_index, h_lib_pairs, h_cn_key, h_cn_value, h_ltail_dev;
     Event ev_groups, ev_regions;
     int big_walk_mode = -1;           // BDX_BIG_WALK=1 / 0: components of 5..64 regions always / never walked on the device; default: when
-                                      // the host's share is large enough to matter (see do_k6)
+                                      // the host's share is large enough to matter (StageDims::walks_big)
     int64_t last_big_groups = -1;     // groups of such components in the previous run of this context (device + host share)
     FinalizeParams fp_deferred{};     // second level of the pass-1 finalisation, to be run by K2's launch (enqueue-ahead runs)
     bool finalize2_deferred = false;
@@ -114,9 +117,7 @@ struct bdx_ctx {
     const RegionRec* k6_r_rec = nullptr;   // the region table laid out by genome-wide id (this rank's regions, n == 0 elsewhere)
     const uint32_t* k6_r_pk = nullptr;
     uint8_t* k6_taint = nullptr;
-    const uint32_t* k3_tid_tail = nullptr;
     bool table_in_hbm = false;        // the final table stays in HBM (with its order keys): rank 0 merges the ranks' tables
-    DevBuf b_sv_out, b_lib_index_out, b_lib_pairs_out, b_cn_key_out, b_cn_value_out, b_ltail_out, b_sv_key;
 
     // results
     bool ran = false;
@@ -138,10 +139,10 @@ struct bdx_ctx {
     uint32_t ov_covered = 0;
     bool replayed = false;            // the last run went through the read-level host replay (a read name seen more than twice)
     bool use_stash = false;           // K1 leaves ready-made records of the anomalous reads for K2 (at most kStashKeys counter keys)
-    // Sizing passes (bdx_reserve, the BAM decoder's sizing thread): the stage functions called with a `Sizing` only grow the buffers of the
-    // stages behind pass 1 -- they read the context's configuration and touch those buffers, nothing of its run state (no flag on the
-    // context says "sizing": round 5's did, and a run beside the sizing thread saw it and launched nothing).  While one is in flight the
-    // entry points that launch those stages refuse with BDX_ESTATE; its error text goes to sizing_err (the feeding thread owns `err`).
+    // The sizing passes (bdx_reserve, the BAM decoder's sizing thread; presize_stages): the size functions of the stages behind pass 1 are
+    // handed `sb` and a description by value, not the context, so they cannot reach its run state (no flag on the context says "sizing":
+    // round 5's did, and a run beside the sizing thread saw it and launched nothing).  While one is in flight the entry points that
+    // launch those stages refuse with BDX_ESTATE; its error text goes to sizing_err (the feeding thread owns `err`).
     std::atomic<int> sizing{0};
     std::string sizing_err;
     std::vector<uint32_t> sup_off;    // [n_svs + 1]
@@ -190,7 +191,7 @@ struct bdx_ctx {
     // keys was copied into the resident column
     struct KeySeg { uint64_t begin; const uint64_t* host; const uint16_t* host_qlen; const uint64_t* host_check; };
     std::vector<KeySeg> key_segs;
-    DevBuf b_seg, b_lb;
+    DevBuf b_seg;
 
     // ---- bdx_count_junction_pairs ----
     size_t cls_n = (size_t)-1;        // reads the class bytes in b_cls describe (set by a completed pass 1; -1: none)
@@ -206,14 +207,10 @@ struct bdx_ctx {
 
 namespace {
 
-thread_local std::string* t_err_sink = nullptr;   // a sizing pass on a thread of its own: its messages do not go to the context's `err`
 int fail(bdx_ctx* c, int code, const std::string& msg) {
-    if (t_err_sink) *t_err_sink = msg;
-    else if (c) c->err = msg;
+    if (c) c->err = msg;
     return code;
 }
-// what a sizing pass hands the stage functions instead of the context's run state
-struct Sizing { uint32_t na; };
 // entry points that launch the stages behind pass 1: not while their buffers are being sized on another thread
 #define NOT_WHILE_SIZING(c)                                                                                                              \
     do {                                                                                                                                 \
@@ -243,8 +240,8 @@ size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
 // from zero again.
 hipError_t next_lb_stamp(bdx_ctx* c, uint32_t* out) {
     if (((++c->lb_seq) & 0x3FFFFFFFu) == 0) {
-        if (c->b_lb.p) { const hipError_t e = hipMemsetAsync(c->b_lb.p, 0, c->b_lb.bytes, c->stream); if (e != hipSuccess) return e; }
-        if (c->b_ws6.p) { const hipError_t e = hipMemsetAsync(c->b_ws6.p, 0, c->b_ws6.bytes, c->stream); if (e != hipSuccess) return e; }
+        if (c->sb.b_lb.p) { const hipError_t e = hipMemsetAsync(c->sb.b_lb.p, 0, c->sb.b_lb.bytes, c->stream); if (e != hipSuccess) return e; }
+        if (c->sb.b_ws6.p) { const hipError_t e = hipMemsetAsync(c->sb.b_ws6.p, 0, c->sb.b_ws6.bytes, c->stream); if (e != hipSuccess) return e; }
         ++c->lb_seq;
     }
     *out = c->lb_seq & 0x3FFFFFFFu;
@@ -297,9 +294,48 @@ void stage_view(const bdx_ctx::Stage& st, bdx_batch_buf* out) {
     out->capacity = K;
 }
 
+// What decides the sizes of the buffers of the stages behind pass 1, by value.  The size functions (size_compact .. size_k6, in front of the
+// stages) get this, the buffers, the stream (two arrays are zeroed when they are allocated) and a place for an error text -- NOT a context:
+// a stage calls its size function at its head, and a sizing pass (presize_stages) calls all four, possibly on a thread beside the one
+// that feeds the context.
+enum class RegionDst { Host, HostAndHbm, Hbm };   // K3's region table: pinned host memory (staged runs); that and a copy in HBM for K6 (bdx_run);
+                                                  // HBM only (sharded runs: a chromosome's table is sent on from there, nobody reads it on this host)
+struct StageDims {
+    uint32_t na = 0;                  // anomalous reads the stages are sized for
+    int nkeys = 0, nlibs = 0;
+    bool use_check = false;
+    bool k2_clears_join = false;      // the context joins its own reads through the direct table: K2's launch presets it (table, partner[], pair_lo[])
+    RegionDst regions = RegionDst::HostAndHbm;
+    bool groups_in_hbm = false, table_in_hbm = false;
+    uint32_t k6_cap = 0;              // K6's per-region arrays hold at least this many regions (sharded runs: the genome's)
+    int big_walk = -1;                // components of 5..64 regions walked on the device: 1 / 0 (test switch, the previous run's groups), -1: the size decides
+    // the join: its entries; those with a partner[] / pair_lo[] word (the context's own reads); the direct table's slots (0: the bucketed
+    // join, which sizes its tables when it runs); whether pair_lo[] is wanted where K2 has not preset it
+    uint32_t join_n = 0, join_own = 0, join_slots = 0;
+    bool join_pair_lo = false;
+
+    uint32_t join_groups() const { return join_n / 2 + 1; }
+    uint32_t k6_regions() const { return std::max(na, k6_cap); }   // (sharded runs: K6's arrays are indexed by genome-wide region id)
+    // Components of 5..64 regions cost one more launch (k6_walk_big_kernel) and a member table of 256 B per label.  Few of
+    // them are walked by the host behind the device's own walk for free; many (dense data) make the host walk the longest
+    // stage.  Without a previous run to go by, the number of anomalous reads decides.
+    int walks_big() const { return big_walk >= 0 ? big_walk : (k6_regions() > 500000u ? 1 : 0); }
+};
+
+// ... of a context that takes `na` anomalous reads of its own through all four stages (bdx_run, the sizing passes)
+StageDims stage_dims(const bdx_ctx* c, uint32_t na) {
+    StageDims d;
+    d.na = na; d.nkeys = c->nkeys; d.nlibs = c->nlibs; d.use_check = c->use_check;
+    d.k2_clears_join = c->force_direct_join || (!c->bucketed_join && na <= kDirectJoinMax);
+    d.groups_in_hbm = c->groups_in_hbm; d.table_in_hbm = c->table_in_hbm; d.k6_cap = c->k6_cap;
+    d.big_walk = c->big_walk_mode >= 0 ? c->big_walk_mode : (c->last_big_groups >= 0 ? (c->last_big_groups > 2000 ? 1 : 0) : -1);
+    d.join_n = d.join_own = na; d.join_slots = d.k2_clears_join ? direct_join_slots(na) : 0;
+    return d;
+}
+
 int pass1_prepare(bdx_ctx* c, uint32_t tiles_cap);
-int presize_stages(bdx_ctx* c, uint32_t na);
-int presize_stages_here(bdx_ctx* c, uint32_t na);
+int presize_stages(bdx_ctx* c, const StageDims& dm);
+int presize_stages_here(bdx_ctx* c, const StageDims& dm);
 int pass1_classify(bdx_ctx* c, uint32_t upto, bool timed);
 
 constexpr uint32_t kStreamTilesMin = 4096;  // classify behind a batch only once this many new tiles (1 M reads) are complete
@@ -468,7 +504,7 @@ int bdx_reserve(bdx_ctx* c, size_t n_reads) {
     // caller still decodes or copies, not inside its first bdx_run.  Small inputs size theirs exactly, when they run.
     if (n_reads >= (1u << 20) && !c->ran) {
         const uint64_t prior = (uint64_t)n_reads / 32 + 4096;
-        if (prior <= kMaxAnomalous) return presize_stages_here(c, (uint32_t)prior);
+        if (prior <= kMaxAnomalous) return presize_stages_here(c, stage_dims(c, (uint32_t)prior));
     }
     return BDX_OK;
 }
@@ -918,32 +954,149 @@ int set_pass1(bdx_ctx* c, const uint32_t* cnt, uint32_t covered, int32_t window,
     return BDX_OK;
 }
 
+// ---- the size functions: every capacity expression of the later stages' buffers stands here, once ----
+#define SZCHK(expr)                                                                                       \
+    do {                                                                                                  \
+        const hipError_t _e = (expr);                                                                     \
+        if (_e != hipSuccess) { *err = std::string(#expr) + ": " + hipGetErrorString(_e); return BDX_EHIP; } \
+    } while (0)
+
+// arrays that two stages size (K2 clears what K3 and K4 fill; K3 and the sharded run use K6's scratch): one expression each
+hipError_t size_c_maxq(StageBufs& b, size_t cap) { return b.b_c_maxq.ensure(cap * 4); }
+hipError_t size_out_deg(StageBufs& b, size_t cap) { return b.b_out_deg.ensure(cap * 6 * 4); }
+hipError_t size_join_words(StageBufs& b, size_t n_own, bool pair_lo) {
+    const hipError_t e = b.b_partner.ensure(n_own * 4);
+    return e == hipSuccess && pair_lo ? b.b_pair_lo.ensure(n_own * 4) : e;
+}
+// look-back words of a scan (bdx_scan.h): they must start out zero once; afterwards every launch brings its own stamp (next_lb_stamp)
+hipError_t size_zero_once(DevBuf& b, size_t bytes, hipStream_t s) {
+    if (b.bytes >= bytes) return hipSuccess;
+    const hipError_t e = b.ensure(bytes);
+    return e == hipSuccess ? hipMemsetAsync(b.p, 0, b.bytes, s) : e;
+}
+
+int size_compact(StageBufs& b, const StageDims& d, std::string* err) {
+    if (!d.na) return BDX_OK;
+    if (d.na > kMaxAnomalous) { *err = "more than 2^31 anomalous reads in one context"; return BDX_ELIMIT; }
+    const size_t cap = d.na;
+    SZCHK(b.b_c_tid.ensure(cap * 4)); SZCHK(b.b_c_pos.ensure(cap * 4)); SZCHK(b.b_c_isize.ensure(cap * 4));
+    SZCHK(b.b_c_meta.ensure(cap * 4)); SZCHK(b.b_c_key.ensure(cap * 8)); SZCHK(b.b_c_nn.ensure(cap * 4));
+    SZCHK(b.b_c_idx.ensure(cap * 4));
+    if (d.use_check) SZCHK(b.b_c_check.ensure(cap * 8));
+    SZCHK(b.b_c_pk.ensure(cap * 4 * d.nkeys));
+    SZCHK(size_c_maxq(b, cap));
+    if (d.k2_clears_join) {
+        SZCHK(b.b_t_key.ensure((size_t)direct_join_slots(d.na) * 8));
+        SZCHK(size_join_words(b, cap, true));
+    }
+    return BDX_OK;
+}
+
+int size_cut(StageBufs& b, const StageDims& d, hipStream_t s, std::string* err) {
+    if (!d.na) return BDX_OK;
+    const size_t cap = d.na;
+    for (DevBuf* u : {&b.b_cand, &b.b_pre_q, &b.b_pre_rev, &b.b_pre_nonctx, &b.b_c_first, &b.b_c_rid, &b.b_region_of}) SZCHK(u->ensure(cap * 4));
+    SZCHK(size_c_maxq(b, cap));
+    // the region table and the group list are written by the kernels straight into pinned host memory: they are write-once,
+    // read-never on the device, so the PCIe writes overlap the kernels and no D2H copy is needed
+    // (HBM only: no pinned mirror -- pinning 24 chromosomes' tables cost a sharded run tens of milliseconds)
+    if (d.regions != RegionDst::Hbm) {
+        SZCHK(b.h_regs.ensure(cap * sizeof(RegionRec)));
+        SZCHK(b.h_pk.ensure(cap * 2 * d.nkeys * 4));
+    }
+    if (d.regions != RegionDst::Host) {
+        SZCHK(b.b_r_rec.ensure(cap * sizeof(RegionRec)));
+        SZCHK(b.b_r_pk.ensure(cap * 2 * d.nkeys * 4));
+    }
+    if (d.regions == RegionDst::HostAndHbm) {   // the device-side SV assembly follows
+        SZCHK(size_out_deg(b, cap));
+        SZCHK(b.h_counts0.ensure(sizeof(StageCounts)));
+    }
+    // the two scans' look-back words, for one element per thread (the finest split they use)
+    SZCHK(size_zero_once(b.b_lb, 5 * (scan_grid(d.na, 1) + 1) * 8, s));
+    return BDX_OK;
+}
+
+int size_join(StageBufs& b, const StageDims& d, std::string* err) {
+    if (!d.join_n) return BDX_OK;
+    if (d.groups_in_hbm) SZCHK(b.b_groups.ensure((size_t)d.join_groups() * sizeof(GroupRec)));   // sharded runs: the groups are packaged for rank 0 from HBM
+    else SZCHK(b.h_groups.ensure((size_t)d.join_groups() * sizeof(GroupRec)));
+    // (foreign entries of a sharded run have no partner[] / pair_lo[] entry: sized for the context's own reads, as K2 cleared them)
+    SZCHK(size_join_words(b, d.join_own, d.join_slots && d.join_pair_lo));
+    if (d.join_slots) SZCHK(b.b_t_key.ensure((size_t)d.join_slots * 8));
+    return BDX_OK;
+}
+
+// capacities of K6's lists for `na` regions: candidates and list entries <= reads / 2, each consuming a read pair
+struct K6Caps {
+    uint32_t sv, term, cn, lib_stride;
+    size_t p2, nsort;   // the inserted list (k6_insert_kernel): device order keys padded to a power of two for the sort; k6_ranksort_kernel's output (lists of that many entries at most)
+};
+K6Caps k6_caps(const StageDims& d) {
+    K6Caps k{};
+    const uint32_t na = d.k6_regions();
+    k.sv = na / 2 + 1; k.term = na / 2 + 1; k.cn = (na / 2 + 1) * (uint32_t)d.nkeys;
+    k.lib_stride = (uint32_t)std::min(d.nlibs, kK6LibStride);
+    k.p2 = 1;
+    while (k.p2 < k.sv) k.p2 <<= 1;
+    k.nsort = std::min<size_t>(k.sv, kK6RankSortMax);
+    return k;
+}
+
+int size_k6(StageBufs& b, const StageDims& d, hipStream_t s, std::string* err) {
+    const size_t cap = d.k6_regions();
+    if (!cap) return BDX_OK;
+    const K6Caps k = k6_caps(d);
+    SZCHK(size_out_deg(b, cap));
+    SZCHK(b.b_parts.ensure(cap * sizeof(PartRec)));
+    SZCHK(b.b_rs.ensure(cap * sizeof(RegSum)));
+    SZCHK(b.b_members.ensure(cap * kK6MaxMembers * sizeof(MemberInfo)));
+    SZCHK(b.b_own.ensure(cap * 7 * 4 + 64 * 4 * 4));
+    if (d.walks_big()) SZCHK(b.b_member_ids.ensure(cap * kK6BigMembers * 4));
+    SZCHK(b.b_slot.ensure(cap * sizeof(SvOut)));
+    SZCHK(b.b_lib_stage.ensure(cap * k.lib_stride * sizeof(LibStage)));
+    SZCHK(b.b_cn_stage.ensure(cap * (size_t)d.nkeys * sizeof(CnStage) + 16));
+    SZCHK(b.b_t_lambda.ensure((size_t)k.term * 8)); SZCHK(b.b_t_k.ensure((size_t)k.term * 4));
+    if (d.table_in_hbm) {   // (rank 0 of a sharded run merges the ranks' tables: this one goes there from HBM)
+        SZCHK(b.b_sv_out.ensure((size_t)k.sv * sizeof(SvOut))); SZCHK(b.b_sv_key.ensure((size_t)k.sv * 8));
+        SZCHK(b.b_lib_index_out.ensure((size_t)k.term * 4)); SZCHK(b.b_lib_pairs_out.ensure((size_t)k.term * 4));
+        SZCHK(b.b_cn_key_out.ensure((size_t)k.cn * 4 + 16)); SZCHK(b.b_cn_value_out.ensure((size_t)k.cn * 4 + 16));
+        SZCHK(b.b_ltail_out.ensure((size_t)k.term * 8));
+    } else {
+        SZCHK(b.h_sv_out.ensure((size_t)k.sv * sizeof(SvOut)));
+        SZCHK(b.h_lib_index.ensure((size_t)k.term * 4)); SZCHK(b.h_lib_pairs.ensure((size_t)k.term * 4));
+        SZCHK(b.h_cn_key.ensure((size_t)k.cn * 4 + 16)); SZCHK(b.h_cn_value.ensure((size_t)k.cn * 4 + 16));
+        SZCHK(b.h_ltail_dev.ensure((size_t)k.term * 8));
+    }
+    SZCHK(b.h_counts2.ensure(sizeof(StageCounts)));
+    SZCHK(b.b_sv_src.ensure((size_t)k.sv * 16)); SZCHK(b.b_ltail.ensure((size_t)k.term * 8));
+    SZCHK(b.b_dlists.ensure((size_t)k.term * 4 + (size_t)k.cn * 8 + 64));
+    // old_key [p2] u64 | hs_key_dev [sv] u64 | old_slot [p2] | ins_T, ins_src, ins_pre_l, ins_pre_c [sv + 1] each | sorted_key [nsort] u64 | sorted_slot [nsort] | rank_part
+    SZCHK(b.b_ins.ensure(k.p2 * 12 + (size_t)k.sv * 8 + ((size_t)k.sv + 1) * 16 + k.nsort * 12 + k.nsort * 4 * kK6RankSlices + 64));
+    SZCHK(size_zero_once(b.b_ws6, 4 * (scan_grid((uint32_t)cap, 1) + 1) * 8, s));   // look-back words of the table scan
+    return BDX_OK;
+}
+
 // K2: compact anomalous reads (prefix counters offset by the bases of earlier shards)
-int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepare_join, const Sizing* sz = nullptr) {
+int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepare_join) {
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int nkeys = c->nkeys;
-    const uint32_t na = sz ? sz->na : c->na_alloc;
-    if (c->stage_timing && !sz) HIPCHK(c, hipEventRecord(c->ev[2], s));
-    Compact cp_sz{};
-    K3Arrays k3_sz{};
-    Compact& cp = sz ? cp_sz : c->cp;
-    K3Arrays& k3 = sz ? k3_sz : c->k3;
+    const uint32_t na = c->na_alloc;
+    if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[2], s));
+    Compact& cp = c->cp;
     cp = Compact{};
-    k3 = K3Arrays{};
+    c->k3 = K3Arrays{};
     if (na) {
-        if (na > kMaxAnomalous) return fail(c, BDX_ELIMIT, "more than 2^31 anomalous reads in one context");
-        const size_t cap = na;
-        HIPCHK(c, c->b_c_tid.ensure(cap * 4)); HIPCHK(c, c->b_c_pos.ensure(cap * 4)); HIPCHK(c, c->b_c_isize.ensure(cap * 4));
-        HIPCHK(c, c->b_c_meta.ensure(cap * 4)); HIPCHK(c, c->b_c_key.ensure(cap * 8)); HIPCHK(c, c->b_c_nn.ensure(cap * 4));
-        HIPCHK(c, c->b_c_idx.ensure(cap * 4));
-        if (c->use_check) HIPCHK(c, c->b_c_check.ensure(cap * 8));
-        HIPCHK(c, c->b_c_pk.ensure(cap * 4 * nkeys));
-        cp.tid = c->b_c_tid.as<int32_t>(); cp.pos = c->b_c_pos.as<int32_t>(); cp.isize = c->b_c_isize.as<int32_t>();
-        cp.meta = c->b_c_meta.as<uint32_t>(); cp.key = c->b_c_key.as<uint64_t>(); cp.nn = c->b_c_nn.as<uint32_t>();
-        cp.idx = c->b_c_idx.as<uint32_t>();
-        cp.check = c->use_check ? c->b_c_check.as<uint64_t>() : nullptr;
-        cp.pk = c->b_c_pk.as<uint32_t>(); cp.cap = na;
+        StageDims dm = stage_dims(c, na);
+        dm.k2_clears_join = dm.k2_clears_join && prepare_join;
+        BDX_TRY(size_compact(c->sb, dm, &c->err));
+        const StageBufs& b = c->sb;
+        cp.tid = b.b_c_tid.as<int32_t>(); cp.pos = b.b_c_pos.as<int32_t>(); cp.isize = b.b_c_isize.as<int32_t>();
+        cp.meta = b.b_c_meta.as<uint32_t>(); cp.key = b.b_c_key.as<uint64_t>(); cp.nn = b.b_c_nn.as<uint32_t>();
+        cp.idx = b.b_c_idx.as<uint32_t>();
+        cp.check = c->use_check ? b.b_c_check.as<uint64_t>() : nullptr;
+        cp.pk = b.b_c_pk.as<uint32_t>(); cp.cap = na;
         K2Params k2{};
         k2.r = c->d; k2.n = c->n; k2.ntiles = c->ntiles; k2.tstride = c->tstride; k2.nkeys = nkeys; k2.nlibs = c->nlibs; k2.libs = c->b_libs.as<DevLib>();
         k2.cls = c->b_cls.as<uint8_t>(); k2.tile_pre = c->b_tile_pre.as<uint32_t>(); k2.c = cp;
@@ -953,19 +1106,15 @@ int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepa
         for (int k = 0; k < nkeys; ++k) k2.pk_base[k] = pk_base ? pk_base[k] : 0u;
         // scratch of the later stages cleared by this launch: the per-candidate max read length of K3, and (when this
         // context joins its own reads) the slot indices of K4's direct table
-        HIPCHK(c, c->b_c_maxq.ensure(cap * 4));
-        k2.fill_ptr[0] = c->b_c_maxq.as<uint32_t>(); k2.fill_words[0] = na; k2.fill_value[0] = 0u;
-        if (!sz) c->join_table_clean = 0;
-        if (prepare_join && (c->force_direct_join || (!c->bucketed_join && na <= kDirectJoinMax))) {
-            const uint32_t slots = direct_join_slots(na);
-            HIPCHK(c, c->b_t_key.ensure((size_t)slots * 8)); HIPCHK(c, c->b_partner.ensure((size_t)na * 4));
-            k2.fill_ptr[1] = c->b_t_key.as<uint32_t>(); k2.fill_words[1] = 2 * slots; k2.fill_value[1] = 0xFFFFFFFFu;
-            k2.fill_ptr[2] = c->b_partner.as<uint32_t>(); k2.fill_words[2] = na; k2.fill_value[2] = 0xFFFFFFFFu;
-            HIPCHK(c, c->b_pair_lo.ensure((size_t)na * 4));
-            k2.fill_ptr[3] = c->b_pair_lo.as<uint32_t>(); k2.fill_words[3] = na; k2.fill_value[3] = 0xFFFFFFFFu;
-            if (!sz) c->join_table_clean = slots;
+        k2.fill_ptr[0] = b.b_c_maxq.as<uint32_t>(); k2.fill_words[0] = na; k2.fill_value[0] = 0u;
+        c->join_table_clean = 0;
+        if (dm.k2_clears_join) {
+            const uint32_t slots = dm.join_slots;
+            k2.fill_ptr[1] = b.b_t_key.as<uint32_t>(); k2.fill_words[1] = 2 * slots; k2.fill_value[1] = 0xFFFFFFFFu;
+            k2.fill_ptr[2] = b.b_partner.as<uint32_t>(); k2.fill_words[2] = na; k2.fill_value[2] = 0xFFFFFFFFu;
+            k2.fill_ptr[3] = b.b_pair_lo.as<uint32_t>(); k2.fill_words[3] = na; k2.fill_value[3] = 0xFFFFFFFFu;
+            c->join_table_clean = slots;
         }
-        if (sz) return BDX_OK;
         {   // name keys the caller's pinned batches still hold (bdx_push): one segment per batch
             size_t ns = 0;
             BDX_TRY(upload_key_segs(c, &ns));
@@ -980,7 +1129,6 @@ int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepa
         launch_k2(k2, k2_lds_bytes(nkeys), s, c->finalize2_deferred ? &c->fp_deferred : nullptr);
         c->finalize2_deferred = false;
     }
-    if (sz) return BDX_OK;
     if (c->finalize2_deferred) {  // (no K2 launch to ride on)
         launch_finalize2_only(c->fp_deferred, s);
         c->finalize2_deferred = false;
@@ -996,7 +1144,7 @@ int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepa
 // a result whose region table is read where the device left it (c->reg == h_regs.p: bdx_run on a large table, sharded runs) gets its own copy:
 // called before the pinned buffers may be reallocated under it (a sizing pass for a larger input) or handed back (bdx_trim_results)
 void own_borrowed_regions(bdx_ctx* c) {
-    if (!c->reg || (const void*)c->reg != c->h_regs.p) return;
+    if (!c->reg || (const void*)c->reg != c->sb.h_regs.p) return;
     const HostRegion* r = c->reg;
     const uint32_t* pk = c->rpk;
     const size_t n = c->nreg;
@@ -1007,141 +1155,102 @@ void own_borrowed_regions(bdx_ctx* c) {
     c->reg = c->regions.data(); c->rpk = c->r_pk.data();
 }
 
-int do_cut(bdx_ctx* c, int has_next, int32_t next_qlen, uint32_t next_nn, bool for_k6, bool keep_dev = false, const Sizing* sz = nullptr) {
+int do_cut(bdx_ctx* c, const K3Tail& tail, RegionDst dst) {
     HIPCHK(c, hipSetDevice(c->device));
-    if (sz) own_borrowed_regions(c);   // (a sizing pass may grow the pinned table below.  bdx_reserve sizes nothing once the context has run, and the decoder's
-                                       // pass follows a reset -- no live result should be here; if one is, it keeps a copy)
     hipStream_t s = c->stream;
-    const int nkeys = c->nkeys;
-    const uint32_t na = sz ? sz->na : c->na_alloc;
-    const uint32_t nn_base = c->nn_base;
-    Compact& cp = c->cp;
-    K3Arrays k3_sz{};
-    K3Arrays& k3 = sz ? k3_sz : c->k3;
+    const uint32_t na = c->na_alloc;
     if (na) {
-        const size_t cap = na;
-        DevBuf* u32bufs[] = {&c->b_cand, &c->b_pre_q, &c->b_pre_rev, &c->b_pre_nonctx, &c->b_c_first, &c->b_c_maxq, &c->b_c_rid,
-                             &c->b_region_of};
-        for (DevBuf* b : u32bufs) HIPCHK(c, b->ensure(cap * 4));
-        // the region table and (below) the group list are written by the kernels straight into pinned host memory:
-        // they are write-once, read-never on the device, so the PCIe writes overlap the kernels and no D2H copy is needed
-        const bool hbm_only = keep_dev && !for_k6;   // sharded runs: a chromosome's table is sent on from HBM, nobody reads it on this host
-        if (!hbm_only) {
-            HIPCHK(c, c->h_regs.ensure(cap * sizeof(RegionRec)));
-            HIPCHK(c, c->h_pk.ensure(cap * 2 * nkeys * 4));
-        }
+        StageDims dm = stage_dims(c, na);
+        dm.regions = dst;
+        BDX_TRY(size_cut(c->sb, dm, s, &c->err));
+        const StageBufs& b = c->sb;
+        K3Arrays& k3 = c->k3;
+        const bool for_k6 = dst == RegionDst::HostAndHbm, hbm_only = dst == RegionDst::Hbm;
         k3.cap = na;
-        k3.cand = c->b_cand.as<int32_t>(); k3.pre_q = c->b_pre_q.as<uint32_t>(); k3.pre_rev = c->b_pre_rev.as<uint32_t>();
-        k3.pre_nonctx = c->b_pre_nonctx.as<uint32_t>(); k3.c_first = c->b_c_first.as<uint32_t>();
-        k3.c_maxq = c->b_c_maxq.as<int32_t>(); k3.c_rid = c->b_c_rid.as<int32_t>(); k3.region_of = c->b_region_of.as<int32_t>();
-        k3.r_rec = c->h_regs.as<RegionRec>(); k3.r_pk = c->h_pk.as<uint32_t>();
-        if (for_k6) {  // the device-side SV assembly reads the region table back: keep a copy in HBM
-            HIPCHK(c, c->b_r_rec.ensure(cap * sizeof(RegionRec)));
-            HIPCHK(c, c->b_r_pk.ensure(cap * 2 * nkeys * 4));
-            HIPCHK(c, c->b_out_deg.ensure(cap * 6 * 4));
-            k3.r_rec_dev = c->b_r_rec.as<RegionRec>(); k3.r_pk_dev = c->b_r_pk.as<uint32_t>(); k3.out_deg = c->b_out_deg.as<uint32_t>();
+        k3.cand = b.b_cand.as<int32_t>(); k3.pre_q = b.b_pre_q.as<uint32_t>(); k3.pre_rev = b.b_pre_rev.as<uint32_t>();
+        k3.pre_nonctx = b.b_pre_nonctx.as<uint32_t>(); k3.c_first = b.b_c_first.as<uint32_t>();
+        k3.c_maxq = b.b_c_maxq.as<int32_t>(); k3.c_rid = b.b_c_rid.as<int32_t>(); k3.region_of = b.b_region_of.as<int32_t>();
+        k3.r_rec = hbm_only ? b.b_r_rec.as<RegionRec>() : b.h_regs.as<RegionRec>();
+        k3.r_pk = hbm_only ? b.b_r_pk.as<uint32_t>() : b.h_pk.as<uint32_t>();
+        if (for_k6) {  // the device-side SV assembly reads the region table back: a copy in HBM
+            k3.r_rec_dev = b.b_r_rec.as<RegionRec>(); k3.r_pk_dev = b.b_r_pk.as<uint32_t>(); k3.out_deg = b.b_out_deg.as<uint32_t>();
             // with the direct join right behind K3, that kernel forwards the table to the host
             k3.host_copy_later = (!c->bucketed_join && na <= kDirectJoinMax) ? 1 : 0;
+            memset(b.h_counts0.p, 0, sizeof(StageCounts));
+            k3.counts_host = b.h_counts0.as<StageCounts>();
         }
-        {   // look-back words of the two scans, sized for one element per thread (the finest split they use)
-            const size_t words = 5 * (scan_grid(na, 1) + 1);
-            if (c->b_lb.bytes < words * 8) {  // the look-back words must start out zero; afterwards every run brings its own stamp
-                HIPCHK(c, c->b_lb.ensure(words * 8));
-                HIPCHK(c, hipMemsetAsync(c->b_lb.p, 0, c->b_lb.bytes, s));
-            }
-            k3.lb_state = c->b_lb.as<unsigned long long>();
-            if (!sz) HIPCHK(c, next_lb_stamp(c, &k3.lb_stamp));
-        }
+        if (hbm_only) { k3.r_rec_dev = nullptr; k3.r_pk_dev = nullptr; k3.host_copy_later = 0; }
+        k3.lb_state = b.b_lb.as<unsigned long long>();
+        HIPCHK(c, next_lb_stamp(c, &k3.lb_stamp));
         k3.counts = c->b_counts.as<StageCounts>();
-        if (for_k6) {
-            HIPCHK(c, c->h_counts0.ensure(sizeof(StageCounts)));
-            if (!sz) memset(c->h_counts0.p, 0, sizeof(StageCounts));
-            k3.counts_host = c->h_counts0.as<StageCounts>();
-        }
-        if (hbm_only) {  // (no pinned mirror: pinning 24 chromosomes' tables cost a sharded run tens of milliseconds)
-            HIPCHK(c, c->b_r_rec.ensure(cap * sizeof(RegionRec)));
-            HIPCHK(c, c->b_r_pk.ensure(cap * 2 * nkeys * 4));
-            k3.r_rec = c->b_r_rec.as<RegionRec>(); k3.r_pk = c->b_r_pk.as<uint32_t>();
-            k3.r_rec_dev = nullptr; k3.r_pk_dev = nullptr;
-            k3.host_copy_later = 0;
-        }
-        if (sz) return BDX_OK;
-        K3Tail tail{has_next, next_qlen, next_nn, c->k3_tid_tail};
         // single-context runs that take the direct join let that kernel do k3_region_of_kernel's work
         c->region_of_fused = for_k6 && !c->bucketed_join && na <= kDirectJoinMax;
-        launch_k3(k3, cp, c->b_p1.as<Pass1>(), na, c->opts.min_len, c->opts.seq_coverage_lim, nkeys, nn_base, tail, !c->region_of_fused, s);
+        launch_k3(k3, c->cp, c->b_p1.as<Pass1>(), na, c->opts.min_len, c->opts.seq_coverage_lim, c->nkeys, c->nn_base, tail, !c->region_of_fused, s);
         if (for_k6 && !k3.host_copy_later) {  // the region table is in pinned memory
             BDX_TRY(signal_ready(c, 3, c->ev_regions));
         }
     }
-    if (sz) return BDX_OK;
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[4], s));
     c->stage = 3;
     return BDX_OK;
 }
 
-// K4 on the context's own reads (single-context run)
-int do_join_local(bdx_ctx* c, uint32_t n, const Entries& en, const uint32_t* n_ptr, bool join_only, const Sizing* sz = nullptr) {
+// K4 on the context's own reads (single-context run), with the foreign entries of a sharded run behind them, or on a staged run's entries
+int do_join_local(bdx_ctx* c, uint32_t n, const Entries& en, const uint32_t* n_ptr, bool join_only) {
     hipStream_t s = c->stream;
-    K4Arrays k4_sz{};
-    K4Arrays& k4 = sz ? k4_sz : c->k4;
+    K4Arrays& k4 = c->k4;
     k4 = K4Arrays{};
     if (!n) return BDX_OK;
-    k4.g_cap = n / 2 + 1;
-    if (c->groups_in_hbm) {   // sharded runs: the groups are packaged for rank 0 from HBM
-        HIPCHK(c, c->b_groups.ensure((size_t)k4.g_cap * sizeof(GroupRec)));
-        k4.g_rec = c->b_groups.as<GroupRec>();
-    } else {
-        HIPCHK(c, c->h_groups.ensure((size_t)k4.g_cap * sizeof(GroupRec)));
-        k4.g_rec = c->h_groups.as<GroupRec>();
-    }
-    // (foreign entries of a sharded run have no partner[] / pair_lo[] entry: sized for the context's own reads, as K2 cleared them)
-    const size_t n_own = en.n_local ? std::min<size_t>(n, std::max<uint32_t>(c->na_alloc, 1u)) : n;
-    HIPCHK(c, c->b_partner.ensure(n_own * 4));
-    k4.partner = c->b_partner.as<int32_t>();
-    if (sz) return BDX_OK;  // (the direct table is sized by do_compact; the bucketed join sizes its own when it runs)
-    if (c->force_direct_join || (!c->bucketed_join && n <= kDirectJoinMax)) {
-        uint32_t slots = direct_join_slots(n);
-        // (the foreign entries of a sharded run come on top of the reads K2 sized the table for: it still has room at half its load)
-        if (c->join_table_clean && (uint64_t)n * 2 <= c->join_table_clean) slots = c->join_table_clean;
+    const bool direct = c->force_direct_join || (!c->bucketed_join && n <= kDirectJoinMax);
+    StageDims dm = stage_dims(c, c->na_alloc);
+    dm.join_n = n;
+    dm.join_own = en.n_local ? std::min<uint32_t>(n, std::max<uint32_t>(c->na_alloc, 1u)) : n;
+    // (the foreign entries of a sharded run come on top of the reads K2 sized the table for: it still has room at half its load)
+    dm.join_slots = !direct ? 0u : (c->join_table_clean && (uint64_t)n * 2 <= c->join_table_clean) ? c->join_table_clean : direct_join_slots(n);
+    dm.join_pair_lo = en.want_pair_lo != 0;
+    BDX_TRY(size_join(c->sb, dm, &c->err));
+    StageBufs& b = c->sb;
+    k4.g_cap = dm.join_groups();
+    k4.g_rec = c->groups_in_hbm ? b.b_groups.as<GroupRec>() : b.h_groups.as<GroupRec>();
+    k4.partner = b.b_partner.as<int32_t>();
+    if (direct) {
+        const uint32_t slots = dm.join_slots;
+        const size_t n_own = dm.join_own;
         const bool want_lo = en.c_rid || en.want_pair_lo;
-        if (c->join_table_clean != slots) {
-            HIPCHK(c, c->b_t_key.ensure((size_t)slots * 8));
-            HIPCHK(c, hipMemsetAsync(c->b_t_key.p, 0xFF, (size_t)slots * 8, s));
-            HIPCHK(c, hipMemsetAsync(c->b_partner.p, 0xFF, n_own * 4, s));
-            if (en.want_pair_lo) {
-                HIPCHK(c, c->b_pair_lo.ensure(n_own * 4));
-                HIPCHK(c, hipMemsetAsync(c->b_pair_lo.p, 0xFF, n_own * 4, s));
-            }
+        if (c->join_table_clean != slots) {   // (K2 has not preset the table)
+            HIPCHK(c, hipMemsetAsync(b.b_t_key.p, 0xFF, (size_t)slots * 8, s));
+            HIPCHK(c, hipMemsetAsync(b.b_partner.p, 0xFF, n_own * 4, s));
+            if (en.want_pair_lo) HIPCHK(c, hipMemsetAsync(b.b_pair_lo.p, 0xFF, n_own * 4, s));
         }
-        k4.pair_lo = ((c->join_table_clean == slots && want_lo) || en.want_pair_lo) ? c->b_pair_lo.as<int32_t>() : nullptr;  // preset to -1 by K2
+        k4.pair_lo = ((c->join_table_clean == slots && want_lo) || en.want_pair_lo) ? b.b_pair_lo.as<int32_t>() : nullptr;  // preset to -1 by K2
         c->join_table_clean = 0;
         k4.direct = 1; k4.t_mask = slots - 1;
-        k4.t_key = c->b_t_key.as<uint64_t>(); k4.t_idx = c->b_t_idx.as<int32_t>();
+        k4.t_key = b.b_t_key.as<uint64_t>(); k4.t_idx = b.b_t_idx.as<int32_t>();
         if (join_only) launch_k4_join_only(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
         else launch_k4(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
         return BDX_OK;
     }
+    // the partitioned join: its tables go by the entries that have arrived, sized here
     uint32_t nb = 1, lg = 0;
     while (nb < (uint32_t)kMaxBuckets && (size_t)nb * 384 < n) { nb <<= 1; ++lg; }  // ~256-512 entries per bucket: >= 1 workgroup per CU early
     k4.nbuckets = nb; k4.log2b = lg;
-    if ((size_t)nb * 4 > c->b_bcnt.bytes) {  // (re)allocated: the partition histogram has to start from zero once
-        HIPCHK(c, c->b_bcnt.ensure((size_t)kMaxBuckets * 4));
-        HIPCHK(c, hipMemsetAsync(c->b_bcnt.p, 0, c->b_bcnt.bytes, s));
+    if ((size_t)nb * 4 > b.b_bcnt.bytes) {  // (re)allocated: the partition histogram has to start from zero once
+        HIPCHK(c, b.b_bcnt.ensure((size_t)kMaxBuckets * 4));
+        HIPCHK(c, hipMemsetAsync(b.b_bcnt.p, 0, b.b_bcnt.bytes, s));
     }
-    HIPCHK(c, c->b_boff.ensure((nb + 1) * 4)); HIPCHK(c, c->b_bcur.ensure(nb * 4));
-    HIPCHK(c, c->b_e_key.ensure((size_t)n * 8)); HIPCHK(c, c->b_e_idx.ensure((size_t)n * 4));
-    HIPCHK(c, c->b_t_key.ensure((size_t)n * 16)); HIPCHK(c, c->b_t_idx.ensure((size_t)n * 8));
-    k4.bcnt = c->b_bcnt.as<uint32_t>(); k4.boff = c->b_boff.as<uint32_t>(); k4.bcur = c->b_bcur.as<uint32_t>();
-    k4.e_key = c->b_e_key.as<uint64_t>(); k4.e_idx = c->b_e_idx.as<uint32_t>();
-    k4.t_key = c->b_t_key.as<uint64_t>(); k4.t_idx = c->b_t_idx.as<int32_t>();
+    HIPCHK(c, b.b_boff.ensure((nb + 1) * 4)); HIPCHK(c, b.b_bcur.ensure(nb * 4));
+    HIPCHK(c, b.b_e_key.ensure((size_t)n * 8)); HIPCHK(c, b.b_e_idx.ensure((size_t)n * 4));
+    HIPCHK(c, b.b_t_key.ensure((size_t)n * 16)); HIPCHK(c, b.b_t_idx.ensure((size_t)n * 8));
+    k4.bcnt = b.b_bcnt.as<uint32_t>(); k4.boff = b.b_boff.as<uint32_t>(); k4.bcur = b.b_bcur.as<uint32_t>();
+    k4.e_key = b.b_e_key.as<uint64_t>(); k4.e_idx = b.b_e_idx.as<uint32_t>();
+    k4.t_key = b.b_t_key.as<uint64_t>(); k4.t_idx = b.b_t_idx.as<int32_t>();
     if (join_only) launch_k4_join_only(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
     else launch_k4(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
     return BDX_OK;
 }
 
-// counts + region table (+ groups) to the host
-int readback(bdx_ctx* c, bool with_groups) {
+// counts + region table to the host (the table already sits in pinned host memory: see size_cut)
+int readback(bdx_ctx* c) {
     hipStream_t s = c->stream;
     const uint32_t na = c->p1.n_anom;
     if (!na) return BDX_OK;
@@ -1150,7 +1259,6 @@ int readback(bdx_ctx* c, bool with_groups) {
     HIPCHK(c, hipGetLastError());
     c->counts = *c->h_counts.as<StageCounts>();
     if (c->counts.overflow) return fail(c, BDX_EINTERNAL, "group list overflow");
-    (void)with_groups;  // regions / prefix samples / groups already sit in pinned host memory (see do_cut / do_join_local)
     return BDX_OK;
 }
 
@@ -1181,114 +1289,60 @@ void decode_groups(bdx_ctx* c, const GroupRec* gr, uint32_t ng, uint32_t ph) {
     }
 }
 
-// K6 on the context's own regions (single-context runs): pair groups per region, SV assembly of the components that need
-// no traversal, everything else listed for the host walk; then the dense results and K5 for the device-assembled SVs.
-// part: 0 the whole first half; 1 up to and including k6_pairs_kernel, 2 the rest; 3 the deferred device walk; 4 the arrays and no launch
+// K6 on the context's own regions: pair groups per region, SV assembly of the components that need no traversal, everything else listed
+// for the host walk; then (do_k6_table) the dense results and K5 for the device-assembled SVs.  k6_prepare lays out K6's arrays and run
+// constants and launches nothing; the callers then launch what they mean (k6_pairs, k6_then_walk below).
 // rounds: min-label propagation rounds (0: kK6LabelRounds, or kK6LabelRoundsBig with the general walk)
-int do_k6(bdx_ctx* c, bool force_host, int part = 0, const Sizing* sz = nullptr, int rounds = 0) {
+int k6_prepare(bdx_ctx* c, bool force_host, int rounds) {
     hipStream_t s = c->stream;
-    K6Arrays a_sz{};
-    K6Arrays& a = sz ? a_sz : c->k6;
-    if (part == 2) {
-        if (!a.cap) return BDX_OK;
-        launch_k6_components(a, a.cap, s);
-        if (!c->poll) {
-            BDX_TRY(signal_ready(c, 1, c->ev_groups));
-        }
-        if (!c->defer_walk) launch_k6_walk(a, a.cap, s);
-        return BDX_OK;
-    }
-    if (part == 3) {   // (the deferred device walk)
-        if (a.cap) launch_k6_walk(a, a.cap, s);
-        return BDX_OK;
-    }
-    const uint32_t na = std::max(sz ? sz->na : c->na_alloc, c->k6_cap);   // (sharded runs: K6's arrays are indexed by genome-wide region id)
-    const int nkeys = c->nkeys, nlibs = c->nlibs;
+    K6Arrays& a = c->k6;
     a = K6Arrays{};
+    const StageDims dm = stage_dims(c, c->na_alloc);
+    const uint32_t na = dm.k6_regions();
     if (!na) return BDX_OK;
-    const size_t cap = na;
-    HIPCHK(c, c->b_out_deg.ensure(cap * 6 * 4));
-    HIPCHK(c, c->b_parts.ensure(cap * sizeof(PartRec)));
-    HIPCHK(c, c->b_rs.ensure(cap * sizeof(RegSum)));
-    HIPCHK(c, c->b_members.ensure(cap * kK6MaxMembers * sizeof(MemberInfo)));
-    HIPCHK(c, c->b_own.ensure(cap * 7 * 4 + 64 * 4 * 4));
-    // Components of 5..64 regions cost one more launch (k6_walk_big_kernel) and a member table of 256 B per label.  Few of
-    // them are walked by the host behind the device's own walk for free; many (dense data) make the host walk the longest
-    // stage.  Without a previous run to go by, the number of anomalous reads decides.
-    const int big_walk = c->big_walk_mode >= 0 ? c->big_walk_mode : (c->last_big_groups >= 0 ? c->last_big_groups > 2000 : na > 500000u);
-    if (big_walk) HIPCHK(c, c->b_member_ids.ensure(cap * kK6BigMembers * 4));
-    a.sv_cap = na / 2 + 1; a.term_cap = na / 2 + 1; a.cn_cap = (na / 2 + 1) * (uint32_t)nkeys;
-    a.lib_stride = (uint32_t)std::min(nlibs, kK6LibStride);
-    HIPCHK(c, c->b_slot.ensure(cap * sizeof(SvOut)));
-    HIPCHK(c, c->b_lib_stage.ensure(cap * a.lib_stride * sizeof(LibStage)));
-    HIPCHK(c, c->b_cn_stage.ensure(cap * (size_t)nkeys * sizeof(CnStage) + 16));
-    HIPCHK(c, c->b_t_lambda.ensure((size_t)a.term_cap * 8)); HIPCHK(c, c->b_t_k.ensure((size_t)a.term_cap * 4));
-    const size_t nblk = scan_grid(na, 1) + 1;
-    if (c->table_in_hbm) {   // (rank 0 of a sharded run merges the ranks' tables: this one goes there from HBM)
-        HIPCHK(c, c->b_sv_out.ensure((size_t)a.sv_cap * sizeof(SvOut))); HIPCHK(c, c->b_sv_key.ensure((size_t)a.sv_cap * 8));
-        HIPCHK(c, c->b_lib_index_out.ensure((size_t)a.term_cap * 4)); HIPCHK(c, c->b_lib_pairs_out.ensure((size_t)a.term_cap * 4));
-        HIPCHK(c, c->b_cn_key_out.ensure((size_t)a.cn_cap * 4 + 16)); HIPCHK(c, c->b_cn_value_out.ensure((size_t)a.cn_cap * 4 + 16));
-        HIPCHK(c, c->b_ltail_out.ensure((size_t)a.term_cap * 8));
-    } else {
-        HIPCHK(c, c->h_sv_out.ensure((size_t)a.sv_cap * sizeof(SvOut)));
-        HIPCHK(c, c->h_lib_index.ensure((size_t)a.term_cap * 4)); HIPCHK(c, c->h_lib_pairs.ensure((size_t)a.term_cap * 4));
-        HIPCHK(c, c->h_cn_key.ensure((size_t)a.cn_cap * 4 + 16)); HIPCHK(c, c->h_cn_value.ensure((size_t)a.cn_cap * 4 + 16));
-        HIPCHK(c, c->h_ltail_dev.ensure((size_t)a.term_cap * 8));
-    }
-    HIPCHK(c, c->h_counts2.ensure(sizeof(StageCounts)));
-    HIPCHK(c, c->b_sv_src.ensure((size_t)a.sv_cap * 16)); HIPCHK(c, c->b_ltail.ensure((size_t)a.term_cap * 8));
-    HIPCHK(c, c->b_dlists.ensure((size_t)a.term_cap * 4 + (size_t)a.cn_cap * 8 + 64));
-    {   // the inserted list (k6_insert_kernel): device order keys padded to a power of two for the sort
-        size_t p2 = 1;
-        while (p2 < a.sv_cap) p2 <<= 1;
-        const size_t svc = a.sv_cap;
-        const size_t nsort = std::min<size_t>(svc, kK6RankSortMax);   // (k6_ranksort_kernel's output: lists of that many entries at most)
-        HIPCHK(c, c->b_ins.ensure(p2 * 12 + svc * 8 + (svc + 1) * 16 + nsort * 12 + nsort * 4 * kK6RankSlices + 64));
-        a.old_key = c->b_ins.as<uint64_t>(); a.hs_key_dev = a.old_key + p2;
-        a.old_slot = (uint32_t*)(a.hs_key_dev + svc); a.ins_T = a.old_slot + p2; a.ins_src = a.ins_T + svc + 1;
-        a.ins_pre_l = a.ins_src + svc + 1; a.ins_pre_c = a.ins_pre_l + svc + 1;
-        a.sorted_key = (uint64_t*)(((uintptr_t)(a.ins_pre_c + svc + 1) + 7) & ~(uintptr_t)7); a.sorted_slot = (uint32_t*)(a.sorted_key + nsort);
-        // (k6_ranksort_kernel is launched, and its ranks are read, where the list of candidates placed by key CAN outgrow what k6_insert_kernel's
-        // one workgroup sorts in LDS (2,048 entries) -- a -t run's candidates are all of that kind: 5-10 k of them at a genome share took that
-        // workgroup's bitonic sort in HBM half a millisecond.  Smaller inputs do without the launch)
-        a.rank_part = a.sv_cap > 2048u ? a.sorted_slot + nsort : nullptr;
-    }
-    a.sv_begin = c->b_sv_src.as<uint2>(); a.sv_src = (uint32_t*)(a.sv_begin + a.sv_cap); a.ltail = c->b_ltail.as<double>();
-    a.d_lib_index = c->b_dlists.as<int32_t>(); a.d_cn_key = a.d_lib_index + a.term_cap; a.d_cn_value = (float*)(a.d_cn_key + a.cn_cap);
+    BDX_TRY(size_k6(c->sb, dm, s, &c->err));
+    const StageBufs& b = c->sb;
+    const K6Caps k = k6_caps(dm);
+    const int nkeys = c->nkeys, nlibs = c->nlibs;
+    const size_t cap = na, p2 = k.p2, svc = k.sv, nsort = k.nsort;
+    a.sv_cap = k.sv; a.term_cap = k.term; a.cn_cap = k.cn; a.lib_stride = k.lib_stride;
+    a.old_key = b.b_ins.as<uint64_t>(); a.hs_key_dev = a.old_key + p2;
+    a.old_slot = (uint32_t*)(a.hs_key_dev + svc); a.ins_T = a.old_slot + p2; a.ins_src = a.ins_T + svc + 1;
+    a.ins_pre_l = a.ins_src + svc + 1; a.ins_pre_c = a.ins_pre_l + svc + 1;
+    a.sorted_key = (uint64_t*)(((uintptr_t)(a.ins_pre_c + svc + 1) + 7) & ~(uintptr_t)7); a.sorted_slot = (uint32_t*)(a.sorted_key + nsort);
+    // (k6_ranksort_kernel is launched, and its ranks are read, where the list of candidates placed by key CAN outgrow what k6_insert_kernel's
+    // one workgroup sorts in LDS (2,048 entries) -- a -t run's candidates are all of that kind: 5-10 k of them at a genome share took that
+    // workgroup's bitonic sort in HBM half a millisecond.  Smaller inputs do without the launch)
+    a.rank_part = a.sv_cap > 2048u ? a.sorted_slot + nsort : nullptr;
+    a.sv_begin = b.b_sv_src.as<uint2>(); a.sv_src = (uint32_t*)(a.sv_begin + a.sv_cap); a.ltail = b.b_ltail.as<double>();
+    a.d_lib_index = b.b_dlists.as<int32_t>(); a.d_cn_key = a.d_lib_index + a.term_cap; a.d_cn_value = (float*)(a.d_cn_key + a.cn_cap);
     a.cap = na;
-    a.r_rec = c->k6_r_rec ? c->k6_r_rec : c->b_r_rec.as<RegionRec>(); a.r_pk = c->k6_r_pk ? c->k6_r_pk : c->b_r_pk.as<uint32_t>();
+    a.r_rec = c->k6_r_rec ? c->k6_r_rec : b.b_r_rec.as<RegionRec>(); a.r_pk = c->k6_r_pk ? c->k6_r_pk : b.b_r_pk.as<uint32_t>();
     a.taint = c->k6_taint;
     a.region_of = c->k3.region_of; a.partner = c->k4.partner; a.pair_lo = c->k4.pair_lo; a.meta = c->cp.meta; a.isize = c->cp.isize;
     a.in_groups = c->k6_in_groups; a.in_goff = c->k6_in_goff; a.first_of = c->k6_in_groups ? c->k6_in_goff : nullptr;
-    a.parts = c->b_parts.as<PartRec>();
-    a.rs = c->b_rs.as<RegSum>();
-    a.out_deg = c->b_out_deg.as<uint32_t>(); a.label = a.out_deg + cap; a.bad_v = a.out_deg + 2 * cap; a.bad = a.out_deg + 3 * cap;
+    a.parts = b.b_parts.as<PartRec>();
+    a.rs = b.b_rs.as<RegSum>();
+    a.out_deg = b.b_out_deg.as<uint32_t>(); a.label = a.out_deg + cap; a.bad_v = a.out_deg + 2 * cap; a.bad = a.out_deg + 3 * cap;
     a.mcount = a.out_deg + 4 * cap; a.pcount = a.out_deg + 5 * cap;
-    a.members = c->b_members.as<MemberInfo>();
-    a.own_nsv = c->b_own.as<uint32_t>(); a.own_nacc = a.own_nsv + cap; a.own_ncn = a.own_nsv + 2 * cap; a.own_first = a.own_nsv + 3 * cap; a.slot_next = a.own_nsv + 4 * cap; a.owners = a.own_nsv + 5 * cap; a.owners_big = a.own_nsv + 6 * cap; a.emit_part = a.own_nsv + 7 * cap;
-    a.member_ids = big_walk ? c->b_member_ids.as<uint32_t>() : nullptr;
-    a.sv_stage = c->b_slot.as<SvOut>(); a.lib_stage = c->b_lib_stage.as<LibStage>(); a.cn_stage = c->b_cn_stage.as<CnStage>();
+    a.members = b.b_members.as<MemberInfo>();
+    a.own_nsv = b.b_own.as<uint32_t>(); a.own_nacc = a.own_nsv + cap; a.own_ncn = a.own_nsv + 2 * cap; a.own_first = a.own_nsv + 3 * cap; a.slot_next = a.own_nsv + 4 * cap; a.owners = a.own_nsv + 5 * cap; a.owners_big = a.own_nsv + 6 * cap; a.emit_part = a.own_nsv + 7 * cap;
+    a.big_walk = dm.walks_big();
+    a.member_ids = a.big_walk ? b.b_member_ids.as<uint32_t>() : nullptr;
+    a.sv_stage = b.b_slot.as<SvOut>(); a.lib_stage = b.b_lib_stage.as<LibStage>(); a.cn_stage = b.b_cn_stage.as<CnStage>();
     if (c->table_in_hbm) {
-        a.sv_out = c->b_sv_out.as<SvOut>(); a.lib_index = c->b_lib_index_out.as<int32_t>(); a.lib_pairs = c->b_lib_pairs_out.as<int32_t>();
-        a.cn_key = c->b_cn_key_out.as<int32_t>(); a.cn_value = c->b_cn_value_out.as<float>();
-        a.sv_key = c->b_sv_key.as<unsigned long long>();
+        a.sv_out = b.b_sv_out.as<SvOut>(); a.lib_index = b.b_lib_index_out.as<int32_t>(); a.lib_pairs = b.b_lib_pairs_out.as<int32_t>();
+        a.cn_key = b.b_cn_key_out.as<int32_t>(); a.cn_value = b.b_cn_value_out.as<float>();
+        a.sv_key = b.b_sv_key.as<unsigned long long>();
     } else {
-        a.sv_out = c->h_sv_out.as<SvOut>(); a.lib_index = c->h_lib_index.as<int32_t>(); a.lib_pairs = c->h_lib_pairs.as<int32_t>();
-        a.cn_key = c->h_cn_key.as<int32_t>(); a.cn_value = c->h_cn_value.as<float>();
+        a.sv_out = b.h_sv_out.as<SvOut>(); a.lib_index = b.h_lib_index.as<int32_t>(); a.lib_pairs = b.h_lib_pairs.as<int32_t>();
+        a.cn_key = b.h_cn_key.as<int32_t>(); a.cn_value = b.h_cn_value.as<float>();
     }
     a.sv_vx = a.sv_key ? a.sv_src + a.sv_cap : nullptr;
-    a.t_lambda = c->b_t_lambda.as<double>(); a.t_k = c->b_t_k.as<int32_t>();
+    a.t_lambda = b.b_t_lambda.as<double>(); a.t_k = b.b_t_k.as<int32_t>();
     a.g_rec = c->k4.g_rec; a.g_cap = c->k4.g_cap;
-    {   // look-back words of the table scan: zero once, afterwards every run brings its own stamp
-        const size_t words = 4 * nblk;
-        if (c->b_ws6.bytes < words * 8) {
-            HIPCHK(c, c->b_ws6.ensure(words * 8));
-            HIPCHK(c, hipMemsetAsync(c->b_ws6.p, 0, c->b_ws6.bytes, s));
-        }
-        a.lb_state = c->b_ws6.as<unsigned long long>();
-        if (!sz) HIPCHK(c, next_lb_stamp(c, &a.lb_stamp));
-    }
-    if (sz) return BDX_OK;
+    a.lb_state = b.b_ws6.as<unsigned long long>();
+    HIPCHK(c, next_lb_stamp(c, &a.lb_stamp));
     a.counts = c->b_counts.as<StageCounts>();
     // run constants: the flag histogram is the device's own reduced counter table (a single-context run adopts its own
     // statistics), the read densities per counter key travel in the kernel arguments
@@ -1296,14 +1350,13 @@ int do_k6(bdx_ctx* c, bool force_host, int part = 0, const Sizing* sz = nullptr,
     a.key_density = c->b_kdens.as<float>();
     a.lib_mean = c->b_lib_mean.as<float>();
     a.counts_host = c->h_counts.as<StageCounts>();
-    a.counts_host2 = c->h_counts2.as<StageCounts>();
+    a.counts_host2 = b.h_counts2.as<StageCounts>();
     memset(c->h_counts.p, 0, sizeof(StageCounts));
-    memset(c->h_counts2.p, 0, sizeof(StageCounts));
+    memset(b.h_counts2.p, 0, sizeof(StageCounts));
     a.p1 = c->b_p1.as<Pass1>();
     a.nlibs = nlibs; a.nkeys = nkeys; a.min_read_pair = c->opts.min_read_pair; a.chr_restricted = c->opts.chr_restricted;
     a.period = std::max(1, c->opts.buffer_size + 1);
     a.force_host = force_host ? 1 : 0;
-    a.big_walk = big_walk;
     a.ins_plain = c->dbg_ins_plain;
     a.asm_plain = c->dbg_asm_plain;
     // (long chains need more rounds to agree on one label; with the general walk on, the step is long enough not to care)
@@ -1312,42 +1365,48 @@ int do_k6(bdx_ctx* c, bool force_host, int part = 0, const Sizing* sz = nullptr,
         a.flag_value = c->seq;
         a.flag_groups = c->h_flags.as<uint32_t>() + 1;
         if (c->k3.host_copy_later) a.flag_regions = c->h_flags.as<uint32_t>() + 3;
-        a.mirror_in_walk = (force_host || c->defer_walk) ? 0 : 1;  // (k6_walk_kernel follows k6_emit_kernel unless everything goes to the host, or the walk waits for the ranks' collectives)
+        a.mirror_in_walk = force_host ? 0 : 1;  // (k6_walk_kernel follows k6_emit_kernel unless everything goes to the host)
     }
-    if (part == 4) return BDX_OK;   // (the arrays only: rank 0 of a sharded run whose host walks the few gathered groups -- the table stage follows)
-    if (part == 1) {
-        launch_k6_pairs(a, na, s);
-        return BDX_OK;
-    }
-    launch_k6_groups(a, na, s);
-    if (!c->poll) {  // the host's share of the groups is complete
-        BDX_TRY(signal_ready(c, 1, c->ev_groups));
-    }
-    launch_k6_walk(a, na, s);
     return BDX_OK;
 }
 
-// bdx_reserve: the stage functions run for their allocations only
-int presize_stages(bdx_ctx* c, uint32_t na) {
-    // (may run on a thread of its own beside the thread that feeds the context: it touches the later stages' buffers and nothing else --
-    // see bdx_ctx::sizing.  Its messages go to sizing_err.)
+// the launches behind k6_prepare (none where it found nothing to do): k6_pairs_kernel alone, and `first` (launch_k6_groups: pairs and
+// components in one go; launch_k6_components) with the device's walk behind it.  A context that does not poll gets the event that says
+// the host's share of the groups is complete in between; one that polls has the word set by k6_pairs_kernel's first thread
+void k6_pairs(bdx_ctx* c) {
+    if (c->k6.cap) launch_k6_pairs(c->k6, c->k6.cap, c->stream);
+}
+int k6_then_walk(bdx_ctx* c, void (*first)(const K6Arrays&, uint32_t, hipStream_t)) {
+    const K6Arrays& a = c->k6;
+    if (!a.cap) return BDX_OK;
+    first(a, a.cap, c->stream);
+    if (!c->poll) BDX_TRY(signal_ready(c, 1, c->ev_groups));
+    launch_k6_walk(a, a.cap, c->stream);
+    return BDX_OK;
+}
+
+// A sizing pass (bdx_reserve, bdx_dist_prepare, the BAM decoder's sizing thread): the four size functions and no launch.  It may run on a
+// thread of its own beside the thread that feeds the context: the size functions see the later stages' buffers and `dm`, nothing else of
+// the context (bdx_ctx::sizing), and the message of a failure goes to sizing_err, not to the feeding thread's `err`.
+int presize_stages(bdx_ctx* c, const StageDims& dm) {
     struct Guard {
         bdx_ctx* c;
-        std::string* keep;
-        explicit Guard(bdx_ctx* c_) : c(c_), keep(t_err_sink) { c->sizing.fetch_add(1, std::memory_order_acq_rel); c->sizing_err.clear(); t_err_sink = &c->sizing_err; }
-        ~Guard() { t_err_sink = keep; c->sizing.fetch_sub(1, std::memory_order_acq_rel); }
+        explicit Guard(bdx_ctx* c_) : c(c_) { c->sizing.fetch_add(1, std::memory_order_acq_rel); c->sizing_err.clear(); }
+        ~Guard() { c->sizing.fetch_sub(1, std::memory_order_acq_rel); }
     } guard(c);
-    const Sizing sz{na};
-    int r = do_compact(c, 0, nullptr, true, &sz);
-    if (r == BDX_OK) r = do_cut(c, 0, 0, 0, true, false, &sz);
-    if (r == BDX_OK) r = do_join_local(c, na, Entries{}, nullptr, true, &sz);
-    if (r == BDX_OK) r = do_k6(c, false, 0, &sz);
-    return r;
+    std::string* err = &c->sizing_err;
+    SZCHK(hipSetDevice(c->device));
+    own_borrowed_regions(c);   // (the pinned region table may grow below.  bdx_reserve sizes nothing once the context has run, and the decoder's
+                               // pass follows a reset -- no live result should read it in place; if one does, it keeps a copy)
+    BDX_TRY(size_compact(c->sb, dm, err));
+    BDX_TRY(size_cut(c->sb, dm, c->stream, err));
+    BDX_TRY(size_join(c->sb, dm, err));
+    return size_k6(c->sb, dm, c->stream, err);
 }
 
 // a sizing pass on the caller's own thread: its message is the context's
-int presize_stages_here(bdx_ctx* c, uint32_t na) {
-    const int r = presize_stages(c, na);
+int presize_stages_here(bdx_ctx* c, const StageDims& dm) {
+    const int r = presize_stages(c, dm);
     if (r != BDX_OK) c->err = c->sizing_err;
     return r;
 }
@@ -1394,7 +1453,7 @@ int do_k6_table(bdx_ctx* c) {
     }
     // (K5 runs inside the table kernel.  The terms' log tails go to the host for Fisher's combination only -- BreakDancer.cpp:71-81 uses the
     // host's exp / log --; otherwise they are 8 bytes per term over PCIe that nobody reads)
-    a.ltail_host = c->table_in_hbm ? c->b_ltail_out.as<double>() : (c->opts.fisher ? c->h_ltail_dev.as<double>() : nullptr);
+    a.ltail_host = c->table_in_hbm ? c->sb.b_ltail_out.as<double>() : (c->opts.fisher ? c->sb.h_ltail_dev.as<double>() : nullptr);
     // (the table kernel's launch: for the regions the pair groups' report named -- the host has read it by now -- not for their upper bound)
     a.fin_regions = (c->counts.n_regions && c->counts.n_regions <= na) ? c->counts.n_regions : na;
     HIPCHK(c, c->h_printed.ensure((size_t)k6_score_grid(a) * 4));
@@ -1421,7 +1480,7 @@ int materialize(bdx_ctx* c) {
     if (c->rows_packed) {
         // the rows crossed the link as SvWire: chromosomes and strand counts are the regions' (SvBuilder.cpp:18-99 takes them from there too),
         // the list offsets the running sums of the counts in table order
-        const SvWire* w = c->h_sv_out.as<SvWire>();
+        const SvWire* w = c->sb.h_sv_out.as<SvWire>();
         M.svs.resize(n);
         int32_t lb = 0, cb = 0;
         for (uint32_t i = 0; i < n; ++i) {
@@ -1442,14 +1501,14 @@ int materialize(bdx_ctx* c) {
             o.grp_mask = (r.bits >> 20) & 7u; o.start = r.start;
         }
     } else {
-        const HostSv* d = c->h_sv_out.as<HostSv>();
+        const HostSv* d = c->sb.h_sv_out.as<HostSv>();
         M.svs.assign(d, d + n);
     }
-    M.lib_index.assign(c->h_lib_index.as<int32_t>(), c->h_lib_index.as<int32_t>() + nt);
-    M.lib_pairs.assign(c->h_lib_pairs.as<int32_t>(), c->h_lib_pairs.as<int32_t>() + nt);
-    M.cn_key.assign(c->h_cn_key.as<int32_t>(), c->h_cn_key.as<int32_t>() + nc);
-    M.cn_value.assign(c->h_cn_value.as<float>(), c->h_cn_value.as<float>() + nc);
-    if (c->opts.fisher) c->log_tail.assign(c->h_ltail_dev.as<double>(), c->h_ltail_dev.as<double>() + nt); else c->log_tail.clear();
+    M.lib_index.assign(c->sb.h_lib_index.as<int32_t>(), c->sb.h_lib_index.as<int32_t>() + nt);
+    M.lib_pairs.assign(c->sb.h_lib_pairs.as<int32_t>(), c->sb.h_lib_pairs.as<int32_t>() + nt);
+    M.cn_key.assign(c->sb.h_cn_key.as<int32_t>(), c->sb.h_cn_key.as<int32_t>() + nc);
+    M.cn_value.assign(c->sb.h_cn_value.as<float>(), c->sb.h_cn_value.as<float>() + nc);
+    if (c->opts.fisher) c->log_tail.assign(c->sb.h_ltail_dev.as<double>(), c->sb.h_ltail_dev.as<double>() + nt); else c->log_tail.clear();
     M.n_groups = c->n_groups_total;
     c->materialized = true;
     return BDX_OK;
@@ -1468,7 +1527,7 @@ int finish_table(bdx_ctx* c) {
                       offsetof(HostSv, start) == offsetof(SvOut, start), "SV record layout");
     c->n_sv_host = (uint32_t)c->walk.svs.size();
     c->n_groups_total = c->walk.n_groups + c->counts.n_groups_dev;
-    const StageCounts c2 = *c->h_counts2.as<StageCounts>();
+    const StageCounts c2 = *c->sb.h_counts2.as<StageCounts>();
     if (c2.overflow) return fail(c, BDX_EINTERNAL, "SV list overflow");
     c->n_sv_total = c2.n_sv_dev; c->n_terms_total = c2.n_terms_dev; c->n_cn_total = c2.n_cn_dev;
     c->counts.n_sv_dev = c2.n_sv_dev - c->n_sv_host;
@@ -1672,7 +1731,7 @@ int bdx_run(bdx_ctx* c) {
     // K2 .. K6 (first half) for c->na_alloc anomalous reads
     auto enqueue_middle = [&]() -> int {
         BDX_TRY(do_compact(c, 0, nullptr, true));
-        BDX_TRY(do_cut(c, 0, 0, 0, true));
+        BDX_TRY(do_cut(c, K3Tail{}, RegionDst::HostAndHbm));
         if (!c->na_alloc) return BDX_OK;
         // the region table is final after K3: the host takes its copy while the device joins the mates
         Entries en{};
@@ -1691,7 +1750,8 @@ int bdx_run(bdx_ctx* c) {
         if (c->k3.host_copy_later && !c->poll) {  // the join kernel has forwarded the region table to pinned memory
             BDX_TRY(signal_ready(c, 3, c->ev_regions));  // (polling: the next kernel, k6_pairs_kernel, sets the ready word itself)
         }
-        return do_k6(c, force_host);
+        BDX_TRY(k6_prepare(c, force_host, 0));
+        return k6_then_walk(c, launch_k6_groups);
     };
     // enqueue-ahead when this context has just run an input of the same size
     uint32_t guess = 0;
@@ -1755,7 +1815,7 @@ int bdx_run(bdx_ctx* c) {
         }
         // (the table sits in pinned memory the device has just written: one streaming copy into ordinary memory is much
         // cheaper than the walk's scattered reads of it)
-        if ((uint64_t)c->h_counts0.as<StageCounts>()->n_regions + ph > kMaxRegions) {   // (region ids are 26-bit fields of the packed group key)
+        if ((uint64_t)c->sb.h_counts0.as<StageCounts>()->n_regions + ph > kMaxRegions) {   // (region ids are 26-bit fields of the packed group key)
             HIPCHK(c, hipStreamSynchronize(s));
             return fail(c, BDX_ELIMIT, "more than 2^26 - 2 accepted regions in one context");
         }
@@ -1764,16 +1824,16 @@ int bdx_run(bdx_ctx* c) {
         // 5.7 MB at a genome share, 0.28 ms of this thread between the join kernel's end and the pair groups' arrival 0.14 ms later; the
         // host's walk of its ~1,200 groups then started late and the device stood idle in front of the table stage.)  A large share
         // (debug "regions_copy" = 1: always) still gets its copy, once the groups have said how large it is.
-        const uint32_t nr_host = c->h_counts0.as<StageCounts>()->n_regions;
+        const uint32_t nr_host = c->sb.h_counts0.as<StageCounts>()->n_regions;
         // (a small table is copied at once, as ever: its copy fits between the join kernel's end and the groups' arrival -- 32 k regions are 70 us)
         const bool copy_first = c->dbg_regions_copy == 1 || (c->dbg_regions_copy == 0 && nr_host < kBorrowRegionsMin);
-        if (copy_first) decode_regions(c, c->h_regs.as<RegionRec>(), c->h_pk.as<uint32_t>(), nr_host, ph, false);
+        if (copy_first) decode_regions(c, c->sb.h_regs.as<RegionRec>(), c->sb.h_pk.as<uint32_t>(), nr_host, ph, false);
         if (!wait_flag(c, 1, c->seq)) {
             if (c->poll) HIPCHK(c, hipStreamSynchronize(s)); else HIPCHK(c, hipEventSynchronize(c->ev_groups));
             if (!flag_arrived(c, 1)) return fail(c, BDX_EINTERNAL, "the pair groups did not arrive: their kernels were not launched");
         }
         c->counts = *c->h_counts.as<StageCounts>();
-        if (!copy_first) decode_regions(c, c->h_regs.as<RegionRec>(), c->h_pk.as<uint32_t>(), nr_host, ph,
+        if (!copy_first) decode_regions(c, c->sb.h_regs.as<RegionRec>(), c->sb.h_pk.as<uint32_t>(), nr_host, ph,
                                         c->dbg_regions_copy == 2 || (uint64_t)c->counts.n_groups * 8 < nr_host);   // (borrowed while the walk touches a fraction of the table:
                                         // a walk of 20 k groups over 15 k regions was 46 us faster on its copy)
         if (c->counts.irregular) {  // a read name seen more than twice: the pair model does not hold (see bdx_walk_reads.cpp)
@@ -1784,7 +1844,7 @@ int bdx_run(bdx_ctx* c) {
             return BDX_OK;
         }
         if (c->counts.overflow) return fail(c, BDX_EINTERNAL, "group list overflow");
-        decode_groups(c, c->h_groups.as<GroupRec>(), c->counts.n_groups, ph);
+        decode_groups(c, c->sb.h_groups.as<GroupRec>(), c->counts.n_groups, ph);
         c->last_big_groups = (int64_t)c->counts.n_groups + c->counts.n_groups_big;  // (the host's share: mostly such components)
     }
     t_h1 = std::chrono::steady_clock::now();
@@ -1866,8 +1926,8 @@ int bdx_stage_regions(bdx_ctx* c, int has_next, int32_t next_qlen, uint32_t next
     if (!c) return BDX_EINVAL;
     if (c->stage < 2) return BDX_ESTATE;
     NOT_WHILE_SIZING(c);
-    BDX_TRY(do_cut(c, has_next, next_qlen, next_nn, false));
-    return readback(c, false);
+    BDX_TRY(do_cut(c, K3Tail{has_next, next_qlen, next_nn, nullptr}, RegionDst::Host));
+    return readback(c);
 }
 
 int bdx_get_stage_regions(const bdx_ctx* c, uint32_t* n_regions, uint32_t* n_anomalous, int32_t* last_maxq) {
@@ -1881,11 +1941,11 @@ int bdx_get_stage_regions(const bdx_ctx* c, uint32_t* n_regions, uint32_t* n_ano
 
 int bdx_get_region_records(const bdx_ctx* c, bdx_region_rec* out, uint32_t* pk, size_t cap) {
     if (!c) return BDX_EINVAL;
-    if (c->stage < 3 || !c->h_regs.p) return BDX_ESTATE;   // (no table yet, or handed back by bdx_trim_results)
+    if (c->stage < 3 || !c->sb.h_regs.p) return BDX_ESTATE;   // (no table yet, or handed back by bdx_trim_results)
     const size_t n = std::min<size_t>(cap, c->counts.n_regions);
     static_assert(sizeof(bdx_region_rec) == sizeof(RegionRec), "region record layout");
-    if (out && n) memcpy(out, c->h_regs.p, n * sizeof(RegionRec));
-    if (pk && n) memcpy(pk, c->h_pk.p, n * 2 * c->nkeys * 4);
+    if (out && n) memcpy(out, c->sb.h_regs.p, n * sizeof(RegionRec));
+    if (pk && n) memcpy(pk, c->sb.h_pk.p, n * 2 * c->nkeys * 4);
     return BDX_OK;
 }
 
@@ -2014,7 +2074,7 @@ int bdx_trim_results(bdx_ctx* c) {
     materialize(c);
     own_borrowed_regions(c);   // (a region table read where the device left it: the getters go on from a copy)
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (PinBuf* b : {&c->h_regs, &c->h_pk, &c->h_groups, &c->h_sv_out, &c->h_lib_index, &c->h_lib_pairs, &c->h_cn_key, &c->h_cn_value, &c->h_ltail_dev}) b->release();
+    for (PinBuf* b : {&c->sb.h_regs, &c->sb.h_pk, &c->sb.h_groups, &c->sb.h_sv_out, &c->sb.h_lib_index, &c->sb.h_lib_pairs, &c->sb.h_cn_key, &c->sb.h_cn_value, &c->sb.h_ltail_dev}) b->release();
     return BDX_OK;
 }
 

@@ -259,7 +259,7 @@ int bam_feed_classifier(bdx_bamdec* d, bool final) {
                     d->presize_thread = std::thread([d, c, prior, device] {
                         const auto t0 = std::chrono::steady_clock::now();
                         int rc = hipSetDevice(device) == hipSuccess ? BDX_OK : BDX_EHIP;
-                        if (rc == BDX_OK) rc = presize_stages(c, (uint32_t)prior);
+                        if (rc == BDX_OK) rc = presize_stages(c, stage_dims(c, (uint32_t)prior));
                         d->presize_rc = rc;
                         d->host_ms[10] = ms_between(t0, std::chrono::steady_clock::now());
                     });

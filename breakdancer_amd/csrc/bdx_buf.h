@@ -75,6 +75,7 @@ struct PinBuf {
     static bool use_registered() { return registered_switch().load(std::memory_order_relaxed); }
     hipError_t ensure(size_t b) {
         if (b <= bytes) return hipSuccess;
+        const bool had = p != nullptr;
         release();
         size_t want = b + b / 8 + 256;
         const auto t0 = std::chrono::steady_clock::now();
@@ -103,7 +104,7 @@ struct PinBuf {
             // hold another context's ready word -- the same sequence number -- and a poll would return before the kernel has run)
             if (e == hipSuccess && want <= ((size_t)1 << 20)) memset(p, 0, want);
         }
-        if (alloc_trace()) fprintf(stderr, "[bdx alloc] pinned %12zu B %8.1f us%s\n", want, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), map_base ? " (registered huge pages)" : "");
+        if (alloc_trace()) fprintf(stderr, "[bdx alloc] pinned %12zu B %8.1f us%s%s\n", want, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), map_base ? " (registered huge pages)" : "", had ? " (regrown: freed first)" : "");
         if (e == hipSuccess) bytes = want; else p = nullptr;
         return e;
     }

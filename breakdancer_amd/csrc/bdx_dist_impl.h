@@ -552,12 +552,10 @@ int bdx_dist_prepare(bdx_dist* d) {
     if (c->n >= (1u << 20) && !c->ran) {
         const uint64_t prior = (uint64_t)c->n / 32 + 4096;
         if (prior <= kMaxAnomalous) {
-            const uint32_t keep = c->k6_cap;
-            c->k6_cap = (uint32_t)std::min<uint64_t>(prior, kMaxRegions);
-            c->table_in_hbm = d->comm->world > 1;
-            c->groups_in_hbm = d->comm->world > 1;
-            const int rc = presize_stages_here(c, (uint32_t)prior);
-            c->k6_cap = keep;
+            StageDims dm = stage_dims(c, (uint32_t)prior);   // (what a run sets on the context at its start: pass1_and_counts, globalize_and_scatter)
+            dm.k6_cap = (uint32_t)std::min<uint64_t>(prior, kMaxRegions);
+            dm.table_in_hbm = dm.groups_in_hbm = d->comm->world > 1;
+            const int rc = presize_stages_here(c, dm);
             if (rc != BDX_OK) return dfail(d, rc, c->err);
             const size_t nr = (size_t)prior;
             DHIP(d, d->b_rg_rec.ensure(nr * sizeof(RegionRec)));
@@ -570,8 +568,8 @@ int bdx_dist_prepare(bdx_dist* d) {
             DHIP(d, d->b_send.ensure(nn * 20 + 4096)); DHIP(d, d->b_recv.ensure(nn * 20 + 4096));   // (a census record of 16 bytes per anomalous read; an eighth of them inter-chromosomal and travelling, 32 bytes each)
             if (d->comm->rank == 0) {   // the genome's region table in pinned memory (regions: about a tenth of the anomalous reads)
                 const size_t nreg = (size_t)c->n / 256 + 4096;
-                DHIP(d, c->h_regs.ensure(nreg * sizeof(RegionRec)));
-                DHIP(d, c->h_pk.ensure(nreg * 2 * d->nkeys * 4));
+                DHIP(d, c->sb.h_regs.ensure(nreg * sizeof(RegionRec)));
+                DHIP(d, c->sb.h_pk.ensure(nreg * 2 * d->nkeys * 4));
             }
         }
     }
@@ -687,8 +685,8 @@ int agreed_failure(bdx_dist* d, const RunStatus& st, const uint64_t* words, int 
 // the result of a rank's context becomes the result context's: the pinned buffers the device assembled the table in change
 // hands (no copy), the counters are taken over
 void swap_table_buffers(bdx_ctx* U, bdx_ctx* C) {
-    std::swap(U->h_sv_out, C->h_sv_out); std::swap(U->h_lib_index, C->h_lib_index); std::swap(U->h_lib_pairs, C->h_lib_pairs);
-    std::swap(U->h_cn_key, C->h_cn_key); std::swap(U->h_cn_value, C->h_cn_value); std::swap(U->h_ltail_dev, C->h_ltail_dev);
+    std::swap(U->sb.h_sv_out, C->sb.h_sv_out); std::swap(U->sb.h_lib_index, C->sb.h_lib_index); std::swap(U->sb.h_lib_pairs, C->sb.h_lib_pairs);
+    std::swap(U->sb.h_cn_key, C->sb.h_cn_key); std::swap(U->sb.h_cn_value, C->sb.h_cn_value); std::swap(U->sb.h_ltail_dev, C->sb.h_ltail_dev);
 }
 void adopt_table(bdx_ctx* U, bdx_ctx* C) {
     swap_table_buffers(U, C);
@@ -974,8 +972,7 @@ int DistRun::begin() {
 int DistRun::pass1_and_counts(std::vector<uint64_t>& v1) {
     C->table_in_hbm = world > 1;
     C->groups_in_hbm = world > 1;
-    C->defer_walk = false;
-    C->k6_cap = 0; C->k6_r_rec = nullptr; C->k6_r_pk = nullptr; C->k6_taint = nullptr; C->k3_tid_tail = nullptr;
+    C->k6_cap = 0; C->k6_r_rec = nullptr; C->k6_r_pk = nullptr; C->k6_taint = nullptr;
     {   // (a set of reads bdx_dist_prepare has not seen: its order is checked before the chromosome table is searched in it)
         const int orc = check_order(d);
         if (orc != BDX_OK) return orc;
@@ -1159,10 +1156,9 @@ int DistRun::cut_regions(const Stats& A, std::vector<uint64_t>& v3) {
     }
     if (!na) return BDX_OK;
     launch_k9_rebase(C->cp, &C->b_p1.as<Pass1>()->n_anom, na, nkeys, T + O.off, nullptr, s);
-    C->k3_tid_tail = T + O.tail;
-    DCTX(d, C, do_cut(C, 0, 0, 0, false, true));
+    DCTX(d, C, do_cut(C, K3Tail{0, 0, 0, T + O.tail}, RegionDst::Hbm));
     trace("region cut");
-    launch_k9_tid_regions(C->b_r_rec.as<RegionRec>(), C->b_counts.as<StageCounts>(), ntids, H + L.rtab, s);
+    launch_k9_tid_regions(C->sb.b_r_rec.as<RegionRec>(), C->b_counts.as<StageCounts>(), ntids, H + L.rtab, s);
     launch_k9_signal(H + 2, d->seq, s);
     if (const int rc = await_word(d, flags + 2, d->seq, s, "the chromosomes' region counts")) return rc;
     memcpy(rtab.data(), H + L.rtab, rtab.size() * 4);
@@ -1248,7 +1244,7 @@ int DistRun::globalize_and_scatter(const Stats& A, const Regions& B, const Excha
     DHIP(d, d->b_recv.ensure(std::max<size_t>(X.rwords, 4) * 8));
     DHIP(d, d->b_rg_rec.ensure((size_t)NR * sizeof(RegionRec)));
     DHIP(d, d->b_rg_pk.ensure(std::max<size_t>((size_t)NR * nkeys2 * 4, 16)));
-    DHIP(d, C->b_out_deg.ensure((size_t)B.capG * 6 * 4));
+    DHIP(d, size_out_deg(C->sb, B.capG));
     DHIP(d, d->b_x.ensure((size_t)B.capG + 64));
     taint = d->b_x.as<uint8_t>();
     DHIP(d, hipMemsetAsync(d->b_rg_rec.p, 0, (size_t)NR * sizeof(RegionRec), s));
@@ -1270,18 +1266,18 @@ int DistRun::globalize_and_scatter(const Stats& A, const Regions& B, const Excha
     }
     GlobalizeParams gp{};
     gp.tid = C->cp.tid; gp.region_of = C->k3.region_of; gp.n_ptr = &C->b_p1.as<Pass1>()->n_anom;
-    gp.r_rec = C->b_r_rec.as<RegionRec>(); gp.r_pk = C->b_r_pk.as<uint32_t>(); gp.nr_local = B.nr_local; gp.roff = T + O.roff;
+    gp.r_rec = C->sb.b_r_rec.as<RegionRec>(); gp.r_pk = C->sb.b_r_pk.as<uint32_t>(); gp.nr_local = B.nr_local; gp.roff = T + O.roff;
     gp.rg_rec = d->b_rg_rec.as<RegionRec>(); gp.rg_pk = d->b_rg_pk.as<uint32_t>(); gp.nkeys2 = nkeys2;
-    gp.scratch = C->b_out_deg.as<uint32_t>(); gp.cap = B.capG; gp.counts = C->b_counts.as<StageCounts>(); gp.nr_global = (uint32_t)NR; gp.last_maxq = B.lm;
+    gp.scratch = C->sb.b_out_deg.as<uint32_t>(); gp.cap = B.capG; gp.counts = C->b_counts.as<StageCounts>(); gp.nr_global = (uint32_t)NR; gp.last_maxq = B.lm;
     launch_k9_globalize(gp, na, s);
     trace("globalize");
     C->k6_cap = (uint32_t)NR; C->k6_r_rec = d->b_rg_rec.as<RegionRec>(); C->k6_r_pk = d->b_rg_pk.as<uint32_t>();
     C->k6_taint = solo ? nullptr : taint;
     if (solo && rank == 0) {   // one rank: the genome's table is this rank's -- to pinned memory beside the joins, for the host's share of the walk and the result
-        if (C->h_regs.ensure((size_t)NR * sizeof(RegionRec)) != hipSuccess || C->h_pk.ensure(std::max<size_t>((size_t)NR * nkeys2 * 4, 16)) != hipSuccess)
+        if (C->sb.h_regs.ensure((size_t)NR * sizeof(RegionRec)) != hipSuccess || C->sb.h_pk.ensure(std::max<size_t>((size_t)NR * nkeys2 * 4, 16)) != hipSuccess)
             return dfail(d, BDX_ENOMEM, "region table");
-        regs = C->h_regs.as<RegionRec>();
-        pk = C->h_pk.as<uint32_t>();
+        regs = C->sb.h_regs.as<RegionRec>();
+        pk = C->sb.h_pk.as<uint32_t>();
         DHIP(d, hipEventRecord(C->ev_copy, s));
         DHIP(d, hipStreamWaitEvent(C->copy_stream, C->ev_copy, 0));
         static_assert(sizeof(RegionRec) % 4 == 0, "copied by words");
@@ -1354,8 +1350,9 @@ int DistRun::join_walk_table(const Stats& A, const Regions& B, const ExchangePla
     }
     trace("join");
     t_x1 = now();
-    DCTX(d, C, do_k6(C, force_host(), 1));
-    DCTX(d, C, do_k6(C, force_host(), 2));   // (components and, right behind them, the device's walk)
+    DCTX(d, C, k6_prepare(C, force_host(), 0));
+    k6_pairs(C);
+    DCTX(d, C, k6_then_walk(C, launch_k6_components));   // (components and, right behind them, the device's walk)
     trace("components and walk");
     if (solo && rank == 0) {   // one rank: its host walks what the device walk leaves, as in bdx_run -- on the table that went to pinned memory beside the joins
         DHIP(d, hipStreamSynchronize(C->copy_stream));
@@ -1380,7 +1377,7 @@ int DistRun::join_walk_table(const Stats& A, const Regions& B, const ExchangePla
     if (*irregular || A.want_support != 0 || phantom(A) != 0) return BDX_OK;   // (the table of this model is not wanted)
     C->walk.clear();
     if (solo && rank == 0) {
-        decode_groups(C, C->h_groups.as<GroupRec>(), C->counts.n_groups, 0);
+        decode_groups(C, C->sb.h_groups.as<GroupRec>(), C->counts.n_groups, 0);
         C->last_big_groups = (int64_t)C->counts.n_groups + C->counts.n_groups_big;
         const auto tw0 = now();
         DCTX(d, C, host_walk(C, B.lm, A.na_all != 0));
@@ -1424,18 +1421,18 @@ int DistRun::place_regions(const Regions& B, const std::vector<size_t>& displ, b
         D.p[q] = GatherPackage{displ[q], displ[q] + nr * rrec, 0, (uint32_t)nr, 0};
         max_nr = std::max(max_nr, (uint32_t)nr);
     }
-    if (C->h_regs.ensure((size_t)NR * rrec) != hipSuccess || C->h_pk.ensure(std::max<size_t>((size_t)NR * rpk, 16)) != hipSuccess) return dfail(d, BDX_ENOMEM, "region table");
-    regs = C->h_regs.as<RegionRec>();
-    pk = C->h_pk.as<uint32_t>();
-    if (U->b_r_rec.ensure((size_t)NR * rrec) != hipSuccess || U->b_r_pk.ensure(std::max<size_t>((size_t)NR * rpk, 16)) != hipSuccess) return dfail(d, BDX_ENOMEM, "region table");
+    if (C->sb.h_regs.ensure((size_t)NR * rrec) != hipSuccess || C->sb.h_pk.ensure(std::max<size_t>((size_t)NR * rpk, 16)) != hipSuccess) return dfail(d, BDX_ENOMEM, "region table");
+    regs = C->sb.h_regs.as<RegionRec>();
+    pk = C->sb.h_pk.as<uint32_t>();
+    if (U->sb.b_r_rec.ensure((size_t)NR * rrec) != hipSuccess || U->sb.b_r_pk.ensure(std::max<size_t>((size_t)NR * rpk, 16)) != hipSuccess) return dfail(d, BDX_ENOMEM, "region table");
     DHIP(d, hipMemcpyAsync(T + O.rbase, B.rbase.data(), ((size_t)ntids + 1) * 8, hipMemcpyHostToDevice, s));
-    launch_k8_place_regions((const char*)d->b_all.p, D, max_nr, (const uint64_t*)(T + O.rbase), ntids, nkeys2, U->b_r_rec.as<RegionRec>(), U->b_r_pk.as<uint32_t>(),
+    launch_k8_place_regions((const char*)d->b_all.p, D, max_nr, (const uint64_t*)(T + O.rbase), ntids, nkeys2, U->sb.b_r_rec.as<RegionRec>(), U->sb.b_r_pk.as<uint32_t>(),
                             T + O.ntot + 1, s);
     DHIP(d, hipEventRecord(C->ev_copy, s));
     DHIP(d, hipStreamWaitEvent(C->copy_stream, C->ev_copy, 0));
     UploadList ul{};
-    ul.copy(regs, U->b_r_rec.p, (size_t)NR * rrec / 4);
-    if (nkeys2 && with_pk) ul.copy(pk, U->b_r_pk.p, (size_t)NR * rpk / 4);   // (without: the rows the host's walk touches follow, launch_k9_pk_rows)
+    ul.copy(regs, U->sb.b_r_rec.p, (size_t)NR * rrec / 4);
+    if (nkeys2 && with_pk) ul.copy(pk, U->sb.b_r_pk.p, (size_t)NR * rpk / 4);   // (without: the rows the host's walk touches follow, launch_k9_pk_rows)
     launch_k9_upload(ul, C->copy_stream);
     regs_pending = true;
     return BDX_OK;
@@ -1453,8 +1450,8 @@ int DistRun::wait_regions() {
 // this rank's region records and their prefix samples, one after the other, at dst (device memory)
 bool DistRun::pack_regions(const Regions& B, char* dst) {
     if (!B.nr_local) return true;
-    return hipMemcpyAsync(dst, C->b_r_rec.p, (size_t)B.nr_local * rrec, hipMemcpyDeviceToDevice, s) == hipSuccess &&
-           hipMemcpyAsync(dst + (size_t)B.nr_local * rrec, C->b_r_pk.p, (size_t)B.nr_local * rpk, hipMemcpyDeviceToDevice, s) == hipSuccess;
+    return hipMemcpyAsync(dst, C->sb.b_r_rec.p, (size_t)B.nr_local * rrec, hipMemcpyDeviceToDevice, s) == hipSuccess &&
+           hipMemcpyAsync(dst + (size_t)B.nr_local * rrec, C->sb.b_r_pk.p, (size_t)B.nr_local * rpk, hipMemcpyDeviceToDevice, s) == hipSuccess;
 }
 
 // ---- a read name seen more than twice (clashing names across merged files): the pair model does not hold, and the reference's
@@ -1516,8 +1513,8 @@ int DistRun::replay_route(const Stats& A, const Regions& B, const Summary& S) {
             if (A.want_support) sidx[o] = A.read_base[t] + rp_host[i * kw + 4];
         }
         if (solo && !regs) {   // (one rank: its table went to pinned memory beside the walk)
-            if (C->h_regs.ensure((size_t)NR * rrec) != hipSuccess || C->h_pk.ensure(std::max<size_t>((size_t)NR * rpk, 16)) != hipSuccess) return dfail(d, BDX_ENOMEM, "region table");
-            regs = C->h_regs.as<RegionRec>(); pk = C->h_pk.as<uint32_t>();
+            if (C->sb.h_regs.ensure((size_t)NR * rrec) != hipSuccess || C->sb.h_pk.ensure(std::max<size_t>((size_t)NR * rpk, 16)) != hipSuccess) return dfail(d, BDX_ENOMEM, "region table");
+            regs = C->sb.h_regs.as<RegionRec>(); pk = C->sb.h_pk.as<uint32_t>();
             DHIP(d, hipMemcpy(regs, d->b_rg_rec.p, (size_t)NR * rrec, hipMemcpyDeviceToHost));
             if (nkeys2) DHIP(d, hipMemcpy(pk, d->b_rg_pk.p, (size_t)NR * rpk, hipMemcpyDeviceToHost));
         }
@@ -1602,10 +1599,10 @@ int DistRun::pack_and_gather(const Regions& B, const Summary& S, const Packages&
     bool good = pack_regions(B, (char*)d->b_pack.p);
     auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes && good) good = hipMemcpyAsync(pp + off, src, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess; };
     put(G.grp_off[rank], C->k4.g_rec, (size_t)S.of_rank[rank].n_groups * sizeof(GroupRec));
-    put(P.rows_off, C->b_sv_out.p, (size_t)P.n_sv * sizeof(SvOut)); put(P.keys_off, C->b_sv_key.p, (size_t)P.n_sv * 8);
-    put(P.lib_index_off, C->b_lib_index_out.p, (size_t)P.n_terms * 4); put(P.lib_pairs_off, C->b_lib_pairs_out.p, (size_t)P.n_terms * 4);
-    put(P.ltail_off, C->b_ltail_out.p, (size_t)P.n_terms * 8);
-    put(P.cn_key_off, C->b_cn_key_out.p, (size_t)P.n_cn * 4); put(P.cn_value_off, C->b_cn_value_out.p, (size_t)P.n_cn * 4);
+    put(P.rows_off, C->sb.b_sv_out.p, (size_t)P.n_sv * sizeof(SvOut)); put(P.keys_off, C->sb.b_sv_key.p, (size_t)P.n_sv * 8);
+    put(P.lib_index_off, C->sb.b_lib_index_out.p, (size_t)P.n_terms * 4); put(P.lib_pairs_off, C->sb.b_lib_pairs_out.p, (size_t)P.n_terms * 4);
+    put(P.ltail_off, C->sb.b_ltail_out.p, (size_t)P.n_terms * 8);
+    put(P.cn_key_off, C->sb.b_cn_key_out.p, (size_t)P.n_cn * 4); put(P.cn_value_off, C->sb.b_cn_value_out.p, (size_t)P.n_cn * 4);
     if (!good) return dfail(d, BDX_EHIP, "package for rank 0");
     trace("package");
     if (rank == 0 && d->b_all.ensure(std::max<size_t>(G.pbytes, 8)) != hipSuccess) return dfail(d, BDX_ENOMEM, "gather buffer");
@@ -1625,8 +1622,8 @@ int DistRun::result_as_k6_context(const Regions& B, uint32_t ng, const GroupRec*
     hipStream_t su = U->stream;
     DHIP(d, U->b_counts.ensure(sizeof(StageCounts))); DHIP(d, U->h_counts.ensure(sizeof(StageCounts)));
     DHIP(d, U->b_cnt.ensure((size_t)ncnt * 4)); DHIP(d, U->b_p1.ensure(sizeof(Pass1))); DHIP(d, U->b_kdens.ensure(64 * 4));
-    DHIP(d, U->h_flags.ensure(64)); DHIP(d, U->h_groups.ensure(((size_t)ng + 1) * sizeof(GroupRec)));
-    if (in_groups) DHIP(d, U->b_out_deg.ensure((size_t)capU * 6 * 4));
+    DHIP(d, U->h_flags.ensure(64)); DHIP(d, U->sb.h_groups.ensure(((size_t)ng + 1) * sizeof(GroupRec)));
+    if (in_groups) DHIP(d, size_out_deg(U->sb, capU));
     {
         StageCounts sc{};
         sc.n_regions = nr; sc.last_maxq = B.lm;
@@ -1639,14 +1636,14 @@ int DistRun::result_as_k6_context(const Regions& B, uint32_t ng, const GroupRec*
         ul.copy(U->b_kdens.p, st_up + 2 + ncnt, U->key_density.size());
         launch_k9_upload(ul, su);
     }
-    if (in_groups) launch_k6_scratch_init(U->b_out_deg.as<uint32_t>(), capU, su);
+    if (in_groups) launch_k6_scratch_init(U->sb.b_out_deg.as<uint32_t>(), capU, su);
     ++U->seq;
     U->na_alloc = 0; U->k6_cap = capU;
-    U->k6_r_rec = U->b_r_rec.as<RegionRec>(); U->k6_r_pk = U->b_r_pk.as<uint32_t>(); U->k6_taint = nullptr;
+    U->k6_r_rec = U->sb.b_r_rec.as<RegionRec>(); U->k6_r_pk = U->sb.b_r_pk.as<uint32_t>(); U->k6_taint = nullptr;
     U->k6_in_groups = in_groups; U->k6_in_goff = in_goff;
     U->cp = Compact{}; U->k3 = K3Arrays{}; U->k4 = K4Arrays{};
-    U->k4.g_rec = U->h_groups.as<GroupRec>(); U->k4.g_cap = ng + 1;
-    U->table_in_hbm = true; U->groups_in_hbm = false; U->defer_walk = false;
+    U->k4.g_rec = U->sb.h_groups.as<GroupRec>(); U->k4.g_cap = ng + 1;
+    U->table_in_hbm = true; U->groups_in_hbm = false;
     memset(&U->counts, 0, sizeof(U->counts));
     return BDX_OK;
 }
@@ -1665,9 +1662,9 @@ int DistRun::walk_gathered(const Stats& A, const Regions& B, const Summary& S, c
     uint32_t* bucket_err = nullptr;   // (device walk: the bucket kernel's verdict)
     if (host_gather) {
         // the gathered groups: out of every rank's package into pinned memory, behind the gather
-        DHIP(d, U->h_groups.ensure(((size_t)ng + 1) * sizeof(GroupRec)));
+        DHIP(d, U->sb.h_groups.ensure(((size_t)ng + 1) * sizeof(GroupRec)));
         {
-            GroupRec* hg = U->h_groups.as<GroupRec>();
+            GroupRec* hg = U->sb.h_groups.as<GroupRec>();
             size_t at = 0;
             for (int q = 0; q < world; ++q) {
                 const size_t nq = (size_t)S.of_rank[q].n_groups;
@@ -1678,7 +1675,7 @@ int DistRun::walk_gathered(const Stats& A, const Regions& B, const Summary& S, c
         DHIP(d, hipEventRecord(d->ev_side, s));   // (the gather, the region table placed behind it, the groups' copies)
         DHIP(d, hipStreamWaitEvent(su, d->ev_side, 0));
         if (const int rc = result_as_k6_context(B, ng, nullptr, nullptr)) return rc;
-        DCTX(d, U, do_k6(U, false, 4));   // (K6's arrays, no launch: the table stage below finds no candidate of the device's; NOT force_host -- that zeroes
+        DCTX(d, U, k6_prepare(U, false, 0));   // (K6's arrays, no launch: the table stage below finds no candidate of the device's; NOT force_host -- that zeroes
                                           // the host candidates' order keys, which the merge of the ranks' tables goes by)
         DHIP(d, hipMemsetAsync(U->k6.own_nsv, 0, (size_t)U->k6_cap * 3 * 4, su));   // own_nsv | own_nacc | own_ncn: no vertex has candidates of its own
         DHIP(d, hipStreamSynchronize(s));   // (the groups are in pinned memory)
@@ -1706,17 +1703,18 @@ int DistRun::walk_gathered(const Stats& A, const Regions& B, const Summary& S, c
         // (components that span ranks are mostly a translocation's two regions and their neighbours: three rounds of label propagation settle
         // them -- the eight of a context that walks large components are seven launches on rank 0's own part of the run; what has not
         // converged fails the closure check and is the host's)
-        DCTX(d, U, do_k6(U, force_host(), 0, nullptr, kK6LabelRoundsGather));
+        DCTX(d, U, k6_prepare(U, force_host(), kK6LabelRoundsGather));
+        DCTX(d, U, k6_then_walk(U, launch_k6_groups));
         if (const int rc = await_flag(d, U, 1, su, nullptr, "the pair groups of the gathered components")) return rc;
         U->counts = *U->h_counts.as<StageCounts>();
         if (U->counts.overflow) return dfail(d, BDX_EINTERNAL, "group list overflow (gathered components)");
     }
-    decode_groups(U, U->h_groups.as<GroupRec>(), U->counts.n_groups, 0);
+    decode_groups(U, U->sb.h_groups.as<GroupRec>(), U->counts.n_groups, 0);
     U->last_big_groups = (int64_t)U->counts.n_groups + U->counts.n_groups_big;
     if (U->counts.n_groups) {   // (the host's share of this walk reads the table in pinned memory: its copy ran beside the device's walk)
         // ... and the proper-read samples of the regions its groups name: those rows only
         // (on the stream of the table's copy, behind it: the result context's own stream is still walking)
-        launch_k9_pk_rows(U->h_groups.as<GroupRec>(), U->counts.n_groups, U->b_r_pk.as<uint32_t>(), pk, (uint32_t)nkeys2, nr, C->copy_stream);
+        launch_k9_pk_rows(U->sb.h_groups.as<GroupRec>(), U->counts.n_groups, U->sb.b_r_pk.as<uint32_t>(), pk, (uint32_t)nkeys2, nr, C->copy_stream);
         regs_pending = true;
         if (const int rc = wait_regions()) return rc;
     }
@@ -1739,8 +1737,8 @@ int DistRun::walk_gathered(const Stats& A, const Regions& B, const Summary& S, c
     TablePackage& P = *table;   // the table of the gathered components, where the result context's K6 left it (byte offsets relative to the gather buffer)
     P.n_sv = (uint32_t)walked->n_sv; P.n_terms = (uint32_t)walked->n_terms; P.n_cn = (uint32_t)walked->n_cn;
     auto off = [&](const DevBuf& b) { return (uint64_t)((uintptr_t)b.p - (uintptr_t)d->b_all.p); };
-    P.rows_off = off(U->b_sv_out); P.keys_off = off(U->b_sv_key); P.lib_index_off = off(U->b_lib_index_out); P.lib_pairs_off = off(U->b_lib_pairs_out);
-    P.ltail_off = off(U->b_ltail_out); P.cn_key_off = off(U->b_cn_key_out); P.cn_value_off = off(U->b_cn_value_out);
+    P.rows_off = off(U->sb.b_sv_out); P.keys_off = off(U->sb.b_sv_key); P.lib_index_off = off(U->sb.b_lib_index_out); P.lib_pairs_off = off(U->sb.b_lib_pairs_out);
+    P.ltail_off = off(U->sb.b_ltail_out); P.cn_key_off = off(U->sb.b_cn_key_out); P.cn_value_off = off(U->sb.b_cn_value_out);
     DHIP(d, hipEventRecord(d->ev_side, U->stream));   // (its table kernel: finish_table has seen its ready word, this orders the streams)
     DHIP(d, hipStreamWaitEvent(s, d->ev_side, 0));
     return BDX_OK;
@@ -1760,10 +1758,10 @@ int DistRun::merge_tables(const Regions& B, const Packages& G, const TableCounts
     }
     const uint32_t n_total = (uint32_t)all.n_sv;
     const uint64_t n_terms_all = all.n_terms, n_cn_all = all.n_cn;
-    DHIP(d, U->h_sv_out.ensure(std::max<size_t>(n_total, 1) * sizeof(SvOut)));
-    DHIP(d, U->h_lib_index.ensure(std::max<size_t>(n_terms_all, 1) * 4)); DHIP(d, U->h_lib_pairs.ensure(std::max<size_t>(n_terms_all, 1) * 4));
-    DHIP(d, U->h_ltail_dev.ensure(std::max<size_t>(n_terms_all, 1) * 8));
-    DHIP(d, U->h_cn_key.ensure(std::max<size_t>(n_cn_all, 1) * 4 + 16)); DHIP(d, U->h_cn_value.ensure(std::max<size_t>(n_cn_all, 1) * 4 + 16));
+    DHIP(d, U->sb.h_sv_out.ensure(std::max<size_t>(n_total, 1) * sizeof(SvOut)));
+    DHIP(d, U->sb.h_lib_index.ensure(std::max<size_t>(n_terms_all, 1) * 4)); DHIP(d, U->sb.h_lib_pairs.ensure(std::max<size_t>(n_terms_all, 1) * 4));
+    DHIP(d, U->sb.h_ltail_dev.ensure(std::max<size_t>(n_terms_all, 1) * 8));
+    DHIP(d, U->sb.h_cn_key.ensure(std::max<size_t>(n_cn_all, 1) * 4 + 16)); DHIP(d, U->sb.h_cn_value.ensure(std::max<size_t>(n_cn_all, 1) * 4 + 16));
     if (n_total) {
         const size_t ws_words = ((size_t)scan_grid(n_total) + 4) * 4;
         DHIP(d, d->b_merge.ensure((size_t)n_total * 12 + ws_words * 4 + sizeof(TableDesc) + 128));
@@ -1773,8 +1771,8 @@ int DistRun::merge_tables(const Regions& B, const Packages& G, const TableCounts
         TableDesc* d_td = (TableDesc*)(((uintptr_t)(ws + ws_words) + 15) & ~(uintptr_t)15);
         DHIP(d, hipMemcpyAsync(d_td, &TD, sizeof(TableDesc), hipMemcpyHostToDevice, s));
         DHIP(d, hipMemcpyAsync(T + O.ntot + 2, &n_total, 4, hipMemcpyHostToDevice, s));
-        MergeOut mo{U->h_sv_out.as<SvOut>(), U->h_lib_index.as<int32_t>(), U->h_lib_pairs.as<int32_t>(), d->opts.fisher ? U->h_ltail_dev.as<double>() : nullptr,
-                    U->h_cn_key.as<int32_t>(), U->h_cn_value.as<float>()};
+        MergeOut mo{U->sb.h_sv_out.as<SvOut>(), U->sb.h_lib_index.as<int32_t>(), U->sb.h_lib_pairs.as<int32_t>(), d->opts.fisher ? U->sb.h_ltail_dev.as<double>() : nullptr,
+                    U->sb.h_cn_key.as<int32_t>(), U->sb.h_cn_value.as<float>()};
         if (dist_tracing()) {   // are the ranks' tables sorted by key, and are the keys distinct?
             DHIP(d, hipStreamSynchronize(s));
             for (int q = 0; q < TD.world; ++q) {
