@@ -89,6 +89,8 @@ struct bdx_ctx {
     PinBuf h_hs_rec, h_hs_aux, h_hs_lists, h_printed;
     StageBufs sb;                     // K2 .. K6: what a sizing pass grows
     PinBuf h_flags;                   // [0] pass 1 ready, [1] host's groups ready, [2] final table ready, [3] region table ready (= run sequence number)
+    PinBuf h_count;                   // [kMaxChunks] 64-bit words: finalize_kernel's chunk totals of anomalous reads, each stamped with the run sequence number
+                                      // in its high half (FinalizeParams::count_host; read by wait_count)
     uint32_t seq = 0;
     // test / measurement switches (bdx_set_debug): all off by default
     int dbg_no_stash = 0, dbg_max_chunks = 0, dbg_ins_plain = 0, dbg_gather_walk = 0, dbg_regions_copy = 0, dbg_asm_plain = 0;
@@ -167,6 +169,7 @@ struct bdx_ctx {
     int spec_test = 0;                // BDX_SPEC_TEST=1: guess half of the last count (forces the retry path)
     uint32_t last_na = 0;
     size_t last_n = 0;
+    uint32_t count_chunks = 0;        // words of h_count the pass 1 in flight posts (0: none, the count comes with the record)
     uint32_t na_alloc = 0;            // the count the later stages are sized and launched with
     bool region_of_fused = false;
     uint32_t join_table_clean = 0;    // slots of the direct join table already set to -1 (by K2), 0 = none
@@ -620,6 +623,27 @@ bool wait_flag(const bdx_ctx* c, int idx, uint32_t value) {
     }
 }
 
+// The count of anomalous reads, ahead of the pass-1 record: finalize_kernel's chunk totals, posted while finalize2_kernel has yet to
+// run.  Every word carries the run's sequence number in its high half, so a word of an earlier run (or of the launch a too-small guess
+// repeated) does not pass for this one's.  false: not posted, polling off or not there in time -- the caller waits for the record.
+bool wait_count(const bdx_ctx* c, uint64_t* n_anom) {
+    if (!c->poll || !c->h_count.p || !c->count_chunks) return false;
+    const volatile uint64_t* w = (const volatile uint64_t*)c->h_count.p;
+    const uint32_t nchunk = c->count_chunks;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t sum = 0;
+    uint32_t g = 0;
+    for (uint32_t spin = 0; g < nchunk; ++spin) {
+        const uint64_t v = w[g];   // (one aligned 8-byte load: value and stamp together)
+        if ((uint32_t)(v >> 32) == c->seq) { sum += (uint32_t)v; ++g; continue; }
+        __builtin_ia32_pause();
+        if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return false;
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    *n_anom = sum;
+    return true;
+}
+
 // behind a poll that timed out and a stream that has drained: was the word written at all?  (A kernel that was never launched -- a
 // launch that failed, a stage that returned early -- leaves zeros where its results should be; they must not pass for an empty input.)
 bool flag_arrived(const bdx_ctx* c, int idx) {
@@ -650,7 +674,8 @@ float ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_cl
 }
 
 // K1 + finalize: class bytes, per-tile tables, *local* pass-1 counters
-int do_pass1(bdx_ctx* c, uint32_t na_cap = 0, bool wait = true, bool defer_second = false);
+// post_count: finalize_kernel also posts the chunk totals of anomalous reads to h_count (the caller reads them with wait_count)
+int do_pass1(bdx_ctx* c, uint32_t na_cap = 0, bool wait = true, bool defer_second = false, bool post_count = false);
 int wait_pass1(bdx_ctx* c);
 
 
@@ -773,6 +798,7 @@ int pass1_prepare(bdx_ctx* c, uint32_t tiles_cap) {
     HIPCHK(c, c->h_cnt.ensure((size_t)ncnt * 4));
     HIPCHK(c, c->h_counts.ensure(sizeof(StageCounts)));
     HIPCHK(c, c->b_counts.ensure(sizeof(StageCounts)));
+    HIPCHK(c, c->h_count.ensure((size_t)kMaxChunks * 8));
     const size_t w_tot = (size_t)ncols * tstride, w_mono = (size_t)nbams * tstride * sizeof(MonoRec) / 4;
     if (w_tot > 0xFFFFFFFFull || w_mono > 0xFFFFFFFFull) {  // beyond the init kernel's 32-bit word counts
         HIPCHK(c, hipMemsetAsync(c->b_tile_tot.p, 0, w_tot * 4, s));
@@ -809,7 +835,7 @@ int pass1_classify(bdx_ctx* c, uint32_t upto, bool timed) {
     return BDX_OK;
 }
 
-int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second) {
+int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second, bool post_count) {
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int nlibs = c->nlibs, nbams = c->nbams, nkeys = c->nkeys;
@@ -873,6 +899,8 @@ int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second) {
     ++c->seq;
     fp.flag_host = c->h_flags.as<uint32_t>(); fp.flag_value = c->seq;
     fp.na_cap = na_cap;
+    fp.count_host = post_count && c->poll ? c->h_count.as<uint64_t>() : nullptr; fp.count_stamp = c->seq;
+    c->count_chunks = fp.count_host ? fp.nchunk : 0;
     // enqueue-ahead: K2 follows without a host decision in between, so its launch takes the one-workgroup second level along
     c->fp_deferred = fp;
     c->finalize2_deferred = defer_second;
@@ -1797,9 +1825,28 @@ int bdx_run(bdx_ctx* c) {
             BDX_TRY(enqueue_middle());
         }
     } else {
-        BDX_TRY(do_pass1(c));
-        BDX_TRY(set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false));
-        BDX_TRY(enqueue_middle());
+        // exact sizing: the later stages are sized and launched from the count finalize_kernel posts, while finalize2_kernel still runs;
+        // the record and what the host derives from it come behind the launches
+        BDX_TRY(do_pass1(c, 0, /*wait=*/false, false, /*post_count=*/true));
+        uint64_t count = 0;
+        if (wait_count(c, &count)) {
+            if (count > kMaxAnomalous) {
+                HIPCHK(c, hipStreamSynchronize(s));
+                return fail(c, BDX_ELIMIT, "more than 2^31 anomalous reads in one context");
+            }
+            if (count) c->na_alloc = (uint32_t)std::min<uint64_t>(count + count / 8 + 1024, kMaxAnomalous);
+            BDX_TRY(enqueue_middle());
+            BDX_TRY(wait_pass1(c));
+            if (c->p1.n_anom != count) {
+                HIPCHK(c, hipStreamSynchronize(s));
+                return fail(c, BDX_EINTERNAL, "the count of anomalous reads posted ahead of the pass-1 record differs from the record's");
+            }
+            BDX_TRY(set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false));
+        } else {  // (polling off, or the words did not arrive in time: the record first)
+            BDX_TRY(wait_pass1(c));
+            BDX_TRY(set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false));
+            BDX_TRY(enqueue_middle());
+        }
     }
     c->last_n = c->n;
     c->last_na = c->p1.n_anom;

@@ -104,6 +104,11 @@ struct FinalizeParams {
     float* key_density;         // [nkeys]; may be null
     uint32_t* flag_host;        // pinned word set to flag_value once the mirrors are written (the host polls it); may be null
     uint32_t flag_value;
+    uint64_t* count_host;       // pinned [kMaxChunks], may be null: the workgroup that scans chunk g of column kColAnom stores
+                                // (count_stamp << 32 | the chunk's total) to word g as soon as it knows it -- one plain aligned 8-byte
+                                // store, value and stamp in one word -- so that the host can size and launch the later stages while
+                                // the second level still runs
+    uint32_t count_stamp;
     uint32_t na_cap;            // 0, or the capacity the later stages were already enqueued with: if there are more anomalous
                                 // reads, the device copy of n_anom is zeroed (they then do nothing) and the host, which still
                                 // gets the true count, runs them again

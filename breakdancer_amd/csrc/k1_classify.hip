@@ -716,6 +716,10 @@ __global__ __launch_bounds__(kFinBlock) void finalize_kernel(const FinalizeParam
         __shared__ uint32_t s_wt[kQ * (kFinBlock / 64)];
         __shared__ uint32_t s_round;
         const uint32_t row_hi = min(p.tstride, (g + 1) * p.chunk_super * kK2TilesPerWave);  // (rows are padded to a multiple of 16 and zero-filled)
+        // The chunk's count of anomalous reads goes to the host the moment it is known (FinalizeParams::count_host): no atomic, no
+        // ticket, no fence -- a fence behind K1's dirty class bytes is what made the folded second level 16 us slower.
+        volatile uint64_t* const count_word = (c == kColAnom && t == 0 && p.count_host) ? p.count_host + g : nullptr;
+        if (count_word && tile_lo >= tile_hi) *count_word = (uint64_t)p.count_stamp << 32;  // (an input without reads: no round at all)
         for (uint32_t base = tile_lo; base < tile_hi; base += kFinBlock * kQ * 4) {
             uint32_t sum[kQ], inc[kQ];
 #pragma unroll
@@ -741,6 +745,8 @@ __global__ __launch_bounds__(kFinBlock) void finalize_kernel(const FinalizeParam
                 if (lane == 63) s_round = li;
             }
             __syncthreads();
+            // (the last round: the total is complete before this round's prefixes are stored)
+            if (count_word && tile_hi - base <= (uint32_t)(kFinBlock * kQ * 4)) *count_word = ((uint64_t)p.count_stamp << 32) | (uint32_t)(s_carry + s_round);
 #pragma unroll
             for (int q = 0; q < kQ; ++q) {
                 const uint32_t i = base + ((uint32_t)q * kFinBlock + t) * 4;

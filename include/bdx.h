@@ -239,7 +239,8 @@ int bdx_set_stage_timing(bdx_ctx* ctx, int on);
  *   2 (default)  the guess is the previous run's count where this context has just run an input of the same size,
  *                otherwise a prior of 1/32 of the reads (inputs of a million reads or more)
  *   1            always the prior: every bdx_run behaves like a first run of its input (what bench.py times)
- *   0            off: wait for the pass-1 record, then size exactly */
+ *   0            off: wait for pass 1's exact count of anomalous reads, then size and launch (the count reaches the host
+ *                ahead of the rest of the pass-1 record, which the host takes behind the launches) */
 int bdx_set_enqueue_ahead(bdx_ctx* ctx, int on);
 
 /* Where the SV candidates of the last bdx_run were assembled.  Components of the region graph that are one region, or
