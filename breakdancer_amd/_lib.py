@@ -50,8 +50,7 @@ SV_DTYPE = np.dtype([("chr", "<i4", 2), ("pos", "<i4", 2), ("fwd", "<i4", 2), ("
 EXPORTS = ["bdx_opts_default", "bdx_create", "bdx_destroy", "bdx_strerror", "bdx_last_error", "bdx_reserve", "bdx_push",
            "bdx_set_device_reads", "bdx_run", "bdx_get_summary", "bdx_get_counters", "bdx_get_regions", "bdx_get_svs",
            "bdx_get_sv_lists", "bdx_get_read_class", "bdx_get_timings", "bdx_classify", "bdx_poisson_log_upper_tail",
-           "bdx_device", "bdx_stream", "bdx_stage_pass1", "bdx_get_pass1_local", "bdx_set_pass1_global", "bdx_stage_compact", "bdx_stage_regions",
-           "bdx_get_stage_regions", "bdx_get_region_records", "bdx_get_compact", "bdx_join_entries", "bdx_stage_walk", "bdx_set_collect_support", "bdx_get_sv_support",
+           "bdx_device", "bdx_stream", "bdx_set_collect_support", "bdx_get_sv_support",
            "bdx_set_host_walk", "bdx_set_debug", "bdx_use_name_check", "bdx_run_many", "bdx_get_walk_split", "bdx_trim_results", "bdx_set_stage_timing", "bdx_get_cross_window_svs",
            "bdx_set_enqueue_ahead", "bdx_was_replayed", "bdx_acquire_batch", "bdx_submit_batch", "bdx_reset_reads", "bdx_set_pass1_statistics",
            "bdx_warm_up", "bdx_set_process_option", "bdx_dist_unique_id", "bdx_dist_create", "bdx_dist_create_threads", "bdx_dist_destroy", "bdx_dist_last_error", "bdx_dist_rank",
@@ -67,10 +66,6 @@ DUP_T = 64
 # bdx_site: 1-based positions, (tid1, pos1) <= (tid2, pos2); bit f of flag_mask: ReadFlag f supports the site
 SITE_DTYPE = np.dtype([("tid1", "<i4"), ("pos1", "<i4"), ("tid2", "<i4"), ("pos2", "<i4"), ("flag_mask", "<u4")])
 SITE_FLAGS = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 5) | (1 << 8)   # BDX_SITE_FLAGS: the anomalous classes
-
-REGION_REC_DTYPE = np.dtype([("tid", "<i4"), ("start", "<i4"), ("end", "<i4"), ("n_reads", "<u4"), ("rev_reads", "<u4"),
-                             ("nonctx_reads", "<u4"), ("normal_read_pairs", "<u4"), ("max_qlen", "<i4"), ("first_read", "<u4")])
-GROUP_DTYPE = np.dtype([("key", "<u8"), ("pairs", "<u4"), ("sum_isize", "<u4")])
 
 _lib = None
 
@@ -124,16 +119,6 @@ def load():
     L.bdx_device.argtypes = [vp]
     L.bdx_stream.argtypes = [vp]
     L.bdx_stream.restype = vp
-    L.bdx_stage_pass1.argtypes = [vp]
-    L.bdx_get_pass1_local.argtypes = [vp, vp, vp, vp]
-    L.bdx_set_pass1_global.argtypes = [vp, vp, C.c_uint32, C.c_int32]
-    L.bdx_stage_compact.argtypes = [vp, C.c_uint32, vp, vp, vp]
-    L.bdx_stage_regions.argtypes = [vp, C.c_int, C.c_int32, C.c_uint32]
-    L.bdx_get_stage_regions.argtypes = [vp, vp, vp, vp]
-    L.bdx_get_region_records.argtypes = [vp, vp, vp, C.c_size_t]
-    L.bdx_get_compact.argtypes = [vp, vp, vp, vp, vp, C.c_size_t]
-    L.bdx_join_entries.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
-    L.bdx_stage_walk.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_int32, C.c_int]
     L.bdx_set_collect_support.argtypes = [vp, C.c_int]
     L.bdx_get_sv_support.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
     L.bdx_count_junction_pairs.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_int, vp]

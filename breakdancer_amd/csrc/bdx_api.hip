@@ -83,7 +83,6 @@ struct bdx_ctx {
 
     // stage buffers
     DevBuf b_libs, b_cls, b_tile_tot, b_tile_pre, b_tile_mono, b_blk_cnt, b_cnt, b_p1, b_fold, b_stash, b_chunk_tot, b_counts;
-    DevBuf b_x_key, b_x_check, b_x_order, b_x_region, b_x_meta, b_x_isize, b_x_n;
     DevBuf b_lib_mean, b_kdens;
     PinBuf h_p1, h_cnt, h_counts, h_terms;
     PinBuf h_hs_rec, h_hs_aux, h_hs_lists, h_printed;
@@ -129,8 +128,6 @@ struct bdx_ctx {
     std::vector<uint32_t> cnt_local;  // this context's own counters
     uint32_t g_covered = 0;
     int32_t g_window = 0;
-    uint32_t nn_base = 0;
-    int stage = 0;                    // 0 nothing, 1 pass 1 done, 2 statistics adopted, 3 regions cut, 4 walked
     uint32_t ntiles = 0, tstride = 0;
     Compact cp{};
     K3Arrays k3{};
@@ -151,7 +148,7 @@ struct bdx_ctx {
     std::vector<uint64_t> sup_idx;
     std::vector<uint8_t> sup_flag;
     std::vector<float> seqcov, lib_density, key_density;
-    std::vector<HostRegion> regions;  // owned copies (staged runs, phantom shift); otherwise reg/rpk point into pinned memory
+    std::vector<HostRegion> regions;  // owned copies (small tables, phantom shift, own_borrowed_regions); otherwise reg/rpk point into pinned memory
     std::vector<uint32_t> r_pk;
     const HostRegion* reg = nullptr;
     size_t nreg = 0;
@@ -301,8 +298,8 @@ void stage_view(const bdx_ctx::Stage& st, bdx_batch_buf* out) {
 // stages) get this, the buffers, the stream (two arrays are zeroed when they are allocated) and a place for an error text -- NOT a context:
 // a stage calls its size function at its head, and a sizing pass (presize_stages) calls all four, possibly on a thread beside the one
 // that feeds the context.
-enum class RegionDst { Host, HostAndHbm, Hbm };   // K3's region table: pinned host memory (staged runs); that and a copy in HBM for K6 (bdx_run);
-                                                  // HBM only (sharded runs: a chromosome's table is sent on from there, nobody reads it on this host)
+enum class RegionDst { HostAndHbm, Hbm };   // K3's region table: pinned host memory and a copy in HBM for K6 (bdx_run);
+                                            // HBM only (sharded runs: a chromosome's table is sent on from there, nobody reads it on this host)
 struct StageDims {
     uint32_t na = 0;                  // anomalous reads the stages are sized for
     int nkeys = 0, nlibs = 0;
@@ -603,8 +600,8 @@ int bdx_set_device_reads(bdx_ctx* c, const bdx_batch* b) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Stages.  bdx_run chains them on one context; the bdx_stage_* entry points expose the same stages so that
-// several contexts (one per chromosome, spread over GPUs) can exchange the few global quantities between them.
+// Stages.  bdx_run chains them on one context; a sharded run (bdx_dist_impl.h) runs the same stages per rank and
+// exchanges the few global quantities between them.
 // ---------------------------------------------------------------------------------------------------------
 }  // extern "C"
 
@@ -843,7 +840,7 @@ int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second, bool pos
     if (c->n >= ((size_t)1 << 32)) return fail(c, BDX_ELIMIT, "more than 2^32 - 1 reads in one context (read indices and the prefix counters are 32-bit)");
     const uint32_t ntiles = (uint32_t)((c->n + kTile - 1) / kTile);
     c->ntiles = ntiles;
-    c->ran = false; c->stage = 0; c->replayed = false;
+    c->ran = false; c->replayed = false;
     c->cls_n = (size_t)-1;
     c->na_alloc = 0;
     c->regions.clear(); c->r_pk.clear(); c->parts.clear();
@@ -929,7 +926,6 @@ int wait_pass1(bdx_ctx* c) {
     // capacity of the later stages: the count plus the headroom an enqueue-ahead run of the same input will ask for, so that
     // its buffers are these buffers (an enqueue-ahead run has set its guess already)
     if (!c->na_alloc && c->p1.n_anom) c->na_alloc = (uint32_t)std::min<uint64_t>((uint64_t)c->p1.n_anom + c->p1.n_anom / 8 + 1024, kMaxAnomalous);
-    c->stage = 1;
     c->cls_n = c->n;
     return BDX_OK;
 }
@@ -978,7 +974,6 @@ int set_pass1(bdx_ctx* c, const uint32_t* cnt, uint32_t covered, int32_t window,
         HIPCHK(c, hipMemcpyAsync(c->b_p1.p, &hdr, sizeof(hdr), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    c->stage = 2;
     return BDX_OK;
 }
 
@@ -1032,10 +1027,8 @@ int size_cut(StageBufs& b, const StageDims& d, hipStream_t s, std::string* err) 
         SZCHK(b.h_regs.ensure(cap * sizeof(RegionRec)));
         SZCHK(b.h_pk.ensure(cap * 2 * d.nkeys * 4));
     }
-    if (d.regions != RegionDst::Host) {
-        SZCHK(b.b_r_rec.ensure(cap * sizeof(RegionRec)));
-        SZCHK(b.b_r_pk.ensure(cap * 2 * d.nkeys * 4));
-    }
+    SZCHK(b.b_r_rec.ensure(cap * sizeof(RegionRec)));
+    SZCHK(b.b_r_pk.ensure(cap * 2 * d.nkeys * 4));
     if (d.regions == RegionDst::HostAndHbm) {   // the device-side SV assembly follows
         SZCHK(size_out_deg(b, cap));
         SZCHK(b.h_counts0.ensure(sizeof(StageCounts)));
@@ -1105,8 +1098,8 @@ int size_k6(StageBufs& b, const StageDims& d, hipStream_t s, std::string* err) {
     return BDX_OK;
 }
 
-// K2: compact anomalous reads (prefix counters offset by the bases of earlier shards)
-int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepare_join) {
+// K2: compact anomalous reads
+int do_compact(bdx_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int nkeys = c->nkeys;
@@ -1116,8 +1109,7 @@ int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepa
     cp = Compact{};
     c->k3 = K3Arrays{};
     if (na) {
-        StageDims dm = stage_dims(c, na);
-        dm.k2_clears_join = dm.k2_clears_join && prepare_join;
+        const StageDims dm = stage_dims(c, na);
         BDX_TRY(size_compact(c->sb, dm, &c->err));
         const StageBufs& b = c->sb;
         cp.tid = b.b_c_tid.as<int32_t>(); cp.pos = b.b_c_pos.as<int32_t>(); cp.isize = b.b_c_isize.as<int32_t>();
@@ -1130,8 +1122,6 @@ int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepa
         k2.cls = c->b_cls.as<uint8_t>(); k2.tile_pre = c->b_tile_pre.as<uint32_t>(); k2.c = cp;
         k2.tile_tot = c->b_tile_tot.as<uint32_t>(); k2.stash = c->use_stash ? c->b_stash.as<StashRec>() : nullptr;
         k2.chunk_tot = c->fp_deferred.chunk_tot; k2.chunk_base = c->fp_deferred.chunk_base; k2.chunk_super = c->fp_deferred.chunk_super;
-        k2.nn_base = nn_base;
-        for (int k = 0; k < nkeys; ++k) k2.pk_base[k] = pk_base ? pk_base[k] : 0u;
         // scratch of the later stages cleared by this launch: the per-candidate max read length of K3, and (when this
         // context joins its own reads) the slot indices of K4's direct table
         k2.fill_ptr[0] = b.b_c_maxq.as<uint32_t>(); k2.fill_words[0] = na; k2.fill_value[0] = 0u;
@@ -1162,13 +1152,9 @@ int do_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, bool prepa
         c->finalize2_deferred = false;
     }
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[3], s));
-    c->nn_base = nn_base;
     return BDX_OK;
 }
 
-// K3: cut regions.  In a whole-genome run the last candidate of a chromosome is closed by the first anomalous read
-// of the next chromosome, which still counts for its nucleotide sum / max read length / normal-pair count
-// (BreakDancer.cpp:202-231): has_next / next_qlen / next_nn carry that read across contexts.
 // a result whose region table is read where the device left it (c->reg == h_regs.p: bdx_run on a large table, sharded runs) gets its own copy:
 // called before the pinned buffers may be reallocated under it (a sizing pass for a larger input) or handed back (bdx_trim_results)
 void own_borrowed_regions(bdx_ctx* c) {
@@ -1183,7 +1169,8 @@ void own_borrowed_regions(bdx_ctx* c) {
     c->reg = c->regions.data(); c->rpk = c->r_pk.data();
 }
 
-int do_cut(bdx_ctx* c, const K3Tail& tail, RegionDst dst) {
+// K3: cut regions.  tid_tail: see launch_k3 (null: a single-context run)
+int do_cut(bdx_ctx* c, const uint32_t* tid_tail, RegionDst dst) {
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const uint32_t na = c->na_alloc;
@@ -1193,38 +1180,38 @@ int do_cut(bdx_ctx* c, const K3Tail& tail, RegionDst dst) {
         BDX_TRY(size_cut(c->sb, dm, s, &c->err));
         const StageBufs& b = c->sb;
         K3Arrays& k3 = c->k3;
-        const bool for_k6 = dst == RegionDst::HostAndHbm, hbm_only = dst == RegionDst::Hbm;
+        const bool for_k6 = dst == RegionDst::HostAndHbm;
         k3.cap = na;
         k3.cand = b.b_cand.as<int32_t>(); k3.pre_q = b.b_pre_q.as<uint32_t>(); k3.pre_rev = b.b_pre_rev.as<uint32_t>();
         k3.pre_nonctx = b.b_pre_nonctx.as<uint32_t>(); k3.c_first = b.b_c_first.as<uint32_t>();
         k3.c_maxq = b.b_c_maxq.as<int32_t>(); k3.c_rid = b.b_c_rid.as<int32_t>(); k3.region_of = b.b_region_of.as<int32_t>();
-        k3.r_rec = hbm_only ? b.b_r_rec.as<RegionRec>() : b.h_regs.as<RegionRec>();
-        k3.r_pk = hbm_only ? b.b_r_pk.as<uint32_t>() : b.h_pk.as<uint32_t>();
+        k3.r_rec = for_k6 ? b.h_regs.as<RegionRec>() : b.b_r_rec.as<RegionRec>();
+        k3.r_pk = for_k6 ? b.h_pk.as<uint32_t>() : b.b_r_pk.as<uint32_t>();
         if (for_k6) {  // the device-side SV assembly reads the region table back: a copy in HBM
             k3.r_rec_dev = b.b_r_rec.as<RegionRec>(); k3.r_pk_dev = b.b_r_pk.as<uint32_t>(); k3.out_deg = b.b_out_deg.as<uint32_t>();
             // with the direct join right behind K3, that kernel forwards the table to the host
             k3.host_copy_later = (!c->bucketed_join && na <= kDirectJoinMax) ? 1 : 0;
             memset(b.h_counts0.p, 0, sizeof(StageCounts));
             k3.counts_host = b.h_counts0.as<StageCounts>();
+        } else {
+            k3.r_rec_dev = nullptr; k3.r_pk_dev = nullptr; k3.host_copy_later = 0;
         }
-        if (hbm_only) { k3.r_rec_dev = nullptr; k3.r_pk_dev = nullptr; k3.host_copy_later = 0; }
         k3.lb_state = b.b_lb.as<unsigned long long>();
         HIPCHK(c, next_lb_stamp(c, &k3.lb_stamp));
         k3.counts = c->b_counts.as<StageCounts>();
         // single-context runs that take the direct join let that kernel do k3_region_of_kernel's work
         c->region_of_fused = for_k6 && !c->bucketed_join && na <= kDirectJoinMax;
-        launch_k3(k3, c->cp, c->b_p1.as<Pass1>(), na, c->opts.min_len, c->opts.seq_coverage_lim, c->nkeys, c->nn_base, tail, !c->region_of_fused, s);
+        launch_k3(k3, c->cp, c->b_p1.as<Pass1>(), na, c->opts.min_len, c->opts.seq_coverage_lim, c->nkeys, tid_tail, !c->region_of_fused, s);
         if (for_k6 && !k3.host_copy_later) {  // the region table is in pinned memory
             BDX_TRY(signal_ready(c, 3, c->ev_regions));
         }
     }
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[4], s));
-    c->stage = 3;
     return BDX_OK;
 }
 
-// K4 on the context's own reads (single-context run), with the foreign entries of a sharded run behind them, or on a staged run's entries
-int do_join_local(bdx_ctx* c, uint32_t n, const Entries& en, const uint32_t* n_ptr, bool join_only) {
+// K4 on the context's own reads (single-context run), with the foreign entries of a sharded run behind them
+int do_join_local(bdx_ctx* c, uint32_t n, const Entries& en, const uint32_t* n_ptr) {
     hipStream_t s = c->stream;
     K4Arrays& k4 = c->k4;
     k4 = K4Arrays{};
@@ -1254,8 +1241,7 @@ int do_join_local(bdx_ctx* c, uint32_t n, const Entries& en, const uint32_t* n_p
         c->join_table_clean = 0;
         k4.direct = 1; k4.t_mask = slots - 1;
         k4.t_key = b.b_t_key.as<uint64_t>(); k4.t_idx = b.b_t_idx.as<int32_t>();
-        if (join_only) launch_k4_join_only(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
-        else launch_k4(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
+        launch_k4_join_only(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
         return BDX_OK;
     }
     // the partitioned join: its tables go by the entries that have arrived, sized here
@@ -1272,21 +1258,7 @@ int do_join_local(bdx_ctx* c, uint32_t n, const Entries& en, const uint32_t* n_p
     k4.bcnt = b.b_bcnt.as<uint32_t>(); k4.boff = b.b_boff.as<uint32_t>(); k4.bcur = b.b_bcur.as<uint32_t>();
     k4.e_key = b.b_e_key.as<uint64_t>(); k4.e_idx = b.b_e_idx.as<uint32_t>();
     k4.t_key = b.b_t_key.as<uint64_t>(); k4.t_idx = b.b_t_idx.as<int32_t>();
-    if (join_only) launch_k4_join_only(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
-    else launch_k4(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
-    return BDX_OK;
-}
-
-// counts + region table to the host (the table already sits in pinned host memory: see size_cut)
-int readback(bdx_ctx* c) {
-    hipStream_t s = c->stream;
-    const uint32_t na = c->p1.n_anom;
-    if (!na) return BDX_OK;
-    HIPCHK(c, hipMemcpyAsync(c->h_counts.p, c->b_counts.p, sizeof(StageCounts), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipGetLastError());
-    c->counts = *c->h_counts.as<StageCounts>();
-    if (c->counts.overflow) return fail(c, BDX_EINTERNAL, "group list overflow");
+    launch_k4_join_only(k4, en, n_ptr, n, c->b_counts.as<StageCounts>(), s);
     return BDX_OK;
 }
 
@@ -1578,7 +1550,6 @@ int finish_table(bdx_ctx* c) {
     c->stage_ms[9] = ms_between(tf1, tf2);
     c->stage_ms[10] = 0;
     c->ran = true;
-    c->stage = 4;
     return BDX_OK;
 }
 
@@ -1595,7 +1566,7 @@ int host_walk(bdx_ctx* c, int32_t last_maxq, bool any_anomalous) {
     return BDX_OK;
 }
 
-// K5 for the host walk's terms (staged runs: the whole walk is the host's)
+// K5 for the host walk's terms (the read-level replay: the whole walk is the host's)
 int score_host_terms(bdx_ctx* c) {
     hipStream_t s = c->stream;
     const uint32_t nt = (uint32_t)c->walk.terms.size();
@@ -1612,7 +1583,7 @@ int score_host_terms(bdx_ctx* c) {
     return BDX_OK;
 }
 
-// staged runs: the walk, the list and the score combination are the host's
+// the read-level replay, a run without anomalous reads: the walk, the list and the score combination are the host's
 int finish_host_walk(bdx_ctx* c) {
     hipStream_t s = c->stream;
     HIPCHK(c, hipStreamSynchronize(s));
@@ -1627,7 +1598,6 @@ int finish_host_walk(bdx_ctx* c) {
     c->counts.n_sv_dev = 0;
     c->materialized = true;
     c->ran = true;
-    c->stage = 4;
     return BDX_OK;
 }
 
@@ -1758,8 +1728,8 @@ int bdx_run(bdx_ctx* c) {
     const bool force_host = c->host_walk_only || ph_opt || c->opts.min_read_pair < 1;
     // K2 .. K6 (first half) for c->na_alloc anomalous reads
     auto enqueue_middle = [&]() -> int {
-        BDX_TRY(do_compact(c, 0, nullptr, true));
-        BDX_TRY(do_cut(c, K3Tail{}, RegionDst::HostAndHbm));
+        BDX_TRY(do_compact(c));
+        BDX_TRY(do_cut(c, nullptr, RegionDst::HostAndHbm));
         if (!c->na_alloc) return BDX_OK;
         // the region table is final after K3: the host takes its copy while the device joins the mates
         Entries en{};
@@ -1774,7 +1744,7 @@ int bdx_run(bdx_ctx* c) {
                 en.counts = c->b_counts.as<StageCounts>(); en.nkeys2 = 2 * c->nkeys;
             }
         }
-        BDX_TRY(do_join_local(c, c->na_alloc, en, &c->b_p1.as<Pass1>()->n_anom, true));
+        BDX_TRY(do_join_local(c, c->na_alloc, en, &c->b_p1.as<Pass1>()->n_anom));
         if (c->k3.host_copy_later && !c->poll) {  // the join kernel has forwarded the region table to pinned memory
             BDX_TRY(signal_ready(c, 3, c->ev_regions));  // (polling: the next kernel, k6_pairs_kernel, sets the ready word itself)
         }
@@ -1921,150 +1891,6 @@ int bdx_run(bdx_ctx* c) {
     c->stage_ms[6] = ms_between(t_h2, t_end);
     c->stage_ms[7] = ms_between(t_begin, t_end);
     return BDX_OK;
-}
-
-// ---- staged entry points (multi-context / multi-GPU runs) ------------------------------------------------------
-int bdx_stage_pass1(bdx_ctx* c) {
-    if (!c) return BDX_EINVAL;
-    NOT_WHILE_SIZING(c);
-    return do_pass1(c);
-}
-
-int bdx_get_pass1_local(const bdx_ctx* c, uint32_t* counters, uint64_t* ref_len_per_bam, uint32_t* totals) {
-    if (!c) return BDX_EINVAL;
-    if (c->stage < 1) return BDX_ESTATE;
-    if (counters) memcpy(counters, c->cnt_local.data(), c->cnt_local.size() * 4);
-    if (ref_len_per_bam)
-        for (int b = 0; b < c->nbams; ++b) ref_len_per_bam[b] = c->p1.ref_len[b];
-    if (totals) {
-        totals[0] = c->p1.n_anom; totals[1] = c->p1.n_normal;
-        for (int k = 0; k < c->nkeys; ++k) totals[2 + k] = c->p1.key_tot[k];
-    }
-    return BDX_OK;
-}
-
-int bdx_set_pass1_global(bdx_ctx* c, const uint32_t* counters, uint32_t covered_ref_len, int32_t window) {
-    if (!c || !counters) return BDX_EINVAL;
-    if (c->stage < 1) return BDX_ESTATE;
-    if (window < 0) window = window_from(c, counters, covered_ref_len);
-    return set_pass1(c, counters, covered_ref_len, window, true);
-}
-
-int bdx_stage_compact(bdx_ctx* c, uint32_t nn_base, const uint32_t* pk_base, int32_t* first_qlen, uint32_t* first_nn) {
-    if (!c) return BDX_EINVAL;
-    if (c->stage < 2) return BDX_ESTATE;
-    NOT_WHILE_SIZING(c);
-    if (c->opts.min_len < 0) return fail(c, BDX_ELIMIT, "staged runs do not support a negative -s");
-    BDX_TRY(do_compact(c, nn_base, pk_base, false));
-    if (first_qlen) *first_qlen = 0;
-    if (first_nn) *first_nn = 0;
-    if (c->p1.n_anom) {  // the first anomalous read of this chromosome closes the previous chromosome's last candidate
-        uint32_t meta = 0, nn = 0;
-        HIPCHK(c, hipMemcpyAsync(&meta, c->cp.meta, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&nn, c->cp.nn, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (first_qlen) *first_qlen = meta_qlen(meta);
-        if (first_nn) *first_nn = nn;
-    }
-    return BDX_OK;
-}
-
-int bdx_stage_regions(bdx_ctx* c, int has_next, int32_t next_qlen, uint32_t next_nn) {
-    if (!c) return BDX_EINVAL;
-    if (c->stage < 2) return BDX_ESTATE;
-    NOT_WHILE_SIZING(c);
-    BDX_TRY(do_cut(c, K3Tail{has_next, next_qlen, next_nn, nullptr}, RegionDst::Host));
-    return readback(c);
-}
-
-int bdx_get_stage_regions(const bdx_ctx* c, uint32_t* n_regions, uint32_t* n_anomalous, int32_t* last_maxq) {
-    if (!c) return BDX_EINVAL;
-    if (c->stage < 3) return BDX_ESTATE;
-    if (n_regions) *n_regions = c->counts.n_regions;
-    if (n_anomalous) *n_anomalous = c->p1.n_anom;
-    if (last_maxq) *last_maxq = c->counts.last_maxq;
-    return BDX_OK;
-}
-
-int bdx_get_region_records(const bdx_ctx* c, bdx_region_rec* out, uint32_t* pk, size_t cap) {
-    if (!c) return BDX_EINVAL;
-    if (c->stage < 3 || !c->sb.h_regs.p) return BDX_ESTATE;   // (no table yet, or handed back by bdx_trim_results)
-    const size_t n = std::min<size_t>(cap, c->counts.n_regions);
-    static_assert(sizeof(bdx_region_rec) == sizeof(RegionRec), "region record layout");
-    if (out && n) memcpy(out, c->sb.h_regs.p, n * sizeof(RegionRec));
-    if (pk && n) memcpy(pk, c->sb.h_pk.p, n * 2 * c->nkeys * 4);
-    return BDX_OK;
-}
-
-int bdx_get_compact(const bdx_ctx* c, uint64_t* key, int32_t* region, uint32_t* meta, int32_t* isize, size_t cap) {
-    if (!c) return BDX_EINVAL;
-    if (c->stage < 3) return BDX_ESTATE;
-    const size_t n = std::min<size_t>(cap, c->p1.n_anom);
-    if (!n) return BDX_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return BDX_EHIP;
-    if (key && hipMemcpy(key, c->cp.key, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return BDX_EHIP;
-    if (region && hipMemcpy(region, c->k3.region_of, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return BDX_EHIP;
-    if (meta && hipMemcpy(meta, c->cp.meta, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return BDX_EHIP;
-    if (isize && hipMemcpy(isize, c->cp.isize, n * 4, hipMemcpyDeviceToHost) != hipSuccess) return BDX_EHIP;
-    return BDX_OK;
-}
-
-int bdx_join_entries(bdx_ctx* c, size_t n, const uint64_t* key, const uint32_t* order, const int32_t* region, const uint32_t* meta,
-                     const int32_t* isize, bdx_group* out, size_t cap, uint32_t* n_groups, uint32_t* n_pairs) {
-    if (!c || (n && (!key || !order || !region || !meta || !isize))) return BDX_EINVAL;
-    if (n > kMaxAnomalous) return fail(c, BDX_ELIMIT, "too many join entries");
-    NOT_WHILE_SIZING(c);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (n_groups) *n_groups = 0;
-    if (n_pairs) *n_pairs = 0;
-    if (!n) return BDX_OK;
-    HIPCHK(c, c->b_x_key.ensure(n * 8)); HIPCHK(c, c->b_x_order.ensure(n * 4)); HIPCHK(c, c->b_x_region.ensure(n * 4));
-    HIPCHK(c, c->b_x_meta.ensure(n * 4)); HIPCHK(c, c->b_x_isize.ensure(n * 4)); HIPCHK(c, c->b_x_n.ensure(16));
-    HIPCHK(c, c->b_counts.ensure(sizeof(StageCounts))); HIPCHK(c, c->h_counts.ensure(sizeof(StageCounts)));
-    const uint32_t n32 = (uint32_t)n;
-    HIPCHK(c, hipMemcpyAsync(c->b_x_key.p, key, n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->b_x_order.p, order, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->b_x_region.p, region, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->b_x_meta.p, meta, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->b_x_isize.p, isize, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->b_x_n.p, &n32, 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->b_counts.p, 0, sizeof(StageCounts), s));
-    Entries en{};
-    en.key = c->b_x_key.as<uint64_t>(); en.region = c->b_x_region.as<int32_t>(); en.order = c->b_x_order.as<uint32_t>();
-    en.meta = c->b_x_meta.as<uint32_t>(); en.isize = c->b_x_isize.as<int32_t>();
-    BDX_TRY(do_join_local(c, n32, en, c->b_x_n.as<uint32_t>(), false));
-    HIPCHK(c, hipMemcpyAsync(c->h_counts.p, c->b_counts.p, sizeof(StageCounts), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipGetLastError());
-    const StageCounts sc = *c->h_counts.as<StageCounts>();
-    if (sc.irregular) return fail(c, BDX_ELIMIT, "a read name occurs more than twice: staged runs cannot replay it (run the chromosomes in one context)");
-    if (sc.overflow) return fail(c, BDX_EINTERNAL, "group list overflow");
-    if (n_groups) *n_groups = sc.n_groups;
-    if (n_pairs) *n_pairs = sc.n_pairs;
-    const size_t ng = std::min<size_t>(cap, sc.n_groups);
-    static_assert(sizeof(bdx_group) == sizeof(GroupRec), "group record layout");
-    if (out && ng) memcpy(out, c->k4.g_rec, ng * sizeof(GroupRec));
-    return BDX_OK;
-}
-
-int bdx_stage_walk(bdx_ctx* c, size_t nregions, const bdx_region_rec* regions, const uint32_t* pk, size_t ngroups,
-                   const bdx_group* groups, int32_t last_maxq, int any_anomalous) {
-    if (!c || (nregions && (!regions || !pk)) || (ngroups && !groups)) return BDX_EINVAL;
-    if (c->stage < 2) return BDX_ESTATE;
-    NOT_WHILE_SIZING(c);
-    decode_regions(c, (const RegionRec*)regions, pk, (uint32_t)nregions, 0, false);
-    decode_groups(c, (const GroupRec*)groups, (uint32_t)ngroups, 0);
-    c->counts.n_regions = (uint32_t)nregions;
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = host_walk(c, last_maxq, any_anomalous != 0);
-    if (rc != BDX_OK) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
-    rc = score_host_terms(c);
-    if (rc == BDX_OK) rc = finish_host_walk(c);
-    c->stage_ms[5] = ms_between(t0, t1);
-    c->stage_ms[6] = ms_between(t1, std::chrono::steady_clock::now());
-    return rc;
 }
 
 int bdx_get_summary(const bdx_ctx* c, bdx_summary* o) {

@@ -151,8 +151,6 @@ struct K2Params {
     const uint32_t* tile_tot;  // K1's per-tile totals and its ready-made records (stash null: not available)
     const StashRec* stash;
     Compact c;
-    uint32_t nn_base;      // normal read pairs / proper reads of earlier shards (0 for a single context)
-    uint32_t pk_base[60];
     // initialisation of later stages' scratch folded into this launch (its grid is large and mostly idle)
     uint32_t* fill_ptr[4];
     uint32_t fill_words[4];

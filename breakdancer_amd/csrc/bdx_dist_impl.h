@@ -999,7 +999,7 @@ int DistRun::pass1_and_counts(std::vector<uint64_t>& v1) {
         ul.fill(T + O.mt, 0u, (size_t)ntids);
         launch_k9_upload(ul, s);
     }
-    DCTX(d, C, do_compact(C, 0, nullptr, true));
+    DCTX(d, C, do_compact(C));
     trace("compaction");
     memset(H + L.first, 0, (size_t)ntids * 16);
     if (na) {
@@ -1156,7 +1156,7 @@ int DistRun::cut_regions(const Stats& A, std::vector<uint64_t>& v3) {
     }
     if (!na) return BDX_OK;
     launch_k9_rebase(C->cp, &C->b_p1.as<Pass1>()->n_anom, na, nkeys, T + O.off, nullptr, s);
-    DCTX(d, C, do_cut(C, K3Tail{0, 0, 0, T + O.tail}, RegionDst::Hbm));
+    DCTX(d, C, do_cut(C, T + O.tail, RegionDst::Hbm));
     trace("region cut");
     launch_k9_tid_regions(C->sb.b_r_rec.as<RegionRec>(), C->b_counts.as<StageCounts>(), ntids, H + L.rtab, s);
     launch_k9_signal(H + 2, d->seq, s);
@@ -1207,7 +1207,7 @@ int DistRun::seed_result(const Stats& A, const Regions& B) {
         U->walk.clear(); U->log_tail.clear();
         U->n_sv_total = U->n_terms_total = U->n_cn_total = U->n_printed = U->n_sv_host = U->n_groups_total = 0;
         memset(&U->counts, 0, sizeof(U->counts));
-        U->materialized = true; U->ran = true; U->stage = 4;
+        U->materialized = true; U->ran = true;
         if (A.want_support) { U->collect_support = true; U->sup_off.assign(1, 0); }   // (no SV, no supporting read: an empty list, not a missing one)
     }
     return BDX_OK;
@@ -1346,7 +1346,7 @@ int DistRun::join_walk_table(const Stats& A, const Regions& B, const ExchangePla
         Entries en{};
         en.key = C->cp.key; en.check = C->cp.check; en.region = C->k3.region_of; en.meta = C->cp.meta; en.isize = C->cp.isize;
         en.n_local = &C->b_p1.as<Pass1>()->n_anom; en.fkey = fkey; en.fcheck = fcheck; en.fregion = fregion; en.want_pair_lo = 1;
-        DCTX(d, C, do_join_local(C, C->na_alloc + nf, en, T + O.ntot, true));
+        DCTX(d, C, do_join_local(C, C->na_alloc + nf, en, T + O.ntot));
     }
     trace("join");
     t_x1 = now();
@@ -1551,7 +1551,7 @@ int DistRun::adopt_own_table(const Regions& B) {
     U->reg = C->reg; U->nreg = C->nreg; U->rpk = C->rpk;   // (the genome's region table stays in this rank's pinned buffers until the next run)
     C->reg = nullptr; C->nreg = 0; C->rpk = nullptr;
     U->counts.n_regions = (uint32_t)B.NR;
-    U->ran = true; U->stage = 4;
+    U->ran = true;
     ms(kPhMerge) = 0;
     return finished();
 }
@@ -1807,7 +1807,7 @@ int DistRun::merge_tables(const Regions& B, const Packages& G, const TableCounts
         materialize(U);
         finish_scores(U->opts, U->log_tail.data(), U->walk.svs.data(), U->walk.svs.size(), &U->n_printed);
     }
-    U->ran = true; U->stage = 4;
+    U->ran = true;
     return BDX_OK;
 }
 

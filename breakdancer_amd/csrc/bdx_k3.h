@@ -70,20 +70,13 @@ struct K3Arrays {
     StageCounts* counts_host;  // pinned host mirror: n_cand / n_regions / last_maxq are stored there as well (may be null)
 };
 
-// the read that closes the last candidate when the stream continues in another context (next chromosome)
-struct K3Tail {
-    int has_next;
-    int32_t qlen;
-    uint32_t nn;
-    // a context that holds SEVERAL chromosomes of a sharded run, not necessarily neighbours in the genome: the read that closes the
-    // last candidate of chromosome t is the first anomalous read of the next chromosome that has any -- wherever it lives --, from
-    // this table of four words per chromosome: {has_next, its read length, the normal-pair count its candidate ends with (the next
-    // read's, or the genome's total), 0}.  Null: the compact list's own next read closes (single-context runs)
-    const uint32_t* tid_tail;
-};
-
+// tid_tail: a context that holds SEVERAL chromosomes of a sharded run, not necessarily neighbours in the genome.  In a whole-genome run the
+// last candidate of a chromosome is closed by the first anomalous read of the next chromosome that has any -- wherever it lives --, which
+// still counts for its nucleotide sum / max read length / normal-pair count (BreakDancer.cpp:202-231): this table holds four words per
+// chromosome, {1 if there is such a read, its read length, the normal-pair count its candidate ends with (the next read's, or the genome's total), 0}.
+// Null: the compact list's own next read closes (single-context runs)
 void launch_k3(const K3Arrays& a, const Compact& cp, const Pass1* p1, uint32_t n_anom_host, int min_len, int seq_coverage_lim,
-               int nkeys, uint32_t nn_base, K3Tail tail, bool region_of_launch, hipStream_t s);
+               int nkeys, const uint32_t* tid_tail, bool region_of_launch, hipStream_t s);
 
 // ---- K4 ---------------------------------------------------------------------------------------------
 constexpr int kMaxBuckets = 8192;
@@ -94,7 +87,6 @@ inline uint32_t direct_join_slots(uint32_t n) {
     while (slots < 4 * (uint64_t)n) slots <<= 1;
     return slots;
 }
-constexpr int kAggSlots = 4096;      // block-local group table: 4096 x 16 B = 64 KiB
 
 struct K4Arrays {
     uint32_t nbuckets;   // power of two
@@ -130,10 +122,8 @@ struct Entries {
     const uint64_t* key;
     const uint64_t* check;   // second name hash: two entries are mates only if it agrees as well (nullptr: the key alone decides)
     const int32_t* region;   // region id (global ids when the entries come from several shards)
-    const uint32_t* order;   // position in the merged stream order; nullptr = the entry index itself
     const uint32_t* meta;    // flag | rev<<4 | lib<<8 | qlen<<16
     const int32_t* isize;    // |isize|
-    int32_t region_base;     // added to both region ids of a pair group (a chromosome's local ids -> genome-wide ids)
     // single-context runs with the direct join: the join kernel derives the region itself (region = c_rid[cand[j]]),
     // stores it into region_out and resets K6's per-region scratch -- k3_region_of_kernel's work without its launch
     const int32_t* cand;
@@ -159,7 +149,7 @@ struct Entries {
     int want_pair_lo;        // fill K4Arrays::pair_lo from `region` (single-context runs derive it from c_rid)
 };
 
-void launch_k4(const K4Arrays& k4, const Entries& e, const uint32_t* n_ptr, uint32_t n_upper, StageCounts* counts, hipStream_t s);
+void launch_k4_join_only(const K4Arrays& k4, const Entries& e, const uint32_t* n_ptr, uint32_t n_upper, StageCounts* counts, hipStream_t s);
 
 // ---- K7: exchange of inter-chromosomal mate records between the GPUs of a chromosome-sharded run ------------------
 constexpr int kMaxRanks = 64;
@@ -183,8 +173,6 @@ struct GatherPackage { uint64_t regions_off, pk_off, groups_off; uint32_t nr, ng
 struct GatherDesc { GatherPackage p[kMaxRanks]; int world; };
 void launch_k8_place_regions(const char* all, const GatherDesc& D, uint32_t max_nr, const uint64_t* rbase, int ntids, int nkeys2, RegionRec* r_rec,
                              uint32_t* r_pk, uint32_t* err, hipStream_t s);
-
-void launch_k4_join_only(const K4Arrays& k4, const Entries& e, const uint32_t* n_ptr, uint32_t n_upper, StageCounts* counts, hipStream_t s);
 
 // ---- K5 ---------------------------------------------------------------------------------------------
 void launch_k5(const double* lambda, const int32_t* k, double* out, uint32_t n, hipStream_t s);

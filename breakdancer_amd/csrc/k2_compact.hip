@@ -149,9 +149,9 @@ template <bool kBases> __device__ __forceinline__ void k2_body(const K2Params& p
                         p.c.key[j] = key;
                         if (p.c.check) p.c.check[j] = check;
                         p.c.idx[j] = (uint32_t)i;
-                        p.c.nn[j] = p.nn_base + pre_norm + e[0] + ((r1.x >> 8) & 511u);
-                        p.c.pk[j] = p.pk_base[0] + pre_k0 + e[1] + (k0 == 0 ? r1.y : 0u);
-                        if (nkeys > 1) p.c.pk[(size_t)p.c.cap + j] = p.pk_base[1] + pre_k1 + e[2] + (k0 == 1 ? r1.y : 0u);
+                        p.c.nn[j] = pre_norm + e[0] + ((r1.x >> 8) & 511u);
+                        p.c.pk[j] = pre_k0 + e[1] + (k0 == 0 ? r1.y : 0u);
+                        if (nkeys > 1) p.c.pk[(size_t)p.c.cap + j] = pre_k1 + e[2] + (k0 == 1 ? r1.y : 0u);
                     }
                     continue;
                 }
@@ -192,7 +192,7 @@ template <bool kBases> __device__ __forceinline__ void k2_body(const K2Params& p
 
         const uint32_t tot = (uint32_t)__popc(m_anom) + ((uint32_t)__popc(m_nleft) << 16);
         const uint32_t ex0 = wave_incl_scan(tot) - tot;
-        const uint32_t nn0 = p.nn_base + pre_norm + (ex0 >> 16);
+        const uint32_t nn0 = pre_norm + (ex0 >> 16);
         const uint32_t local0 = ex0 & 0xFFFFu;
         // Wave-level compaction before the gather: every anomalous slot drops (offset in tile, class byte, nn) into the
         // wave's LDS slice at its in-tile rank; then lanes 0..cnt-1 each fetch ONE whole record, so the column
@@ -254,8 +254,8 @@ template <bool kBases> __device__ __forceinline__ void k2_body(const K2Params& p
             }
             const uint32_t v = (uint32_t)__popc(mk0) + ((uint32_t)__popc(mk1) << 16);
             const uint32_t ex = wave_incl_scan(v) - v;
-            const uint32_t b0 = p.pk_base[k0] + (k0 == 0 ? pre_k0 : col_prefix<kBases>(p, kColKey0 + k0, tile2, chunk, lane));
-            const uint32_t b1 = k0 + 1 < nkeys ? p.pk_base[k0 + 1] + (k0 == 0 ? pre_k1 : col_prefix<kBases>(p, kColKey0 + k0 + 1, tile2, chunk, lane)) : 0u;
+            const uint32_t b0 = k0 == 0 ? pre_k0 : col_prefix<kBases>(p, kColKey0 + k0, tile2, chunk, lane);
+            const uint32_t b1 = k0 + 1 < nkeys ? (k0 == 0 ? pre_k1 : col_prefix<kBases>(p, kColKey0 + k0 + 1, tile2, chunk, lane)) : 0u;
             uint32_t j = rank0 + local0;
             for (uint32_t mm = m_anom; mm; mm &= mm - 1, ++j) {
                 if (j >= p.c.cap) break;
@@ -269,7 +269,7 @@ template <bool kBases> __device__ __forceinline__ void k2_body(const K2Params& p
 }
 
 __device__ __forceinline__ void k2_fills(const K2Params& p) {  // (every workgroup of the launch takes part)
-#pragma unroll
+#pragma nounroll  // (indexed at run time, the argument block is read from kernarg memory where it is used; unrolled, all of it is loaded on entry and a third spilled to lanes: one VGPR more)
     for (int f = 0; f < 4; ++f)
         for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < p.fill_words[f]; i += gridDim.x * kBlock) p.fill_ptr[f][i] = p.fill_value[f];
 }

@@ -75,8 +75,7 @@ struct CandCtx {
     Compact cp;
     const Pass1* p1;
     int min_len, seq_coverage_lim;
-    uint32_t nn_base;
-    K3Tail tail;
+    const uint32_t* tid_tail;   // see launch_k3; null: a single-context run
     __device__ CandStats stats(uint32_t c, uint32_t nc) const {
         CandStats s;
         const uint32_t na = p1->n_anom;
@@ -88,15 +87,15 @@ struct CandCtx {
         s.rev = a.pre_rev[l] - (f ? a.pre_rev[f - 1] : 0u);
         s.nonctx = a.pre_nonctx[l] - (f ? a.pre_nonctx[f - 1] : 0u);
         // sharded run, several chromosomes in this context: the last candidate of a chromosome is closed by the first anomalous read
-        // of the next chromosome that has one, which may live on another rank (K3Tail::tid_tail)
-        const bool chrom_last = tail.tid_tail && (c + 1 == nc || cp.tid[nxt] != cp.tid[f]);
-        const uint32_t* tl = chrom_last ? tail.tid_tail + 4 * (size_t)cp.tid[f] : nullptr;
+        // of the next chromosome that has one, which may live on another rank (tid_tail)
+        const bool chrom_last = tid_tail && (c + 1 == nc || cp.tid[nxt] != cp.tid[f]);
+        const uint32_t* tl = chrom_last ? tid_tail + 4 * (size_t)cp.tid[f] : nullptr;
         const uint32_t e = (c + 1 < nc && !chrom_last) ? nxt : l;
         int qsum = (int)(a.pre_q[e] - a.pre_q[f]);
         int maxq = a.c_maxq[c];
-        const bool tail_closes = chrom_last ? tl[0] != 0 : (c + 1 == nc && tail.has_next);  // closed by the first anomalous read of the next chromosome
-        const int tail_qlen = chrom_last ? (int)tl[1] : tail.qlen;
+        const bool tail_closes = chrom_last && tl[0];  // closed by the first anomalous read of the next chromosome
         if (tail_closes) {
+            const int tail_qlen = (int)tl[1];
             qsum += tail_qlen;
             maxq = max(maxq, tail_qlen);
         }
@@ -105,7 +104,7 @@ struct CandCtx {
         s.accept = (end - start > min_len) && (cov < (float)seq_coverage_lim);
         // normal read pairs seen while the candidate was open (BreakDancer.cpp:202-206): between its first
         // read and the breaking read, or the end of the stream
-        const uint32_t nn_end = chrom_last ? tl[2] : (c + 1 < nc ? cp.nn[nxt] : (tail_closes ? tail.nn : nn_base + p1->n_normal));
+        const uint32_t nn_end = chrom_last ? tl[2] : (c + 1 < nc ? cp.nn[nxt] : p1->n_normal);
         s.nnormal = nn_end - cp.nn[f];
         return s;
     }
@@ -167,17 +166,17 @@ __global__ __launch_bounds__(256) void k3_region_of_kernel(K3Arrays a, const Pas
 }
 
 void launch_k3(const K3Arrays& a, const Compact& cp, const Pass1* p1, uint32_t n_anom_host, int min_len, int seq_coverage_lim,
-               int nkeys, uint32_t nn_base, K3Tail tail, bool region_of_launch, hipStream_t s) {
+               int nkeys, const uint32_t* tid_tail, bool region_of_launch, hipStream_t s) {
     if (n_anom_host == 0) return;
     // a.c_maxq[0 .. n_anom) must be zero on entry (K2 clears it while compacting)
     const uint32_t* n_ptr = &p1->n_anom;
     HeadIn hin{cp.tid, cp.pos, cp.meta, p1};
-    HeadOut hout{a, cp.tid, tail.tid_tail ? 1 : 0};
+    HeadOut hout{a, cp.tid, tid_tail ? 1 : 0};
     // one launch per scan (decoupled look-back)
     const size_t nblk = scan_grid(a.cap, 1);
     if (n_anom_host > (1u << 19)) scan_launch_lb<U4, 2>(hin, hout, n_ptr, n_anom_host, a.lb_state, a.lb_stamp, s);   // (two reads per lane: half the workgroups and look-back words -- 45 -> 35 us at a genome share; four: 39)
     else scan_launch_lb<U4, 1>(hin, hout, n_ptr, n_anom_host, a.lb_state, a.lb_stamp, s);
-    const CandCtx cx{a, cp, p1, min_len, seq_coverage_lim, nn_base, tail};
+    const CandCtx cx{a, cp, p1, min_len, seq_coverage_lim, tid_tail};
     scan_launch_lb<uint32_t, 1>(AcceptIn{cx}, AcceptOut{cx, nkeys}, &a.counts->n_cand, n_anom_host, a.lb_state + 4 * nblk, a.lb_stamp, s);
     if (region_of_launch) hipLaunchKernelGGL(k3_region_of_kernel, dim3((n_anom_host + 255) / 256), dim3(256), 0, s, a, p1);  // else: fused into the join
 }

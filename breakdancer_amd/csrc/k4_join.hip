@@ -6,10 +6,10 @@
 //   SvBuilder.cpp:101-118        _observe_read: pair mates by name; the *second observed* mate decides
 //                                flag, library and |isize| of the pair
 //
-// A pair exists iff both mates sit in accepted regions.  Reads of accepted regions are partitioned by a
-// hash of the name key into buckets that fit an LDS table (160 KiB per CU on gfx950), each bucket is
-// joined by one workgroup with open addressing in LDS, and the pairs are then aggregated per
-// (region_lo, region_hi, flag, library) in a second LDS table keyed by the packed group id.  The edge
+// A pair exists iff both mates sit in accepted regions.  Up to kDirectJoinMax entries meet in one
+// open-addressing table in HBM; beyond that they are partitioned by a hash of the name key into buckets
+// that fit an LDS table (160 KiB per CU on gfx950) and each bucket is joined by one workgroup with open
+// addressing in LDS.  The pairs are aggregated per (region_lo, region_hi, flag, library) by K6; the edge
 // weight of the reference's graph is the sum of a group's pair counts.
 #include "bdx_k3.h"
 #include "bdx_scan.h"
@@ -255,85 +255,14 @@ __global__ __launch_bounds__(256) void k4_direct_join_kernel(K4Arrays k4, Entrie
     counts->irregular = 1;  // (a probe sequence this long: thousands of reads share one name)
 }
 
-constexpr uint64_t kEmptyGroup = ~0ull;
-
-__global__ __launch_bounds__(256) void k4_aggregate_kernel(K4Arrays k4, Entries en, const uint32_t* n_ptr, StageCounts* counts) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long* s_key = (unsigned long long*)smem;  // [kAggSlots]
-    uint32_t* s_cnt = (uint32_t*)(s_key + kAggSlots);
-    uint32_t* s_sum = s_cnt + kAggSlots;
-    uint32_t* s_ws = s_sum + kAggSlots;  // [4]; everything lives in the dynamic region (keeps its base 16-B aligned)
-    uint32_t& s_base = s_ws[4];
-    uint32_t& s_pairs = s_ws[5];
-    const uint32_t na = *n_ptr;
-    const uint32_t base = blockIdx.x * kPartChunk;
-    if (base >= na) return;
-    for (int s = threadIdx.x; s < kAggSlots; s += 256) { s_key[s] = kEmptyGroup; s_cnt[s] = 0; s_sum[s] = 0; }
-    if (threadIdx.x == 0) s_pairs = 0;
-    __syncthreads();
-    uint32_t mypairs = 0;
-    for (int it = 0; it < kPartChunk / 256; ++it) {
-        const uint32_t j = base + it * 256 + threadIdx.x;
-        if (j >= na) continue;
-        const int rj = en.region[j];
-        if (rj < 0) continue;
-        const int32_t p = k4.partner[j];
-        if (p < 0) continue;
-        // j must be the second-observed mate (Q9): the later read in merged stream order
-        const uint32_t oj = en.order ? en.order[j] : j, op = en.order ? en.order[p] : (uint32_t)p;
-        if (op >= oj) continue;
-        const int rp = en.region[p];
-        const uint32_t m = en.meta[j];
-        const uint64_t gk = group_pack((uint32_t)(rp + en.region_base), (uint32_t)(rj + en.region_base), (uint32_t)meta_lib(m),
-                                       (uint32_t)meta_flag(m));
-        uint32_t s = (uint32_t)(mix64(gk) & (kAggSlots - 1));
-        while (true) {
-            const unsigned long long old = atomicCAS(&s_key[s], (unsigned long long)kEmptyGroup, (unsigned long long)gk);
-            if (old == kEmptyGroup || old == gk) break;
-            s = (s + 1) & (kAggSlots - 1);
-        }
-        atomicAdd(&s_cnt[s], 1u);
-        atomicAdd(&s_sum[s], (uint32_t)en.isize[j]);
-        ++mypairs;
-    }
-    if (mypairs) atomicAdd(&s_pairs, mypairs);
-    __syncthreads();
-    // flush: count occupied slots (16 per thread), reserve a range of the output list once per workgroup
-    uint32_t occ = 0;
-    for (int q = 0; q < kAggSlots / 256; ++q) occ += s_key[threadIdx.x * (kAggSlots / 256) + q] != kEmptyGroup;
-    const uint32_t inc = wave_incl_scan(occ);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 63) s_ws[w] = inc;
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-    for (int k = 0; k < 4; ++k) { if (k < w) off += s_ws[k]; tot += s_ws[k]; }
-    if (threadIdx.x == 0) {
-        s_base = tot ? atomicAdd(&counts->n_groups, tot) : 0u;
-        if (s_pairs) atomicAdd(&counts->n_pairs, s_pairs);
-    }
-    __syncthreads();
-    uint32_t o = s_base + off + inc - occ;
-    for (int q = 0; q < kAggSlots / 256; ++q) {
-        const int s = threadIdx.x * (kAggSlots / 256) + q;
-        if (s_key[s] != kEmptyGroup) {
-            if (o < k4.g_cap) { GroupRec g; g.key = s_key[s]; g.pairs = s_cnt[s]; g.sum_isize = s_sum[s]; k4.g_rec[o] = g; }
-            else counts->overflow = 1;
-            ++o;
-        }
-    }
-}
-
-static void launch_k4_impl(const K4Arrays& k4, const Entries& en, const uint32_t* n_ptr, uint32_t n_anom_host, StageCounts* counts,
-                           hipStream_t s, bool aggregate) {
+// mate join only: the pair groups are formed per region by K6
+void launch_k4_join_only(const K4Arrays& k4, const Entries& en, const uint32_t* n_ptr, uint32_t n_anom_host, StageCounts* counts,
+                         hipStream_t s) {
     if (n_anom_host == 0) return;
     const uint32_t g = (n_anom_host + kPartChunk - 1) / kPartChunk;
     if (k4.direct) {
         const uint32_t gd = (n_anom_host + 255) / 256 + (en.r_rec_host ? kJoinForwardBlocks : 0u);
         hipLaunchKernelGGL(k4_direct_join_kernel, dim3(gd), dim3(256), 0, s, k4, en, n_ptr, counts);
-        if (aggregate) {
-            (void)hipFuncSetAttribute((const void*)k4_aggregate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kAggSlots * 16 + 32);
-            hipLaunchKernelGGL(k4_aggregate_kernel, dim3(g), dim3(256), (size_t)kAggSlots * 16 + 32, s, k4, en, n_ptr, counts);
-        }
         return;
     }
     // bcnt is zero on entry (zeroed at allocation, then by every bucket scan); partner[] needs no initialisation: the join
@@ -344,20 +273,9 @@ static void launch_k4_impl(const K4Arrays& k4, const Entries& en, const uint32_t
     static bool attr_set = false;
     if (!attr_set) {  // more than 64 KiB of dynamic LDS has to be opted into
         (void)hipFuncSetAttribute((const void*)k4_join_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kJoinLdsSlots * 12);
-        (void)hipFuncSetAttribute((const void*)k4_aggregate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kAggSlots * 16 + 32);
         attr_set = true;
     }
     hipLaunchKernelGGL(k4_join_kernel, dim3(k4.nbuckets), dim3(256), (size_t)kJoinLdsSlots * 12, s, k4, en.region, en.check, counts);
-    if (aggregate) hipLaunchKernelGGL(k4_aggregate_kernel, dim3(g), dim3(256), (size_t)kAggSlots * 16 + 32, s, k4, en, n_ptr, counts);
-}
-
-void launch_k4(const K4Arrays& k4, const Entries& en, const uint32_t* n_ptr, uint32_t n_anom_host, StageCounts* counts, hipStream_t s) {
-    launch_k4_impl(k4, en, n_ptr, n_anom_host, counts, s, true);
-}
-// mate join only: the pair groups are then formed per region by K6 (single-context runs, where region ids follow the stream)
-void launch_k4_join_only(const K4Arrays& k4, const Entries& en, const uint32_t* n_ptr, uint32_t n_anom_host, StageCounts* counts,
-                         hipStream_t s) {
-    launch_k4_impl(k4, en, n_ptr, n_anom_host, counts, s, false);
 }
 
 }  // namespace bdx

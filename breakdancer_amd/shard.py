@@ -46,7 +46,7 @@ def owner_of(keys, world):
 
 
 class LocalComm:
-    """world of one (also what the tests use to exercise the staged path on a single GPU)"""
+    """world of one (run_per_chromosome's default: every chromosome on this GPU)"""
     rank, world = 0, 1
 
     def allreduce_sum(self, a):

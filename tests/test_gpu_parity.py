@@ -392,6 +392,60 @@ def test_bucketed_join_path(seed, monkeypatch):
     compare(run, product_from_oracle(run))
 
 
+_TWO_CHROMOSOMES = []
+
+
+def _two_chromosome_case():
+    """two chromosomes of 240 kbp in one stream, two libraries (a read group each, alternating by pair) counted apart (cn_lib: two
+    keys): a normal pair every 150 bp, and every 30 kbp a deletion cluster of six pairs (mates 10 kbp apart, so a cluster is two
+    regions).  The stream goes on for 20 kbp of normal pairs behind the last anomalous read.  One oracle run, shared by the cases"""
+    if _TWO_CHROMOSOMES:
+        return _TWO_CHROMOSOMES[0]
+    rows = []   # (tid, pos, mpos, isize, flag, pair)
+    pair = 0
+    for tid in (0, 1):
+        for p in range(1000, 241000, 150):
+            rows.append((tid, p, p + 300, 400, 0x1 | 0x2 | 0x20 | 0x40, pair))
+            rows.append((tid, p + 300, p, -400, 0x1 | 0x2 | 0x10 | 0x80, pair))
+            pair += 1
+        for c in range(5000, 215000, 30000):
+            for i in range(6):
+                rows.append((tid, c + 10 * i, c + 10 * i + 10000, 10100, 0x1 | 0x20 | 0x40, pair))
+                rows.append((tid, c + 10 * i + 10000, c + 10 * i, -10100, 0x1 | 0x10 | 0x80, pair))
+                pair += 1
+    rows.sort(key=lambda r: (r[0], r[1]))
+    a = np.array(rows, np.int64)
+    n = len(a)
+    st = dict(tid=a[:, 0].astype(np.int32), pos=a[:, 1].astype(np.int32), mtid=a[:, 0].astype(np.int32), mpos=a[:, 2].astype(np.int32),
+              isize=a[:, 3].astype(np.int32), flag=a[:, 4].astype(np.uint16), qlen=np.full(n, 100, np.int32),
+              bdqual=np.full(n, 60, np.uint8), rg=["rg%d" % (q % 2 + 1) for q in a[:, 5]], name_id=(a[:, 5] + 1).astype(np.uint64))
+    cfg = "".join("readgroup:rg%d\tplatform:illumina\tmap:x.bam\treadlen:100.00\tlib:lib%d\tlower:310.00\tupper:490.00\tmean:400.00\tstd:30.00\n"
+                  % (i, i) for i in (1, 2))
+    run = oracle_case(cfg, [st], ["c1", "c2"], make_opts(cn_lib=1, score_threshold=-1))
+    anomalous = np.flatnonzero(np.abs(a[:, 3]) > 490)
+    tail_pairs = int((a[anomalous[-1] + 1:, 3] > 0).sum())
+    _TWO_CHROMOSOMES.append((run, n, tail_pairs))
+    return _TWO_CHROMOSOMES[0]
+
+
+@pytest.mark.parametrize("bucketed", [0, 1])
+def test_two_chromosomes_two_keys_normal_pairs_behind_the_last_region(bucketed, monkeypatch):
+    """K3's two ends of a candidate's normal-pair count in a single context: the last candidate of the first chromosome is closed by
+    the next chromosome's first anomalous read (that read's count), the last candidate of the stream by nothing (pass 1's total, the
+    normal pairs behind it included); with two counter keys, so K2 writes a second column of proper-read prefixes.  Region table and
+    copy numbers against the oracle, through the direct join and through the bucketed one"""
+    if bucketed:
+        monkeypatch.setenv("BDX_BUCKETED_JOIN", "1")
+    run, n, tail_pairs = _two_chromosome_case()
+    assert 3000 < n < 10000 and run.n_merged == n and run.nlibs == 2 and run.W < 9000
+    assert run.n_regions == 28 and run.n_svs == 14 and (run.sv_i[:, 14] == 2).all()        # two regions a cluster; two keys a candidate
+    assert set(run.regions[:, 1].tolist()) == {0, 1}
+    assert tail_pairs > 100 and run.regions[-1, 4] >= tail_pairs                            # the stream's end closes the last region
+    bd = product_from_oracle(run)
+    compare(run, bd)
+    bd.close()
+
+
 @pytest.mark.parametrize("mode", ["ahead", "retry", "off"])
 def test_repeated_runs_on_one_context(mode, monkeypatch):
     """a context that runs again on an input of the same size enqueues the later stages before the pass-1 record is back,
