@@ -61,7 +61,8 @@ inline Entry pre_entry(int sym, int len) { return make((uint16_t)sym, len, K_LIT
 
 // Canonical Huffman code -> two-level decode table.  table must hold (1 << tbits) + room for the second level
 // (<= 2 * nsyms entries suffice for 15-bit codes over these alphabets).  Returns false for an over-subscribed code, or an
-// incomplete one unless allow_incomplete (DEFLATE permits a single distance code).
+// incomplete one unless allow_incomplete and it is no code at all or a single code of length 1 (what DEFLATE permits for
+// distances; zlib's inflate_table: "max != 1" -- a lone code of two or more bits is an "incomplete distances set").
 template <class MakeEntry>
 bool build_table(const uint8_t* lens, int nsyms, int tbits, Entry* table, int table_cap, MakeEntry mk, bool allow_incomplete) {
     int count[kMaxLen + 1] = {0};
@@ -78,7 +79,7 @@ bool build_table(const uint8_t* lens, int nsyms, int tbits, Entry* table, int ta
     }
     int used = 0;
     for (int l = 1; l <= kMaxLen; ++l) used += count[l];
-    if (left > 0 && !(allow_incomplete && used <= 1)) return false;
+    if (left > 0 && !(allow_incomplete && used == count[1])) return false;  // (left > 0: count[1] <= 1)
     const int tsize = 1 << tbits;
     for (int i = 0; i < tsize; ++i) table[i] = make(0, 1, K_BAD, 0);
     if (used == 0) return true;

@@ -3,6 +3,9 @@
 // bdx-inflate-check --members FILE [AVAIL]: the members the shared parser (bgzf.h) finds in FILE when it may look at the
 // first AVAIL bytes only (default: all) -- one line "offset total payload_off payload_len ulen" each, then "end <offset>
 // <status>" for what ended the walk.  Test tooling for bgzf.h.
+// bdx-inflate-check --each FILE: one line "index zlib_ok fast_ok bytes_equal" per member of FILE, empty ones included; a member that
+// zlib rejects is no failure here (tests/test_deflate_cases.py feeds it members that must be rejected).  fast_inflate reads each payload
+// from a heap copy with exactly the 32 bytes behind it that its callers guarantee, so that a sanitizer build sees a read beyond them.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -47,8 +50,36 @@ static int list_members(const char* path, const char* avail_arg) {
     return 0;
 }
 
+static int each_member(const char* path) {
+    try {
+        const bdhost::MappedFile file(path, false);
+        const uint8_t* m = file.data();
+        const size_t size = file.size();
+        size_t off = 0, index = 0;
+        BgzfMember mem;
+        while (bdhost::bgzf_member_at(m, size, off, path, &mem)) {
+            const size_t coff = off + mem.payload_off, clen = mem.payload_len;
+            const uint32_t ulen = mem.ulen;
+            off += mem.total;
+            std::vector<uint8_t> a((size_t)ulen + 64), b((size_t)ulen + 1);
+            const bool okz = bdhost::bgzf_try_inflate_zlib(m + coff, clen, b.data(), ulen);
+            bool okf = false;
+            if (coff + clen + 32 <= size) {
+                const std::vector<uint8_t> in(m + coff, m + coff + clen + 32);
+                okf = bdhost::fast_inflate(in.data(), clen, a.data(), ulen, 64);
+            }
+            printf("%zu %d %d %d\n", index++, (int)okz, (int)okf, (int)(okz && okf && memcmp(a.data(), b.data(), ulen) == 0));
+        }
+    } catch (std::exception const& e) {
+        fprintf(stderr, "%s\n", e.what());
+        return 2;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !strcmp(argv[1], "--members")) return list_members(argv[2], argc > 3 ? argv[3] : nullptr);
+    if (argc == 3 && !strcmp(argv[1], "--each")) return each_member(argv[2]);
     size_t blocks = 0, bad = 0, rejected = 0, bytes = 0;
     double t_fast = 0, t_zlib = 0;
     std::vector<uint8_t> a(65536 + 64), b(65536 + 64);

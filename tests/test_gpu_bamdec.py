@@ -8,6 +8,7 @@ import zlib
 import numpy as np
 import pytest
 
+from deflate_cases import TokenDeflate
 from helpers import GOLDEN, read_bam
 
 pytestmark = pytest.mark.gpu
@@ -68,79 +69,6 @@ def test_inflate_matches_zlib_on_synthetic_members(kz, monkeypatch):
         assert got == w, "member %d (%s) differs at byte %d" % (i, labels[i], next(k for k in range(len(w)) if got[k] != w[k]))
         o += len(w)
     assert o == len(out)
-
-
-class TokenDeflate:
-    """a DEFLATE writer for chosen token sequences (RFC 1951): zlib picks its own matches, the window tests below need a match of a
-    given length at a given distance right behind given tokens.  One block: the fixed code (3.2.6), or a dynamic block (3.2.7)
-    with the code lengths the caller gives (complete codes; sent without run lengths)"""
-    LBASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
-    LEXTRA = [0] * 8 + [1] * 4 + [2] * 4 + [3] * 4 + [4] * 4 + [5] * 4 + [0]
-    DBASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577]
-    DEXTRA = [0, 0, 0, 0] + [i // 2 for i in range(2, 28)]
-
-    @staticmethod
-    def canonical(lens):   # symbol -> (code, length), RFC 1951 3.2.2
-        code, out = 0, {}
-        for l in range(1, 16):
-            for s, x in enumerate(lens):
-                if x == l:
-                    out[s] = (code, l)
-                    code += 1
-            code <<= 1
-        return out
-
-    def __init__(self, lit_lens=None, dist_lens=None):
-        self.acc, self.nbits, self.out, self.data = 0, 0, bytearray(), bytearray()
-        self.bits(1, 1)   # BFINAL
-        if lit_lens is None:
-            self.bits(1, 2)
-            lit_lens = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8
-            dist_lens = [5] * 30
-        else:
-            assert len(lit_lens) == 286 and len(dist_lens) == 30
-            assert sum(2.0 ** -l for l in lit_lens if l) == 1.0 and sum(2.0 ** -l for l in dist_lens if l) == 1.0
-            self.bits(2, 2)
-            self.bits(286 - 257, 5); self.bits(30 - 1, 5); self.bits(19 - 4, 4)
-            for sym in (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15):   # the code-length code: 0..15 in four bits each
-                self.bits(0 if sym >= 16 else 4, 3)
-            for l in list(lit_lens) + list(dist_lens):
-                self.code(l, 4)
-        self.lit, self.dist = self.canonical(lit_lens), self.canonical(dist_lens)
-
-    def bits(self, v, n):   # n bits of v, least significant first
-        self.acc |= (v & ((1 << n) - 1)) << self.nbits
-        self.nbits += n
-        while self.nbits >= 8:
-            self.out.append(self.acc & 255)
-            self.acc >>= 8
-            self.nbits -= 8
-
-    def code(self, c, n):   # a Huffman code: most significant bit first
-        self.bits(int(format(c, "0%db" % n)[::-1], 2), n)
-
-    def literal(self, b):
-        self.code(*self.lit[b])
-        self.data.append(b)
-
-    def match(self, length, dist):
-        assert 3 <= length <= 258 and 1 <= dist <= len(self.data) and dist <= 32768
-        ls = max(i for i in range(29) if self.LBASE[i] <= length) if length < 258 else 28
-        self.code(*self.lit[257 + ls])
-        self.bits(length - self.LBASE[ls], self.LEXTRA[ls])
-        ds = max(i for i in range(30) if self.DBASE[i] <= dist)
-        self.code(*self.dist[ds])
-        self.bits(dist - self.DBASE[ds], self.DEXTRA[ds])
-        for _ in range(length):
-            self.data.append(self.data[-dist])
-
-    def finish(self):
-        self.code(*self.lit[256])
-        if self.nbits: self.bits(0, 8 - self.nbits)
-        data, comp = bytes(self.data), bytes(self.out)
-        assert zlib.decompress(comp, -15) == data
-        return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", len(comp) + 25) + comp +
-                struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data))), data
 
 
 # a dynamic code whose longest matches have codes beyond any primary table (length 258: 10 bits; lengths 3..10: 4..10 bits), a match
@@ -294,6 +222,41 @@ def test_inflate_verdict_on_corrupted_members_agrees_with_zlib(kz, monkeypatch):
             stricter += 1
         o += n
     assert stricter <= len(verdicts) // 20   # (zlib tolerates garbage behind the final block; so does the kernel -- nearly always the same verdict)
+
+
+@KZ
+def test_inflate_verdict_on_the_hand_built_corpus_is_zlibs(kz, monkeypatch):
+    """tests/deflate_cases.py in one launch: codes of every length up to 15 bits, stored blocks between Huffman blocks, headers at the edges
+    of RFC 1951 3.2.7, and members that have to be refused for one stated reason each (test_deflate_cases.py holds the labels to zlib and
+    shows what the corpus reaches).  Every valid member: status 0 and zlib's bytes; every reject: a status -- no allowance for being
+    stricter.  Payloads lie at every alignment, and every valid member has a rejected neighbour (whose output bytes, never cleared on the
+    device, are not looked at)"""
+    import deflate_cases as D
+    from breakdancer_amd import bamdec
+    cases = D.interleaved(D.corpus())
+    rng = np.random.default_rng(13)
+    image, rows = bytearray(), []
+    for i, (label, payload, ulen, want) in enumerate(cases):
+        image += rng.integers(0, 256, i % 8, dtype=np.uint8).tobytes()
+        rows.append((0, len(image), len(payload), ulen))
+        image += payload
+    members = np.array(rows, dtype=[("member", "<u8"), ("payload", "<u8"), ("payload_len", "<u4"), ("inflated_len", "<u4")])
+    assert {int(x) % 8 for x in members["payload"]} == set(range(8))
+    valid = [c[3] is not None for c in cases]
+    assert all(not valid[i] or (i > 0 and not valid[i - 1]) or (i + 1 < len(cases) and not valid[i + 1]) for i in range(len(cases)))
+    out, status, ms = bamdec.inflate_blocks(bytes(image), members)
+    wrong, o = [], 0
+    for i, (label, payload, ulen, want) in enumerate(cases):
+        got = out[o:o + ulen].tobytes()
+        o += ulen
+        if want is None:
+            if status[i] == 0: wrong.append("%s: accepted" % label)
+        elif status[i] != 0:
+            wrong.append("%s: rejected with status %d" % (label, status[i]))
+        elif got != want:
+            wrong.append("%s: differs at byte %d of %d" % (label, next(k for k in range(ulen) if got[k] != want[k]), ulen))
+    assert o == len(out)
+    assert not wrong, "%d of %d members:\n%s" % (len(wrong), len(cases), "\n".join(wrong))
 
 
 # ---- records ----
