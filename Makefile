@@ -4,11 +4,11 @@ ARCH ?= gfx950
 CSRC := breakdancer_amd/csrc
 HOST := breakdancer_amd/host
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Iinclude
-KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/k8_junction.hip $(CSRC)/ks_sites.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/bdx_api.hip
+KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/k8_junction.hip $(CSRC)/ks_sites.hip $(CSRC)/ki_bounds.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/bdx_api.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
 HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp
 
-all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-feed-probe oracle
+all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-feed-probe oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -37,6 +37,11 @@ bin/bdx-sites-check: $(HOST)/sites_check_main.cpp $(HOST)/sites.cpp $(HOST)/site
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/sites_check_main.cpp $(HOST)/sites.cpp
 
+# test tooling: --ci's interval arithmetic (vcf.cpp) on its own (tests/test_ci.py builds it a second time under a sanitizer)
+bin/bdx-ci-check: $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h
+	@mkdir -p bin
+	g++ $(HOSTFLAGS) -o $@ $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp
+
 # measurement tool (bench.py): the feeder's ceilings -- page cache -> pinned -> HBM
 bin/bdx-feed-probe: tools/feed_probe.hip
 	@mkdir -p bin
@@ -54,7 +59,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-sites-check
+	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-sites-check bin/bdx-ci-check
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -313,6 +313,22 @@ class BreakDancer:
         self._chk(self.lib.bdx_count_site_pairs(self.h, p(s), len(s), int(window), int(bool(by_library)), p(out)), "bdx_count_site_pairs")
         return out
 
+    def site_breakpoint_bounds(self, sites, window):
+        """Breakpoint intervals of given SV sites from the supporting pairs of the last run (bdx_site_breakpoint_bounds; the rule is in
+        include/bdx.h): `sites` and `window` as for count_site_pairs, whose records -- all keys pooled -- are the ones that count.  Each
+        bounds the breakpoint at either end by where its read there starts, its strand and its library's uppercutoff.  Returns an array
+        of _lib.SITE_BOUNDS_DTYPE: n, and per end the largest lower bound lo and the smallest upper bound hi (1-based; lo > hi when the
+        pairs contradict each other; all 0 with n == 0)."""
+        if isinstance(sites, np.ndarray) and sites.dtype == L.SITE_DTYPE:
+            s = np.ascontiguousarray(sites)
+        else:
+            rows = [tuple(int(v) for v in r) for r in sites]
+            s = np.array(rows, dtype=L.SITE_DTYPE) if rows else np.zeros(0, dtype=L.SITE_DTYPE)
+        out = np.zeros(len(s), dtype=L.SITE_BOUNDS_DTYPE)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.bdx_site_breakpoint_bounds(self.h, p(s), len(s), int(window), p(out)), "bdx_site_breakpoint_bounds")
+        return out
+
     def set_stage_timing(self, on=True):
         """HIP events between the stages (compact / regions / join timings); costs a few microseconds per event."""
         self._chk(self.lib.bdx_set_stage_timing(self.h, int(on)), "bdx_set_stage_timing")

@@ -198,6 +198,8 @@ struct bdx_ctx {
     DevBuf b_jq, b_jc;                // its queries and counts
     // ---- bdx_count_site_pairs ----
     DevBuf b_sq, b_sc;                // its sites and counts
+    // ---- bdx_site_breakpoint_bounds ----
+    DevBuf b_iq, b_io, b_iu;          // its sites, bounds and the libraries' U table
     // ---- bdx_set_mark_duplicates ----
     bool mark_dup = false;            // KD marks duplicates in the flag column at the head of pass 1; pass 1 then does not start behind arriving batches
     bool dup_done = false;            // KD has run over this load (nothing can be appended to it any more)
@@ -2204,12 +2206,14 @@ int bdx_count_junction_pairs(bdx_ctx* c, const int32_t* tid, const int32_t* pos_
     return BDX_OK;
 }
 
-int bdx_count_site_pairs(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, int by_library, uint32_t* counts) {
+// What bdx_count_site_pairs and bdx_site_breakpoint_bounds check before they touch the device, in this order.  *none: n == 0, nothing to do.
+static int check_site_call(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, const void* out, bool* none) {
+    *none = false;
     if (!c) return BDX_EINVAL;
     NOT_WHILE_SIZING(c);
     if (c->cls_n != c->n && !(c->ran && c->n == 0)) return fail(c, BDX_ESTATE, "no run has classified the reads this context holds");
-    if (n == 0) return BDX_OK;
-    if (!sites || !counts) return fail(c, BDX_EINVAL, "null array");
+    if (n == 0) { *none = true; return BDX_OK; }
+    if (!sites || !out) return fail(c, BDX_EINVAL, "null array");
     if (window < 0 || window > (1 << 30)) return fail(c, BDX_EINVAL, "window < 0 or window > 2^30");
     if (n > ((size_t)1 << 31)) return fail(c, BDX_ELIMIT, "more than 2^31 sites in one call");
     for (size_t i = 0; i < n; ++i) {
@@ -2221,6 +2225,13 @@ int bdx_count_site_pairs(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t wi
         if (s.flag_mask == 0 || (s.flag_mask & ~BDX_SITE_FLAGS))
             return fail(c, BDX_EINVAL, "site " + std::to_string(i) + ": flag_mask is 0 or has a bit outside the anomalous classes");
     }
+    return BDX_OK;
+}
+
+int bdx_count_site_pairs(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, int by_library, uint32_t* counts) {
+    bool none;
+    BDX_TRY(check_site_call(c, sites, n, window, counts, &none));
+    if (none) return BDX_OK;
     const int nkeys = by_library ? c->nlibs : c->nbams;
     // (a context with one library / one file never copies the respective column: every read is key 0 there)
     const uint8_t* key = nkeys > 1 ? (by_library ? c->d.lib : c->d.bam) : nullptr;
@@ -2241,6 +2252,40 @@ int bdx_count_site_pairs(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t wi
     return BDX_OK;
 }
 
+int bdx_site_breakpoint_bounds(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, bdx_site_bounds* out) {
+    bool none;
+    BDX_TRY(check_site_call(c, sites, n, window, out, &none));
+    if (none) return BDX_OK;
+    // U per library: ceil(uppercutoff); 0 when that is negative; 2^30 when the cutoff is NaN, infinite or above 2^30
+    std::vector<uint32_t> u(c->libs.size());
+    for (size_t i = 0; i < u.size(); ++i) {
+        const double v = (double)c->libs[i].uppercutoff;
+        u[i] = !std::isfinite(v) || v > 1073741824.0 ? (1u << 30) : (v < 0 ? 0u : (uint32_t)std::ceil(v));
+    }
+    const int nlibs = c->nlibs;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t obytes = n * sizeof(bdx_site_bounds);
+    HIPCHK(c, c->b_iq.ensure(n * sizeof(bdx_site)));
+    HIPCHK(c, c->b_io.ensure(obytes));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->b_iq.p, sites, n * sizeof(bdx_site), hipMemcpyHostToDevice, s));
+    KiParams p{};
+    if (nlibs > 1) {   // (a context with one library never copies the lib column, and its U travels with the launch)
+        HIPCHK(c, c->b_iu.ensure(u.size() * 4));
+        HIPCHK(c, hipMemcpyAsync(c->b_iu.p, u.data(), u.size() * 4, hipMemcpyHostToDevice, s));
+        p.lib = c->d.lib; p.utab = c->b_iu.as<uint32_t>();
+    }
+    p.tid = c->d.tid; p.pos = c->d.pos; p.mtid = c->d.mtid; p.mpos = c->d.mpos; p.flag = c->d.flag;
+    p.cls = c->b_cls.as<uint8_t>(); p.n = c->n;
+    p.sites = c->b_iq.as<KsSite>(); p.nq = (uint32_t)n; p.nlibs = nlibs; p.window = window;
+    p.long_insert = c->opts.illumina_long_insert ? 1 : 0; p.u0 = u.empty() ? 0u : u[0]; p.out = c->b_io.as<KiBounds>();
+    launch_ki(p, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, p.out, obytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return BDX_OK;
+}
+
 int bdx_set_process_option(const char* name, int value) {
     if (!name) return BDX_EINVAL;
     if (!strcmp(name, "pin_malloc")) { PinBuf::registered_switch().store(value == 0); return BDX_OK; }
@@ -2250,7 +2295,7 @@ int bdx_set_process_option(const char* name, int value) {
 int bdx_warm_up(int device) {
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
     warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k8(nullptr);
-    warm_k9(nullptr); warm_kx(nullptr); warm_ks(nullptr);
+    warm_k9(nullptr); warm_kx(nullptr); warm_ks(nullptr); warm_ki(nullptr);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? BDX_OK : BDX_EHIP;
 }
 

@@ -222,6 +222,27 @@ struct KsParams {
     uint32_t* counts;                   // [nq][nkeys]
 };
 
+// KI (ki_bounds.hip): breakpoint intervals of given SV sites from the records KS counts, keys pooled (bdx_site_breakpoint_bounds)
+struct KiBounds {                       // = bdx_site_bounds (include/bdx.h)
+    uint32_t n;                         // the records that count for the site
+    int32_t lo1, hi1, lo2, hi2;         // per end: the largest lower and the smallest upper bound, 1-based; all 0 with n == 0
+};
+struct KiParams {
+    const int32_t *tid, *pos, *mtid, *mpos;   // the resident store, sorted by (tid, pos)
+    const uint16_t* flag;               // SAM flags
+    const uint8_t* lib;                 // library column; read only when nlibs > 1
+    const uint8_t* cls;                 // K1's class bytes
+    uint64_t n;
+    const KsSite* sites;
+    uint32_t nq;
+    int nlibs;                          // 1..255
+    int32_t window;                     // 0..2^30
+    int32_t long_insert;                // -l: reads point away from their fragment
+    uint32_t u0;                        // library 0's insert-size bound U (0..2^30) ...
+    const uint32_t* utab;               // ... and every library's [nlibs]; read only when nlibs > 1
+    KiBounds* out;                      // [nq]
+};
+
 // KD (kd_markdup.hip): duplicate marking over the resident store (bdx_set_mark_duplicates, bdx_mark_duplicates)
 constexpr int kDupT = 64;               // neighbours a record looks at each way; runs of more records go through the table
 struct KdCounts {
@@ -255,6 +276,7 @@ void launch_kd_apply(const KdParams& p, uint16_t* flag, uint8_t* mask, hipStream
 // launchers (host side, defined in the .hip files)
 void launch_k8(const K8Params& p, hipStream_t s);
 void launch_ks(const KsParams& p, hipStream_t s);
+void launch_ki(const KiParams& p, hipStream_t s);
 void launch_k1(const K1Params& p, int grid, size_t lds, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 size_t k1_lds_bytes(int nlibs, int nbams, int nkeys);
 void launch_finalize(const FinalizeParams& p, hipStream_t s, bool second_level = true);

@@ -1,4 +1,4 @@
-// The 64-ary ballot search of the kernels that answer queries over the resident store (K8, k8_junction.hip; KS, ks_sites.hip).
+// The 64-ary ballot search of the kernels that answer queries over the resident store (K8, k8_junction.hip; KS, ks_sites.hip; KI, ki_bounds.hip).
 #pragma once
 #include "bdx_dev.h"
 

@@ -318,6 +318,59 @@ std::vector<VcfRecord> site_records(const Options& opts, const BamConfig& cfg, c
     return out;
 }
 
+// --ci: CIPOS / CIEND of --vcf and --sites-vcf records.  Each record becomes a site -- its two ends put into order, its mask the read
+// classes that print as its type (Options::sv_flag_mask, the mapping --sites uses) -- whose supporting pairs bound the breakpoint at
+// either end (KI, bdx_site_breakpoint_bounds; a sharded run's sites on the rank that holds tid1, as for KS).  An end that was swapped
+// for normalisation is swapped back.  No CI for a record with an end on a chromosome the run did not read, a position below 1, a type no
+// read class maps to, or no supporting pair.
+void fill_ci(const Options& opts, const RunContexts& rc, int32_t window, std::vector<VcfRecord>& out) {
+    constexpr size_t kWords = sizeof(bdx_site_bounds) / 4;   // (count_on_ranks moves rows of 32-bit words: a site's bounds are five)
+    static_assert(sizeof(bdx_site_bounds) == 20 && alignof(bdx_site_bounds) == 4, "bdx_site_bounds is five 32-bit words");
+    std::vector<bdx_site> q;
+    std::vector<int32_t> q_tid;
+    std::vector<size_t> q_row;
+    std::vector<char> q_swapped;
+    for (size_t k = 0; k < out.size(); ++k) {
+        const VcfRecord& r = out[k];
+        const uint32_t mask = opts.sv_flag_mask(r.type);
+        if (!rc.held(r.chr1) || !rc.held(r.chr2) || r.pos1 < 1 || r.pos2 < 1 || mask == 0) continue;
+        const bool swapped = r.chr1 > r.chr2 || (r.chr1 == r.chr2 && r.pos1 > r.pos2);
+        q.push_back(swapped ? bdx_site{r.chr2, r.pos2, r.chr1, r.pos1, mask} : bdx_site{r.chr1, r.pos1, r.chr2, r.pos2, mask});
+        q_tid.push_back(q.back().tid1); q_row.push_back(k); q_swapped.push_back(swapped ? 1 : 0);
+    }
+    std::vector<uint32_t> words;
+    count_on_ranks(rc, q_tid, kWords, "bdx_site_breakpoint_bounds", words, [&](bdx_ctx* c, const std::vector<size_t>& m, uint32_t* w) {
+        std::vector<bdx_site> mine(m.size());
+        for (size_t j = 0; j < m.size(); ++j) mine[j] = q[m[j]];
+        std::vector<bdx_site_bounds> b(m.size());
+        const int st = bdx_site_breakpoint_bounds(c, mine.data(), m.size(), window, b.data());
+        if (st == BDX_OK) memcpy(w, b.data(), b.size() * sizeof(bdx_site_bounds));
+        return st;
+    });
+    for (size_t i = 0; i < q.size(); ++i) {
+        bdx_site_bounds b;
+        memcpy(&b, words.data() + i * kWords, sizeof b);
+        if (b.n == 0) continue;
+        VcfRecord& r = out[q_row[i]];
+        r.has_ci = true;
+        r.ci_n = b.n;
+        r.ci_lo1 = q_swapped[i] ? b.lo2 : b.lo1; r.ci_hi1 = q_swapped[i] ? b.hi2 : b.hi1;
+        r.ci_lo2 = q_swapped[i] ? b.lo1 : b.lo2; r.ci_hi2 = q_swapped[i] ? b.hi1 : b.hi2;
+    }
+}
+
+// How far a supporting mate can start from a breakpoint it brackets: the ceiling of the largest finite library uppercutoff, the window
+// of --sites and --ci when theirs is not given.
+int32_t cutoff_window(const BamConfig& cfg, const char* option) {
+    double ub = -1.0;
+    for (size_t i = 0; i < cfg.num_libs(); ++i) {
+        const double u = cfg.library_config(i).uppercutoff;
+        if (std::isfinite(u)) ub = std::max(ub, std::ceil(u));
+    }
+    if (ub < 0) throw std::runtime_error(std::string(option) + ": no library has a finite uppercutoff, give " + option + "-window");
+    return (int32_t)std::min(ub, 1073741824.0);
+}
+
 }  // namespace
 
 // Releasing a GPU context takes the driver longer than the whole GPU path runs, and a process cannot return before its resources
@@ -428,16 +481,10 @@ int run(int argc, char** argv) {
             std::vector<std::pair<std::string, uint32_t>> type_masks;
             for (const char* t : kSiteTypes) type_masks.emplace_back(t, opts.sv_flag_mask(t));
             read_sites(opts.sites, names, type_masks, site_table);
-            if (sites_window < 0) {   // how far a supporting mate can start from a breakpoint it brackets: the largest library cutoff
-                double ub = -1.0;
-                for (size_t i = 0; i < cfg.num_libs(); ++i) {
-                    const double u = cfg.library_config(i).uppercutoff;
-                    if (std::isfinite(u)) ub = std::max(ub, std::ceil(u));
-                }
-                if (ub < 0) throw std::runtime_error("--sites: no library has a finite uppercutoff, give --sites-window");
-                sites_window = (int32_t)std::min(ub, 1073741824.0);
-            }
+            if (sites_window < 0) sites_window = cutoff_window(cfg, "--sites");
         }
+        // --ci: its window is settled here as well -- without a finite cutoff the run ends before the GPU is touched
+        const int32_t ci_window = !opts.ci ? 0 : opts.ci_window >= 0 ? opts.ci_window : cutoff_window(cfg, "--ci");
         // Decode threads: the work is CPU-bound on zlib (~375 MB/s of inflated bytes per core), so what counts is the number of
         // cores this process may really use -- the cgroup's CPU quota when there is one (a container with "16 CPUs" on a
         // 256-thread host: 16 threads 0.64 s, 32 0.55 s, 64 0.70 s for 15 M records), else the hardware threads.  Twice that
@@ -666,6 +713,17 @@ int run(int argc, char** argv) {
                     fprintf(stderr, "[bdx timing] --sites: pair and junction counts of %zu sites (window %d, %zu lines on unknown sequences ignored) %.4f s\n",
                             site_table.sites.size(), sites_window, site_table.unknown_lines, secs(tv, now()));
             }
+            if (opts.ci) {
+                const auto tv = now();
+                fill_ci(opts, rc, ci_window, vcf_rows);
+                fill_ci(opts, rc, ci_window, site_rows);
+                size_t with = 0;
+                for (auto const* rows : {&vcf_rows, &site_rows})
+                    for (auto const& r : *rows) with += r.has_ci;
+                if (timing)
+                    fprintf(stderr, "[bdx timing] --ci: breakpoint bounds of %zu records (window %d, %zu with supporting pairs) %.4f s\n",
+                            vcf_rows.size() + site_rows.size(), ci_window, with, secs(tv, now()));
+            }
         }
 
         // (a large run's pinned result tables go back while the table is printed: the process's end is that much shorter.  BDX_TRIM=0: kept)
@@ -816,11 +874,13 @@ int run(int argc, char** argv) {
                     const size_t p = b.rfind("/");
                     samples.push_back(p != std::string::npos ? b.substr(p + 1) : b);
                 }
-            if (vcf) vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(vcf_rows), opts.exclude, nullptr, opts.mark_dup);
+            const VcfCi ci_info{ci_window};
+            const VcfCi* ci = opts.ci ? &ci_info : nullptr;
+            if (vcf) vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(vcf_rows), opts.exclude, nullptr, opts.mark_dup, ci);
             vcf.reset();
             if (sites_vcf) {
                 const VcfSites info{opts.sites, sites_window};
-                sites_vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(site_rows), opts.exclude, &info, opts.mark_dup);
+                sites_vcf->write(opts.orig_argv, contigs, lengths, samples, std::move(site_rows), opts.exclude, &info, opts.mark_dup, ci);
             }
             sites_vcf.reset();
         }

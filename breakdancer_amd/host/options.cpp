@@ -65,6 +65,8 @@ void print_usage(const bdx_opts& o) {
     fprintf(stderr, "       --sites FILE   genotype the SV sites of this table (the tool's own output columns) over the records the run holds\n");
     fprintf(stderr, "       --sites-vcf FILE   the VCF the --sites genotypes are written to (GT:GQ:PL:DR:DV; required with --sites)\n");
     fprintf(stderr, "       --sites-window INT how far from a breakpoint a supporting read may start [the largest library uppercutoff]\n");
+    fprintf(stderr, "       --ci           add CIPOS / CIEND (and CIN) to every --vcf / --sites-vcf record: the breakpoint intervals its supporting pairs allow\n");
+    fprintf(stderr, "       --ci-window INT    how far from a breakpoint a supporting read of --ci may start [the largest library uppercutoff]\n");
     fprintf(stderr, "       --mark-dup     flag duplicate read pairs (same library, positions and strands of both mates) on the GPU; they are ignored like reads with SAM flag 0x400\n");
     fprintf(stderr, "\n");
 }
@@ -75,10 +77,11 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
     // (the reference's letters parse exactly as with getopt; the long options are this tool's own)
-    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup };
+    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow };
     static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude},
                                          {"sites", required_argument, nullptr, kSites}, {"sites-vcf", required_argument, nullptr, kSitesVcf},
                                          {"sites-window", required_argument, nullptr, kSitesWindow}, {"mark-dup", no_argument, nullptr, kMarkDup},
+                                         {"ci", no_argument, nullptr, kCi}, {"ci-window", required_argument, nullptr, kCiWindow},
                                          {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
@@ -102,14 +105,18 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
             sites_vcf = optarg;
             continue;
         }
-        if (c == kSitesWindow) {
+        if (c == kCi) {
+            ci = true;
+            continue;
+        }
+        if (c == kSitesWindow || c == kCiWindow) {
             char* end = nullptr;
             const long v = strtol(optarg, &end, 10);
             if (end == optarg || *end || v < 0 || v > (1L << 30)) {
-                fprintf(stderr, "--sites-window takes an integer from 0 to 2^30, not '%s'.\n", optarg);
+                fprintf(stderr, "--%s-window takes an integer from 0 to 2^30, not '%s'.\n", c == kCiWindow ? "ci" : "sites", optarg);
                 exit(1);
             }
-            sites_window = (int)v;
+            (c == kCiWindow ? ci_window : sites_window) = (int)v;
             continue;
         }
         const Row* row = nullptr;
@@ -131,6 +138,10 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     }
     if (sites.empty() != sites_vcf.empty() || (sites.empty() && sites_window >= 0)) {
         fprintf(stderr, "--sites FILE and --sites-vcf FILE go together (and --sites-window with them).\n");
+        exit(1);
+    }
+    if ((ci && vcf.empty() && sites_vcf.empty()) || (!ci && ci_window >= 0)) {
+        fprintf(stderr, "--ci needs --vcf FILE or --sites-vcf FILE to write to (and --ci-window goes with --ci).\n");
         exit(1);
     }
     o.chr_restricted = chr.empty() ? 0 : 1;

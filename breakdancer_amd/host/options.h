@@ -1,6 +1,6 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
 // (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf, --exclude, --sites / --sites-vcf /
-// --sites-window and --mark-dup.
+// --sites-window, --mark-dup and --ci / --ci-window.
 #pragma once
 #include <string>
 #include <vector>
@@ -22,6 +22,8 @@ struct Options {
     std::string sites_vcf;       // --sites-vcf: ... and the VCF they are written to (one needs the other)
     bool mark_dup = false;       // --mark-dup: duplicate read pairs get SAM flag 0x400 on the GPU before pass 1 (bdx_set_mark_duplicates)
     int sites_window = -1;       // --sites-window: how far from a breakpoint a supporting read may start (-1: from the libraries' cutoffs)
+    bool ci = false;             // --ci: CIPOS / CIEND / CIN of every --vcf / --sites-vcf record from its supporting pairs (bdx_site_breakpoint_bounds)
+    int ci_window = -1;          // --ci-window: how far from a breakpoint such a pair's read may start (-1: from the libraries' cutoffs)
     bdx_opts o;                  // numeric options in the C-ABI layout
     std::vector<std::string> orig_argv;
     int device = 0;              // env BDX_DEVICE

@@ -25,6 +25,13 @@ Genotype call_genotype(int64_t dr, int64_t dv) {
     return g;
 }
 
+CiOffsets ci_offsets(int64_t lo, int64_t hi, int64_t P) {
+    CiOffsets c;
+    c.a = std::min({lo, hi, P}) - P;
+    c.b = std::max({lo, hi, P}) - P;
+    return c;
+}
+
 VcfWriter::VcfWriter(const std::string& path) : path_(path) {
     f_ = fopen(path.c_str(), "w");
     if (!f_) throw std::runtime_error("unable to open VCF output file '" + path + "'");
@@ -36,7 +43,7 @@ VcfWriter::~VcfWriter() {
 
 void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                       const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude,
-                      const VcfSites* sites, bool mark_dup) {
+                      const VcfSites* sites, bool mark_dup, const VcfCi* ci) {
     if (!f_) throw std::runtime_error("VCF output file '" + path_ + "' is already closed");
     FILE* f = f_;
     fprintf(f, "##fileformat=VCFv4.2\n##source=breakdancer-max-mi355x\n##command=");
@@ -45,6 +52,7 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
     if (!exclude.empty()) fprintf(f, "##exclude=%s\n", exclude.c_str());
     if (sites) fprintf(f, "##sites=%s\n##sites_window=%d\n", sites->file.c_str(), sites->window);
     if (mark_dup) fprintf(f, "##mark_dup=1\n");
+    if (ci) fprintf(f, "##ci_window=%d\n", ci->window);
     for (size_t t = 0; t < contigs.size(); ++t)
         fprintf(f, "##contig=<ID=%s,length=%u>\n", contigs[t].c_str(), t < lengths.size() ? lengths[t] : 0u);
     fputs("##FILTER=<ID=PASS,Description=\"All filters passed\">\n"
@@ -65,6 +73,12 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
               "##INFO=<ID=ORI2,Number=1,Type=String,Description=\"Reads on the + and - strand at the second breakpoint (Orientation2)\">\n"
               "##INFO=<ID=NREADS,Number=1,Type=Integer,Description=\"Read pairs supporting the call (num_Reads)\">\n"
               "##INFO=<ID=BDAF,Number=1,Type=Float,Description=\"BreakDancer allele frequency (Allele_frequency)\">\n",
+              f);
+    if (ci)
+        fputs("##INFO=<ID=CIPOS,Number=2,Type=Integer,Description=\"Confidence interval around POS: the breakpoint interval the supporting pairs' reads allow (read start, strand, library uppercutoff)\">\n"
+              "##INFO=<ID=CIEND,Number=2,Type=Integer,Description=\"Confidence interval around END, likewise\">\n"
+              "##INFO=<ID=CIPOS2,Number=2,Type=Integer,Description=\"Confidence interval around POS2, likewise (records without END)\">\n"
+              "##INFO=<ID=CIN,Number=1,Type=Integer,Description=\"Read pairs the confidence intervals come from: those with one mate starting within ci_window of each breakpoint\">\n",
               f);
     fputs("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
           "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: second-smallest PL, capped at 99\">\n"
@@ -91,6 +105,11 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
             fprintf(f, ";ORI1=%s;ORI2=%s;NREADS=%d;BDAF=", r.ori1.c_str(), r.ori2.c_str(), r.nreads);
             if (std::isfinite(r.af)) fprintf(f, "%.6g", (double)r.af);
             else fputs(".", f);
+        }
+        if (ci && r.has_ci) {
+            const CiOffsets c1 = ci_offsets(r.ci_lo1, r.ci_hi1, r.pos1), c2 = ci_offsets(r.ci_lo2, r.ci_hi2, r.pos2);
+            fprintf(f, ";CIPOS=%lld,%lld;%s=%lld,%lld;CIN=%u", (long long)c1.a, (long long)c1.b, r.chr2 == r.chr1 && r.pos2 >= r.pos1 ? "CIEND" : "CIPOS2",
+                    (long long)c2.a, (long long)c2.b, r.ci_n);
         }
         fputs("\tGT:GQ:PL:DR:DV", f);
         for (size_t k = 0; k < samples.size(); ++k) {

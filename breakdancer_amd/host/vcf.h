@@ -3,6 +3,8 @@
 // over the run's resident records (bdx_count_junction_pairs).
 // --sites-vcf: the same writer for given sites (sites.h) -- there DV is counted on the GPU as well (bdx_count_site_pairs), a record has
 // no score, orientation counts, NREADS or BDAF, and its ID is SITE<k>.
+// --ci: either output's records gain CIPOS / CIEND (CIPOS2 where the record prints no END) and CIN from the breakpoint bounds their
+// supporting pairs give (bdx_site_breakpoint_bounds).
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -22,6 +24,14 @@ struct Genotype {
 };
 Genotype call_genotype(int64_t dr, int64_t dv);
 
+// --ci: the confidence interval around an end printed at P whose supporting pairs bound the breakpoint below by lo and above by hi
+// (1-based; lo > hi: the pairs contradict each other), as offsets from P: a = min(lo, hi, P) - P, b = max(lo, hi, P) - P.  So a <= 0 <= b
+// always, and a contradictory cluster shows as the span of its contradiction.
+struct CiOffsets {
+    int64_t a = 0, b = 0;
+};
+CiOffsets ci_offsets(int64_t lo, int64_t hi, int64_t P);
+
 // one printed row of the table
 struct VcfRecord {
     size_t row = 0;                  // 1-based row number among the printed rows (ID = BDX<row>)
@@ -31,12 +41,20 @@ struct VcfRecord {
     float af = 0;
     std::vector<int64_t> dr, dv;     // per sample; < 0: unknown ('.')
     bool has_size = true;            // (a site: the table it came from had a numeric Size column; no SVLEN without)
+    bool has_ci = false;             // --ci: the record's supporting pairs bound its breakpoints (none do: no CI keys) ...
+    uint32_t ci_n = 0;               // ... their number (CIN) ...
+    int ci_lo1 = 0, ci_hi1 = 0, ci_lo2 = 0, ci_hi2 = 0;   // ... and the bounds at (chr1, pos1) and at (chr2, pos2), as the record prints its ends
 };
 
 // what makes an output a --sites-vcf one: the records are given sites (ID SITE<row>, QUAL '.', INFO without ORI1 / ORI2 / NREADS / BDAF)
 struct VcfSites {
     std::string file;                // --sites, for the ##sites= line
     int32_t window = 0;              // the window the pairs were counted with, for ##sites_window=
+};
+
+// what makes an output a --ci one: the ##ci_window= line and the CIPOS / CIEND / CIPOS2 / CIN header lines
+struct VcfCi {
+    int32_t window = 0;              // the window the supporting pairs were looked for with
 };
 
 class VcfWriter {
@@ -48,10 +66,11 @@ public:
     VcfWriter& operator=(const VcfWriter&) = delete;
     // header + records, sorted by (chr1, pos1) with ties in row order; `contigs` are the reference sequences (names are also the
     // records' CHROM / CHR2 values); exclude: the --exclude file of the run ("": none) for the ##exclude= line; sites: non-null for a
-    // --sites-vcf output; mark_dup: the run marked duplicates (--mark-dup), for the ##mark_dup=1 line; the file is closed afterwards
+    // --sites-vcf output; mark_dup: the run marked duplicates (--mark-dup), for the ##mark_dup=1 line; ci: non-null for a run
+    // with --ci; the file is closed afterwards
     void write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude = "",
-               const VcfSites* sites = nullptr, bool mark_dup = false);
+               const VcfSites* sites = nullptr, bool mark_dup = false, const VcfCi* ci = nullptr);
 
 private:
     std::string path_;

@@ -523,6 +523,31 @@ int bdx_count_junction_pairs(bdx_ctx* ctx, const int32_t* tid, const int32_t* po
 typedef struct bdx_site { int32_t tid1, pos1, tid2, pos2; uint32_t flag_mask; } bdx_site;
 int bdx_count_site_pairs(bdx_ctx* ctx, const bdx_site* sites, size_t n, int32_t window, int by_library, uint32_t* counts); /* [n][nkeys] */
 
+/* Breakpoint intervals of GIVEN SV sites from their supporting pairs: no counterpart in the reference (CIPOS / CIEND of the CLI's --ci).
+ * A read of a supporting pair lies wholly on one side of the breakpoint its fragment crosses, and the fragment reaches no further than
+ * its library's uppercutoff from the read's start; intersecting those one-read intervals over a site's supporting pairs is the classical
+ * paired-end breakpoint interval.  The rule, written down here once:
+ *   WHICH RECORDS   sites, window, the context's state and every argument error are those of bdx_count_site_pairs, checked in the same
+ *                   order.  The records that count for site i are exactly the records bdx_count_site_pairs counts for it, all keys pooled;
+ *                   out[i].n is their number (the row sum of bdx_count_site_pairs for either key choice).
+ *   OBSERVATIONS    a counting record gives one observation (x, reverse, U) to each end of the site.  By the forward route (it is near pos1,
+ *                   its mate near pos2): end 1 gets (pos, flag & 0x10, U), end 2 gets (mpos, flag & 0x20, U).  By the reverse route only:
+ *                   end 1 gets (mpos, flag & 0x20, U), end 2 gets (pos, flag & 0x10, U).  A record that matches both routes is taken by
+ *                   the forward route, once.  U belongs to the record's library (lib; an index out of range is library 0): ceil(uppercutoff),
+ *                   0 when that is negative, 2^30 when the cutoff is NaN, infinite or above 2^30.  With opts.illumina_long_insert (-l) reads
+ *                   point away from their fragment: `reverse` is inverted.
+ *   INTERVALS       with P = x + 1 (64-bit arithmetic) a forward read bounds the breakpoint to [P, P + U], a reverse read to [P - U, P].
+ *   BOUNDS          lo_e is the maximum of the lower bounds of end e's observations, hi_e the minimum of their upper bounds; both are
+ *                   clamped to [1, 2^31 - 1] at the end.  With n == 0 all four are 0.  lo_e > hi_e is a legitimate result -- the pairs
+ *                   contradict each other, as when an aligner lets a read overhang the junction -- and is reported as it is.
+ * Only what the record itself carries is looked at (as in the other rules): qlen is not used -- it is not resident for pinned pushes and
+ * the mate's is unknown anyway -- which loosens each bound by at most one read length.
+ * After bdx_run, or on a rank's context (bdx_dist_chromosome) after bdx_dist_run: that rank's chromosomes -- a site is answered by the
+ * rank that holds tid1.  A chromosome the context holds no reads of, or beyond the header, gives n == 0.  Not beside another call on the
+ * same context (bdx_trim_results included). */
+typedef struct bdx_site_bounds { uint32_t n; int32_t lo1, hi1, lo2, hi2; } bdx_site_bounds;   /* 20 bytes */
+int bdx_site_breakpoint_bounds(bdx_ctx* ctx, const bdx_site* sites, size_t n, int32_t window, bdx_site_bounds* out);
+
 /* Duplicate marking: no counterpart in the reference, which only ignores reads that already carry SAM flag 0x400
  * (io/IlluminaPEReadClassifier.cpp:66-74; K1 restates that).  The rule, written down here once:
  *   RUNS        the store is cut into runs: maximal stretches of consecutive records with equal (tid, pos).  For coordinate-sorted input a

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""What --sites' pair count (bdx_count_site_pairs, KS) costs at a GPU's share of a genome, next to K8 at the same queries, and how far
-its record-only rule stands from the walk's own count.
+"""What --sites' pair count (bdx_count_site_pairs, KS) costs at a GPU's share of a genome, next to K8 and to --ci's breakpoint bounds
+(bdx_site_breakpoint_bounds, KI) at the same queries, and how far its record-only rule stands from the walk's own count.
 
 (a) One context over a synthetic genome share (synth.make_genome: hg38 lengths x fraction, 4 libraries, 30x, as tools/junction_probe.py):
     --sites N sites (default 10,000) made from that run's printed calls -- each call's two ends and type, cycled with its ends moved by up
     to a window when there are fewer calls than sites -- counted with the window the CLI would choose (the largest library uppercutoff),
     timed by HIP events on the context's stream around the whole call (site upload, kernel, count download) and by the host's clock; a
     first call (code object load included) and `--repeat` more.  bdx_count_junction_pairs (K8) is timed the same way on the same sites:
-    one query per site, over both junctions of a same-chromosome site and over the first of a CTX site.
+    one query per site, over both junctions of a same-chromosome site and over the first of a CTX site.  bdx_site_breakpoint_bounds (KI)
+    likewise, on the same sites with the same window, beside each of the two (it has no key choice: it reads the library column whenever the
+    context has more than one library); its n must equal KS's row sums.
 (b) With --recall: the CLI on the chr21 golden fixture, its own table fed back as --sites; per printed call, the site's DV summed over
     the samples against the call's num_Reads.
 Usage: site_probe.py [--fraction 0.125] [--sites 10000] [--repeat 5] [--recall] [--out FILE]  (--out: the whole record as JSON; the summary
@@ -87,7 +89,10 @@ def kernel_probe(fraction, n_sites, repeat):
         for by_library in (False, True):
             c, ev, host = timed(bd, stream, lambda: bd.count_site_pairs(sites, window, by_library=by_library))
             _, ev8, host8 = timed(bd, stream, lambda: bd.count_junction_pairs(j_tid, j_a, j_b, by_library=by_library))
-            calls.append(dict(call=i, by_library=by_library, sites_event_ms=ev, sites_host_ms=host, k8_event_ms=ev8, k8_host_ms=host8))
+            b, evi, hosti = timed(bd, stream, lambda: bd.site_breakpoint_bounds(sites, window))
+            calls.append(dict(call=i, by_library=by_library, sites_event_ms=ev, sites_host_ms=host, k8_event_ms=ev8, k8_host_ms=host8,
+                              bounds_event_ms=evi, bounds_host_ms=hosti))
+            assert (b["n"] == c.sum(axis=1)).all()
             if not by_library:
                 ref = c if ref is None else ref
                 assert (c == ref).all()
@@ -99,7 +104,11 @@ def kernel_probe(fraction, n_sites, repeat):
     out = dict(fraction=fraction, reads=n, printed_rows=rows, sites=int(n_sites), window=window, same_chromosome_sites=int(same.sum()),
                keys_by_file=1, keys_by_library=len(libs), pairs_counted_mean=float(ref.sum(axis=1).mean()), sites_with_pairs=float((ref.sum(axis=1) > 0).mean()),
                calls=calls, median_sites_event_ms=med("sites_event_ms"), median_sites_host_ms=med("sites_host_ms"),
-               median_k8_event_ms=med("k8_event_ms"), median_k8_host_ms=med("k8_host_ms"))
+               median_k8_event_ms=med("k8_event_ms"), median_k8_host_ms=med("k8_host_ms"),
+               median_bounds_event_ms=med("bounds_event_ms"), median_bounds_host_ms=med("bounds_host_ms"))
+    # (KI's call is the same whichever KS call it stands next to: both medians are over the same kind of call)
+    out["bounds_over_sites_event"] = {k: round(out["median_bounds_event_ms"][k] / out["median_sites_event_ms"][k], 3) for k in ("by_file", "by_library")}
+    out["sites_contradictory"] = float(((b["n"] > 0) & ((b["lo1"] > b["hi1"]) | (b["lo2"] > b["hi2"]))).mean())
     bd.close()
     return out
 
