@@ -8,7 +8,7 @@ KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
 HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp
 
-all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-feed-probe oracle
+all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-feed-probe tests/prims/libbdx_prims.so oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -42,6 +42,10 @@ bin/bdx-ci-check: $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp
 
+# test tooling: the shared scan and wave-search headers on their own behind plain C entry points (tests/test_gpu_prims.py)
+tests/prims/libbdx_prims.so: tests/prims/prims.hip $(CSRC)/bdx_scan.h $(CSRC)/bdx_wave_search.h $(CSRC)/bdx_dev.h
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -shared -o $@ $<
+
 # measurement tool (bench.py): the feeder's ceilings -- page cache -> pinned -> HBM
 bin/bdx-feed-probe: tools/feed_probe.hip
 	@mkdir -p bin
@@ -59,7 +63,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-sites-check bin/bdx-ci-check
+	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-sites-check bin/bdx-ci-check tests/prims/libbdx_prims.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

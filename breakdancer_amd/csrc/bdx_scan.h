@@ -3,6 +3,7 @@
 // generic over the element type (uint32_t or a 4-column struct) and over load/store functors so the
 // callers fuse their own per-element work into phase 1 / phase 3.  Element count may live on the device
 // (n_ptr) so no host round trip is needed between dependent stages.
+// Pinned on their own, against numpy's running sums, by tests/test_gpu_prims.py (harness: tests/prims/prims.hip).
 #pragma once
 #include "bdx_dev.h"
 
@@ -147,6 +148,7 @@ inline uint32_t scan_grid(uint32_t n_upper, int iters = kScanIters) {
 
 constexpr uint32_t kScanSelfSumMax = 1024;  // workgroups up to which phase 3 sums the block totals itself
 
+// *total (the grand sum) is written on the phase-2 route only: a launch of kScanSelfSumMax workgroups or fewer leaves it as it was
 template <class T, int kIters = kScanIters, class In, class Out>
 void scan_launch(In in, Out out, const uint32_t* n_ptr, uint32_t n_upper, T* blk_ws, T* total, hipStream_t s) {
     const uint32_t g = scan_grid(n_upper, kIters);

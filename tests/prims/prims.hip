@@ -1,0 +1,240 @@
+// Test-only harness (tests/test_gpu_prims.py) around the two shared primitive headers, included unchanged: csrc/bdx_scan.h
+// (the three-launch scan, the look-back scan and its walk) and csrc/bdx_wave_search.h.  Built into tests/prims/libbdx_prims.so;
+// nothing of it is part of libbdx.so.  Every entry point takes host pointers, does its own allocations and copies, waits for
+// the stream and returns HIP's error code (hipErrorInvalidValue for a call that breaks a precondition of the look-back scan:
+// such a launch would spin, so it is refused here and never made).  Elements are uint32_t words, a U4 four of them in a row.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <new>
+#include <unordered_set>
+
+#include "bdx_scan.h"
+#include "bdx_wave_search.h"
+
+using namespace bdx;
+
+namespace {
+
+#define CK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
+
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+    template <class T> T* as() const { return (T*)p; }
+};
+
+constexpr unsigned char kFill = 0xA5;               // outputs start out as 0xA5A5A5A5 words: what no launch wrote keeps them
+constexpr uint32_t kLbMaxN = (1u << 20) + 1;        // no look-back grid beyond 4,097 workgroups from a test
+enum : int { kFlagN = 0, kFlagE = 1, kFlagLanes = 2, kFlagWords = 4 };
+
+__device__ __forceinline__ bool same(uint32_t a, uint32_t b) { return a == b; }
+__device__ __forceinline__ bool same(const U4& a, const U4& b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
+
+// The functors load and store, and note what the scans promise their callers: the n handed over is *n_ptr ...
+template <class T> struct In {
+    const T* src;
+    const uint32_t* n_ptr;
+    uint32_t* flags;
+    __device__ T operator()(uint32_t j, uint32_t n) const {
+        if (n != *n_ptr) flags[kFlagN] = 1u;
+        return src[j];
+    }
+};
+// ... e is the element's input, and the lanes of one call hold consecutive elements from lane 0 on (K3's HeadOut shuffles on that)
+template <class T> struct Out {
+    T* dst;
+    const T* src;
+    const uint32_t* n_ptr;
+    uint32_t* flags;
+    __device__ void operator()(uint32_t j, uint32_t n, const T& inc, const T& e) const {
+        if (n != *n_ptr) flags[kFlagN] = 1u;
+        if (!same(e, src[j])) flags[kFlagE] = 1u;
+        const uint64_t act = __ballot(1);
+        const uint32_t up = (uint32_t)__shfl_up((int)j, 1);
+        if ((act & (act + 1)) != 0 || ((threadIdx.x & 63) != 0 && up != j - 1)) flags[kFlagLanes] = 1u;
+        dst[j] = inc;
+    }
+};
+
+// in / out: [n_upper] elements; flags: [kFlagWords]
+template <class T> struct ScanBufs {
+    DevBuf in, out, n, flags;
+    uint32_t n_upper = 0;
+    int open(const uint32_t* h_in, uint32_t n_now, uint32_t n_up) {
+        n_upper = n_up;
+        CK(in.alloc((size_t)n_up * sizeof(T)));
+        CK(out.alloc((size_t)n_up * sizeof(T)));
+        CK(n.alloc(4));
+        CK(flags.alloc(kFlagWords * 4));
+        if (n_up) CK(hipMemcpy(in.p, h_in, (size_t)n_up * sizeof(T), hipMemcpyHostToDevice));
+        if (n_up) CK(hipMemset(out.p, kFill, (size_t)n_up * sizeof(T)));
+        CK(hipMemcpy(n.p, &n_now, 4, hipMemcpyHostToDevice));
+        CK(hipMemset(flags.p, 0, kFlagWords * 4));
+        return 0;
+    }
+    In<T> fin() const { return In<T>{in.as<T>(), n.as<uint32_t>(), flags.as<uint32_t>()}; }
+    Out<T> fout() const { return Out<T>{out.as<T>(), in.as<T>(), n.as<uint32_t>(), flags.as<uint32_t>()}; }
+    int close(uint32_t* h_out, uint32_t* h_flags) {
+        CK(hipGetLastError());
+        CK(hipStreamSynchronize(nullptr));
+        if (n_upper) CK(hipMemcpy(h_out, out.p, (size_t)n_upper * sizeof(T), hipMemcpyDeviceToHost));
+        CK(hipMemcpy(h_flags, flags.p, kFlagWords * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+
+template <class T> int scan3(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t n_upper, uint32_t* total, uint32_t* flags) {
+    if (n > n_upper) return (int)hipErrorInvalidValue;
+    ScanBufs<T> b;
+    if (const int rc = b.open(in, n, n_upper)) return rc;
+    DevBuf blk, tot;
+    const size_t blk_bytes = (size_t)scan_grid(n_upper) * sizeof(T);
+    CK(blk.alloc(blk_bytes));
+    CK(hipMemset(blk.p, 0xFF, blk_bytes));   // (the workspace need not start out as anything)
+    CK(tot.alloc(sizeof(T)));
+    CK(hipMemset(tot.p, kFill, sizeof(T)));
+    scan_launch<T>(b.fin(), b.fout(), b.n.template as<uint32_t>(), n_upper, blk.as<T>(), tot.as<T>(), nullptr);
+    if (const int rc = b.close(out, flags)) return rc;
+    CK(hipMemcpy(total, tot.p, sizeof(T), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// look-back words of one scan: sized for n_upper, zero once, and the stamps they have seen since
+struct LbState {
+    unsigned long long* words = nullptr;
+    uint32_t cap_wg = 0;
+    int cols = 0;
+    std::unordered_set<uint32_t> used;
+};
+
+int lb_admit(LbState* st, int cols, uint32_t n, uint32_t n_upper, uint32_t stamp) {
+    if (!st || st->cols != cols || n > n_upper || n_upper > kLbMaxN || scan_grid(n_upper, 1) > st->cap_wg) return (int)hipErrorInvalidValue;
+    if (stamp == 0 || stamp > 0x3FFFFFFFu || !st->used.insert(stamp).second) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+template <class T, int kIters> int scan_lb(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t n_upper, void* state, uint32_t stamp, uint32_t* flags) {
+    LbState* st = (LbState*)state;
+    if (const int rc = lb_admit(st, ScanCols<T>::n, n, n_upper, stamp)) return rc;
+    ScanBufs<T> b;
+    if (const int rc = b.open(in, n, n_upper)) return rc;
+    scan_launch_lb<T, kIters>(b.fin(), b.fout(), b.n.template as<uint32_t>(), n_upper, st->words, stamp, nullptr);
+    return b.close(out, flags);
+}
+
+// k6_place_kernel's head: a workgroup per 256 elements of n, its total handed in, the walk called by every thread
+__global__ __launch_bounds__(kScanBlock) void head_kernel(const U4* tots, const uint32_t* n_ptr, unsigned long long* state, uint32_t stamp, U4* carry_out) {
+    __shared__ uint32_t s_prefix[4];
+    const uint32_t n = *n_ptr;
+    const uint32_t bid = blockIdx.x, base = bid * kScanBlock;
+    if (base >= n) return;
+    const U4 tot = tots[bid];
+    const U4 carry = lookback_exclusive<U4>(tot, state, stamp, bid, s_prefix);
+    carry_out[(size_t)base + threadIdx.x] = carry;
+}
+
+// four waves a workgroup, a query each
+__global__ __launch_bounds__(256) void search_kernel(const int32_t* tid, const int32_t* pos, uint64_t n, const int32_t* qt, const int64_t* qp, uint32_t nq, uint64_t* out) {
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;
+    out[(size_t)q * 64 + (threadIdx.x & 63)] = wave_lower_bound(tid, pos, n, qt[q], qp[q]);
+}
+
+}  // namespace
+
+extern "C" {
+
+// the three-launch scan as K9 calls it; total: [columns] words, written on the phase-2 route only
+int prims_scan3_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t n_upper, uint32_t* total, uint32_t* flags) {
+    return scan3<uint32_t>(in, out, n, n_upper, total, flags);
+}
+int prims_scan3_u4(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t n_upper, uint32_t* total, uint32_t* flags) {
+    return scan3<U4>(in, out, n, n_upper, total, flags);
+}
+
+int prims_lb_state_new(uint32_t n_upper, int cols, void** out) {
+    if ((cols != 1 && cols != 4) || n_upper > kLbMaxN) return (int)hipErrorInvalidValue;
+    LbState* st = new (std::nothrow) LbState;
+    if (!st) return (int)hipErrorOutOfMemory;
+    st->cap_wg = scan_grid(n_upper, 1);
+    st->cols = cols;
+    const size_t bytes = (size_t)st->cap_wg * cols * 8;
+    hipError_t e = hipMalloc((void**)&st->words, bytes);
+    if (e == hipSuccess) e = hipMemset(st->words, 0, bytes);
+    if (e != hipSuccess) { if (st->words) (void)hipFree(st->words); delete st; return (int)e; }
+    *out = st;
+    return 0;
+}
+// what next_lb_stamp does when its counter comes round: every word back to zero, and every stamp free again
+int prims_lb_state_clear(void* state) {
+    LbState* st = (LbState*)state;
+    if (!st) return (int)hipErrorInvalidValue;
+    CK(hipMemset(st->words, 0, (size_t)st->cap_wg * st->cols * 8));
+    st->used.clear();
+    return 0;
+}
+void prims_lb_state_free(void* state) {
+    LbState* st = (LbState*)state;
+    if (!st) return;
+    (void)hipFree(st->words);
+    delete st;
+}
+
+// the three instantiations of K3
+int prims_scan_lb_u32_1(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t n_upper, void* state, uint32_t stamp, uint32_t* flags) {
+    return scan_lb<uint32_t, 1>(in, out, n, n_upper, state, stamp, flags);
+}
+int prims_scan_lb_u4_1(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t n_upper, void* state, uint32_t stamp, uint32_t* flags) {
+    return scan_lb<U4, 1>(in, out, n, n_upper, state, stamp, flags);
+}
+int prims_scan_lb_u4_2(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t n_upper, void* state, uint32_t stamp, uint32_t* flags) {
+    return scan_lb<U4, 2>(in, out, n, n_upper, state, stamp, flags);
+}
+
+// tots: [scan_grid(n_upper, 1)] U4; carry_out: [scan_grid(n_upper, 1) * 256] U4, the carry every thread got
+int prims_lb_head(const uint32_t* tots, uint32_t* carry_out, uint32_t n, uint32_t n_upper, void* state, uint32_t stamp) {
+    LbState* st = (LbState*)state;
+    if (const int rc = lb_admit(st, 4, n, n_upper, stamp)) return rc;
+    const uint32_t g = scan_grid(n_upper, 1);
+    DevBuf t, c, nn;
+    CK(t.alloc((size_t)g * sizeof(U4)));
+    CK(c.alloc((size_t)g * kScanBlock * sizeof(U4)));
+    CK(nn.alloc(4));
+    CK(hipMemcpy(t.p, tots, (size_t)g * sizeof(U4), hipMemcpyHostToDevice));
+    CK(hipMemset(c.p, kFill, (size_t)g * kScanBlock * sizeof(U4)));
+    CK(hipMemcpy(nn.p, &n, 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(head_kernel, dim3(g), dim3(kScanBlock), 0, nullptr, t.as<U4>(), nn.as<uint32_t>(), st->words, stamp, c.as<U4>());
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(nullptr));
+    CK(hipMemcpy(carry_out, c.p, (size_t)g * kScanBlock * sizeof(U4), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// tid / pos: [n_upper] records sorted by (tid, pos), of which the first n are searched; out: [nq][64], the answer every lane got
+int prims_search(const int32_t* tid, const int32_t* pos, uint64_t n, uint64_t n_upper, const int32_t* qt, const int64_t* qp, uint32_t nq, uint64_t* out) {
+    if (n > n_upper) return (int)hipErrorInvalidValue;
+    if (!nq) return 0;
+    DevBuf dt, dp, dqt, dqp, dout;
+    CK(dt.alloc(n_upper * 4));
+    CK(dp.alloc(n_upper * 4));
+    CK(dqt.alloc((size_t)nq * 4));
+    CK(dqp.alloc((size_t)nq * 8));
+    CK(dout.alloc((size_t)nq * 64 * 8));
+    if (n_upper) {
+        CK(hipMemcpy(dt.p, tid, n_upper * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dp.p, pos, n_upper * 4, hipMemcpyHostToDevice));
+    }
+    CK(hipMemcpy(dqt.p, qt, (size_t)nq * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dqp.p, qp, (size_t)nq * 8, hipMemcpyHostToDevice));
+    CK(hipMemset(dout.p, kFill, (size_t)nq * 64 * 8));
+    hipLaunchKernelGGL(search_kernel, dim3((nq + 3) / 4), dim3(256), 0, nullptr, dt.as<int32_t>(), dp.as<int32_t>(), n, dqt.as<int32_t>(), dqp.as<int64_t>(), nq,
+                       dout.as<uint64_t>());
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(nullptr));
+    CK(hipMemcpy(out, dout.p, (size_t)nq * 64 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"
