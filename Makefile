@@ -4,7 +4,7 @@ ARCH ?= gfx950
 CSRC := breakdancer_amd/csrc
 HOST := breakdancer_amd/host
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Iinclude
-KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/k8_junction.hip $(CSRC)/ks_sites.hip $(CSRC)/ki_bounds.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/bdx_api.hip
+KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/kq_queries.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/bdx_api.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
 HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp
 
@@ -42,8 +42,8 @@ bin/bdx-ci-check: $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp
 
-# test tooling: the shared scan and wave-search headers on their own behind plain C entry points (tests/test_gpu_prims.py)
-tests/prims/libbdx_prims.so: tests/prims/prims.hip $(CSRC)/bdx_scan.h $(CSRC)/bdx_wave_search.h $(CSRC)/bdx_dev.h
+# test tooling: the shared scan, wave-search and window-walk headers on their own behind plain C entry points (tests/test_gpu_prims.py)
+tests/prims/libbdx_prims.so: tests/prims/prims.hip $(CSRC)/bdx_scan.h $(CSRC)/bdx_wave_search.h $(CSRC)/bdx_window.h $(CSRC)/bdx_dev.h include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -shared -o $@ $<
 
 # measurement tool (bench.py): the feeder's ceilings -- page cache -> pinned -> HBM

@@ -193,13 +193,10 @@ struct bdx_ctx {
     std::vector<KeySeg> key_segs;
     DevBuf b_seg;
 
-    // ---- bdx_count_junction_pairs ----
+    // ---- bdx_count_junction_pairs, bdx_count_site_pairs, bdx_site_breakpoint_bounds (run_query) ----
     size_t cls_n = (size_t)-1;        // reads the class bytes in b_cls describe (set by a completed pass 1; -1: none)
-    DevBuf b_jq, b_jc;                // its queries and counts
-    // ---- bdx_count_site_pairs ----
-    DevBuf b_sq, b_sc;                // its sites and counts
-    // ---- bdx_site_breakpoint_bounds ----
-    DevBuf b_iq, b_io, b_iu;          // its sites, bounds and the libraries' U table
+    DevBuf b_qin, b_qout;             // a call's uploads (queries or sites, and behind them KI's table of the libraries' U) and its results.
+                                      // One pair serves the three: every call ends with hipStreamSynchronize, so none can see another's data
     // ---- bdx_set_mark_duplicates ----
     bool mark_dup = false;            // KD marks duplicates in the flag column at the head of pass 1; pass 1 then does not start behind arriving batches
     bool dup_done = false;            // KD has run over this load (nothing can be appended to it any more)
@@ -2165,20 +2162,59 @@ int bdx_classify(const bdx_opts* opts, const bdx_lib* libs, int nlibs, const bdx
     return bdx_get_read_class(c, cls_out, b->n);
 }
 
-int bdx_count_junction_pairs(bdx_ctx* c, const int32_t* tid, const int32_t* pos_a, const int32_t* pos_b, size_t n, int by_library,
-                             uint32_t* counts) {
+// ---- queries over the resident store: K8, KS, KI (kq_queries.hip) ----
+
+// What the three calls check first, in this order: a context, no sizing pass in flight, a run that classified the store.  *none: n == 0, nothing to do.
+static int check_query_state(bdx_ctx* c, size_t n, bool* none) {
+    *none = false;
     if (!c) return BDX_EINVAL;
     NOT_WHILE_SIZING(c);
     if (c->cls_n != c->n && !(c->ran && c->n == 0)) return fail(c, BDX_ESTATE, "no run has classified the reads this context holds");
-    if (n == 0) return BDX_OK;
+    *none = n == 0;
+    return BDX_OK;
+}
+
+static StoreView store_view(const bdx_ctx* c) {
+    return StoreView{c->d.tid, c->d.pos, c->d.mtid, c->d.mpos, c->d.isize, c->d.flag, c->b_cls.as<uint8_t>(), c->n};
+}
+
+// the key column of the counting calls (a context with one library / one file never copies the respective column: every read is key 0 there)
+static const uint8_t* key_column(const bdx_ctx* c, int by_library, int nkeys) { return nkeys > 1 ? (by_library ? c->d.lib : c->d.bam) : nullptr; }
+
+// The call sequence the three share: the host arrays of `up` go to the device one behind the other, `launch` gets where they start, where
+// the results go and the stream, and the call returns when the results are in `out`.
+struct QueryUpload { const void* src; size_t bytes; };
+static int run_query(bdx_ctx* c, std::initializer_list<QueryUpload> up, void* out, size_t out_bytes,
+                     const std::function<void(const char* in, void* results, hipStream_t s)>& launch) {
+    HIPCHK(c, hipSetDevice(c->device));
+    size_t in_bytes = 0;
+    for (const QueryUpload& u : up) in_bytes += u.bytes;
+    HIPCHK(c, c->b_qin.ensure(in_bytes));
+    HIPCHK(c, c->b_qout.ensure(out_bytes));
+    hipStream_t s = c->stream;
+    char* in = c->b_qin.as<char>();
+    for (const QueryUpload& u : up) {
+        if (u.bytes) HIPCHK(c, hipMemcpyAsync(in, u.src, u.bytes, hipMemcpyHostToDevice, s));
+        in += u.bytes;
+    }
+    launch(c->b_qin.as<char>(), c->b_qout.p, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, c->b_qout.p, out_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return BDX_OK;
+}
+
+int bdx_count_junction_pairs(bdx_ctx* c, const int32_t* tid, const int32_t* pos_a, const int32_t* pos_b, size_t n, int by_library,
+                             uint32_t* counts) {
+    bool none;
+    BDX_TRY(check_query_state(c, n, &none));
+    if (none) return BDX_OK;
     if (!tid || !pos_a || !pos_b || !counts) return fail(c, BDX_EINVAL, "null array");
     for (size_t i = 0; i < n; ++i)
         if (tid[i] < 0 || pos_a[i] < 1 || pos_a[i] > pos_b[i])
             return fail(c, BDX_EINVAL, "query " + std::to_string(i) + ": tid < 0, pos_a < 1 or pos_a > pos_b");
     if (n > ((size_t)1 << 31)) return fail(c, BDX_ELIMIT, "more than 2^31 queries in one call");
     const int nkeys = by_library ? c->nlibs : c->nbams;
-    // (a context with one library / one file never copies the respective column: every read is key 0 there)
-    const uint8_t* key = nkeys > 1 ? (by_library ? c->d.lib : c->d.bam) : nullptr;
     // K1 calls a pair normal only if (float)|isize| is not above its library's upper cutoff (-l's remaps included: NORMAL_RF needs it
     // below the cutoff) and |isize| <= -m.  Every such integer lies below the float that follows the cutoff (a NaN cutoff bounds nothing).
     double ub = -1.0;
@@ -2187,32 +2223,16 @@ int bdx_count_junction_pairs(bdx_ctx* c, const int32_t* tid, const int32_t* pos_
         ub = std::max(ub, std::isnan(u) || u == INFINITY ? 2147483647.0 : std::ceil((double)std::nextafter(u, INFINITY)) - 1.0);
     }
     const int32_t lmax = (int32_t)std::max(-1.0, std::min<double>({ub, (double)c->opts.max_sd, 2147483647.0}));
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t cbytes = n * (size_t)nkeys * 4;
-    HIPCHK(c, c->b_jq.ensure(n * 12));
-    HIPCHK(c, c->b_jc.ensure(cbytes));
-    hipStream_t s = c->stream;
-    int32_t* q = c->b_jq.as<int32_t>();
-    HIPCHK(c, hipMemcpyAsync(q, tid, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(q + n, pos_a, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(q + 2 * n, pos_b, n * 4, hipMemcpyHostToDevice, s));
-    K8Params p{};
-    p.tid = c->d.tid; p.pos = c->d.pos; p.isize = c->d.isize; p.key = key; p.cls = c->b_cls.as<uint8_t>(); p.n = c->n;
-    p.q_tid = q; p.q_a = q + n; p.q_b = q + 2 * n; p.nq = (uint32_t)n; p.nkeys = nkeys; p.lmax = lmax; p.counts = c->b_jc.as<uint32_t>();
-    launch_k8(p, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(counts, p.counts, cbytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return BDX_OK;
+    return run_query(c, {{tid, n * 4}, {pos_a, n * 4}, {pos_b, n * 4}}, counts, n * (size_t)nkeys * 4, [&](const char* in, void* results, hipStream_t s) {
+        const int32_t* q = (const int32_t*)in;
+        launch_k8(K8Params{store_view(c), key_column(c, by_library, nkeys), q, q + n, q + 2 * n, (uint32_t)n, nkeys, lmax, (uint32_t*)results}, s);
+    });
 }
 
 // What bdx_count_site_pairs and bdx_site_breakpoint_bounds check before they touch the device, in this order.  *none: n == 0, nothing to do.
 static int check_site_call(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, const void* out, bool* none) {
-    *none = false;
-    if (!c) return BDX_EINVAL;
-    NOT_WHILE_SIZING(c);
-    if (c->cls_n != c->n && !(c->ran && c->n == 0)) return fail(c, BDX_ESTATE, "no run has classified the reads this context holds");
-    if (n == 0) { *none = true; return BDX_OK; }
+    BDX_TRY(check_query_state(c, n, none));
+    if (*none) return BDX_OK;
     if (!sites || !out) return fail(c, BDX_EINVAL, "null array");
     if (window < 0 || window > (1 << 30)) return fail(c, BDX_EINVAL, "window < 0 or window > 2^30");
     if (n > ((size_t)1 << 31)) return fail(c, BDX_ELIMIT, "more than 2^31 sites in one call");
@@ -2233,23 +2253,9 @@ int bdx_count_site_pairs(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t wi
     BDX_TRY(check_site_call(c, sites, n, window, counts, &none));
     if (none) return BDX_OK;
     const int nkeys = by_library ? c->nlibs : c->nbams;
-    // (a context with one library / one file never copies the respective column: every read is key 0 there)
-    const uint8_t* key = nkeys > 1 ? (by_library ? c->d.lib : c->d.bam) : nullptr;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t cbytes = n * (size_t)nkeys * 4;
-    HIPCHK(c, c->b_sq.ensure(n * sizeof(bdx_site)));
-    HIPCHK(c, c->b_sc.ensure(cbytes));
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->b_sq.p, sites, n * sizeof(bdx_site), hipMemcpyHostToDevice, s));
-    KsParams p{};
-    p.tid = c->d.tid; p.pos = c->d.pos; p.mtid = c->d.mtid; p.mpos = c->d.mpos; p.flag = c->d.flag; p.key = key;
-    p.cls = c->b_cls.as<uint8_t>(); p.n = c->n;
-    p.sites = c->b_sq.as<KsSite>(); p.nq = (uint32_t)n; p.nkeys = nkeys; p.window = window; p.counts = c->b_sc.as<uint32_t>();
-    launch_ks(p, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(counts, p.counts, cbytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return BDX_OK;
+    return run_query(c, {{sites, n * sizeof(bdx_site)}}, counts, n * (size_t)nkeys * 4, [&](const char* in, void* results, hipStream_t s) {
+        launch_ks(KsParams{store_view(c), key_column(c, by_library, nkeys), (const KsSite*)in, (uint32_t)n, nkeys, window, (uint32_t*)results}, s);
+    });
 }
 
 int bdx_site_breakpoint_bounds(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, bdx_site_bounds* out) {
@@ -2263,27 +2269,12 @@ int bdx_site_breakpoint_bounds(bdx_ctx* c, const bdx_site* sites, size_t n, int3
         u[i] = !std::isfinite(v) || v > 1073741824.0 ? (1u << 30) : (v < 0 ? 0u : (uint32_t)std::ceil(v));
     }
     const int nlibs = c->nlibs;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t obytes = n * sizeof(bdx_site_bounds);
-    HIPCHK(c, c->b_iq.ensure(n * sizeof(bdx_site)));
-    HIPCHK(c, c->b_io.ensure(obytes));
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->b_iq.p, sites, n * sizeof(bdx_site), hipMemcpyHostToDevice, s));
-    KiParams p{};
-    if (nlibs > 1) {   // (a context with one library never copies the lib column, and its U travels with the launch)
-        HIPCHK(c, c->b_iu.ensure(u.size() * 4));
-        HIPCHK(c, hipMemcpyAsync(c->b_iu.p, u.data(), u.size() * 4, hipMemcpyHostToDevice, s));
-        p.lib = c->d.lib; p.utab = c->b_iu.as<uint32_t>();
-    }
-    p.tid = c->d.tid; p.pos = c->d.pos; p.mtid = c->d.mtid; p.mpos = c->d.mpos; p.flag = c->d.flag;
-    p.cls = c->b_cls.as<uint8_t>(); p.n = c->n;
-    p.sites = c->b_iq.as<KsSite>(); p.nq = (uint32_t)n; p.nlibs = nlibs; p.window = window;
-    p.long_insert = c->opts.illumina_long_insert ? 1 : 0; p.u0 = u.empty() ? 0u : u[0]; p.out = c->b_io.as<KiBounds>();
-    launch_ki(p, s);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, p.out, obytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return BDX_OK;
+    const bool many = nlibs > 1;   // (a context with one library never copies the lib column, and its U travels with the launch: no table)
+    const size_t sbytes = n * sizeof(bdx_site);
+    return run_query(c, {{sites, sbytes}, {u.data(), many ? u.size() * 4 : 0}}, out, n * sizeof(bdx_site_bounds), [&](const char* in, void* results, hipStream_t s) {
+        launch_ki(KiParams{store_view(c), many ? c->d.lib : nullptr, (const KsSite*)in, (uint32_t)n, nlibs, window, c->opts.illumina_long_insert ? 1 : 0,
+                           u.empty() ? 0u : u[0], many ? (const uint32_t*)(in + sbytes) : nullptr, (KiBounds*)results}, s);
+    });
 }
 
 int bdx_set_process_option(const char* name, int value) {
@@ -2294,8 +2285,8 @@ int bdx_set_process_option(const char* name, int value) {
 
 int bdx_warm_up(int device) {
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
-    warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k8(nullptr);
-    warm_k9(nullptr); warm_kx(nullptr); warm_ks(nullptr); warm_ki(nullptr);
+    warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k9(nullptr);
+    warm_kx(nullptr); warm_kq(nullptr);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? BDX_OK : BDX_EHIP;
 }
 

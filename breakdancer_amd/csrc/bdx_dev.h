@@ -191,12 +191,18 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
-// K8 (k8_junction.hip): normal pairs covering SV junctions, per query and key (bdx_count_junction_pairs)
-struct K8Params {
-    const int32_t *tid, *pos, *isize;   // the resident store, sorted by (tid, pos)
-    const uint8_t* key;                 // library or source-file column; read only when nkeys > 1
+// The resident store as the kernels that answer queries over it see it (K8, KS, KI: kq_queries.hip; their shared pieces: bdx_window.h)
+struct StoreView {
+    const int32_t *tid, *pos, *mtid, *mpos, *isize;   // sorted by (tid, pos)
+    const uint16_t* flag;               // SAM flags
     const uint8_t* cls;                 // K1's class bytes
     uint64_t n;
+};
+
+// K8: normal pairs covering SV junctions, per query and key (bdx_count_junction_pairs)
+struct K8Params {
+    StoreView st;
+    const uint8_t* key;                 // library or source-file column; read only when nkeys > 1
     const int32_t *q_tid, *q_a, *q_b;   // queries: chromosome, junctions a <= b (1-based)
     uint32_t nq;
     int nkeys;                          // 1..255
@@ -204,17 +210,14 @@ struct K8Params {
     uint32_t* counts;                   // [nq][nkeys]
 };
 
-// KS (ks_sites.hip): alternate-supporting pairs at given SV sites, per site and key (bdx_count_site_pairs)
+// KS: alternate-supporting pairs at given SV sites, per site and key (bdx_count_site_pairs)
 struct KsSite {                         // = bdx_site (include/bdx.h)
     int32_t tid1, pos1, tid2, pos2;     // 1-based positions, (tid1, pos1) <= (tid2, pos2)
     uint32_t flag_mask;                 // bit f: ReadFlag f supports the site
 };
 struct KsParams {
-    const int32_t *tid, *pos, *mtid, *mpos;   // the resident store, sorted by (tid, pos)
-    const uint16_t* flag;               // SAM flags
+    StoreView st;
     const uint8_t* key;                 // library or source-file column; read only when nkeys > 1
-    const uint8_t* cls;                 // K1's class bytes
-    uint64_t n;
     const KsSite* sites;
     uint32_t nq;
     int nkeys;                          // 1..255
@@ -222,17 +225,14 @@ struct KsParams {
     uint32_t* counts;                   // [nq][nkeys]
 };
 
-// KI (ki_bounds.hip): breakpoint intervals of given SV sites from the records KS counts, keys pooled (bdx_site_breakpoint_bounds)
+// KI: breakpoint intervals of given SV sites from the records KS counts, keys pooled (bdx_site_breakpoint_bounds)
 struct KiBounds {                       // = bdx_site_bounds (include/bdx.h)
     uint32_t n;                         // the records that count for the site
     int32_t lo1, hi1, lo2, hi2;         // per end: the largest lower and the smallest upper bound, 1-based; all 0 with n == 0
 };
 struct KiParams {
-    const int32_t *tid, *pos, *mtid, *mpos;   // the resident store, sorted by (tid, pos)
-    const uint16_t* flag;               // SAM flags
+    StoreView st;
     const uint8_t* lib;                 // library column; read only when nlibs > 1
-    const uint8_t* cls;                 // K1's class bytes
-    uint64_t n;
     const KsSite* sites;
     uint32_t nq;
     int nlibs;                          // 1..255

@@ -1,4 +1,5 @@
-// The 64-ary ballot search of the kernels that answer queries over the resident store (K8, k8_junction.hip; KS, ks_sites.hip; KI, ki_bounds.hip).
+// The 64-ary ballot search of the kernels that answer queries over the resident store (K8, KS, KI: kq_queries.hip), which reach it through
+// the window walk of bdx_window.h.
 // Pinned on its own, against bisect_left, by tests/test_gpu_prims.py (harness: tests/prims/prims.hip).
 #pragma once
 #include "bdx_dev.h"

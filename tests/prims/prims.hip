@@ -1,5 +1,6 @@
-// Test-only harness (tests/test_gpu_prims.py) around the two shared primitive headers, included unchanged: csrc/bdx_scan.h
-// (the three-launch scan, the look-back scan and its walk) and csrc/bdx_wave_search.h.  Built into tests/prims/libbdx_prims.so;
+// Test-only harness (tests/test_gpu_prims.py) around the shared primitive headers, included unchanged: csrc/bdx_scan.h
+// (the three-launch scan, the look-back scan and its walk), csrc/bdx_wave_search.h and csrc/bdx_window.h (the window walk of the
+// query kernels and their per-wave key counters).  Built into tests/prims/libbdx_prims.so;
 // nothing of it is part of libbdx.so.  Every entry point takes host pointers, does its own allocations and copies, waits for
 // the stream and returns HIP's error code (hipErrorInvalidValue for a call that breaks a precondition of the look-back scan:
 // such a launch would spin, so it is refused here and never made).  Elements are uint32_t words, a U4 four of them in a row.
@@ -11,6 +12,7 @@
 
 #include "bdx_scan.h"
 #include "bdx_wave_search.h"
+#include "bdx_window.h"
 
 using namespace bdx;
 
@@ -142,6 +144,62 @@ __global__ __launch_bounds__(256) void search_kernel(const int32_t* tid, const i
     out[(size_t)q * 64 + (threadIdx.x & 63)] = wave_lower_bound(tid, pos, n, qt[q], qp[q]);
 }
 
+// the window walk: four waves a workgroup, a query (t, wlo, whi) each.  The body counts its calls and notes what the walk promises it:
+// all 64 lanes in every call, lane l at the index lane 0 holds + l, s the record's pos; it adds 1 to the query's word of every record
+// it is handed with `in` (a vector atomicAdd).  steps / flags: [nq][64], what every lane saw
+enum : uint32_t { kWalkLanes = 1, kWalkOrder = 2, kWalkPos = 4 };
+__global__ __launch_bounds__(256) void walk_kernel(const int32_t* tid, const int32_t* pos, uint64_t n, uint64_t n_upper, const int32_t* qt, const int64_t* qlo,
+                                                   const int64_t* qhi, uint32_t nq, uint32_t* visits, uint32_t* steps, uint32_t* flags) {
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= nq) return;
+    const int lane = threadIdx.x & 63;
+    uint32_t nsteps = 0, bad = 0;
+    wave_window_walk(tid, pos, n, qt[q], qlo[q], qhi[q], [&](uint64_t i, int64_t s, bool in) {
+        if (__ballot(1) != ~0ull) bad |= kWalkLanes;
+        if (i != (uint64_t)__shfl((long long)i, 0) + (uint64_t)lane) bad |= kWalkOrder;
+        if (in) {
+            if (i >= n || s != (int64_t)pos[i]) bad |= kWalkPos;
+            else atomicAdd(&visits[(size_t)q * n_upper + i], 1u);
+        }
+        ++nsteps;
+    });
+    steps[(size_t)q * 64 + lane] = nsteps;
+    flags[(size_t)q * 64 + lane] = bad;
+}
+
+// the per-wave key counters under the walk, as K8 and KS use them: a record is a hit where its byte of `hit` is not zero, its key is its
+// byte of `key`.  Every wave of a block opens and closes the counters, the waves without a query too
+__global__ __launch_bounds__(256) void count_kernel(const int32_t* tid, const int32_t* pos, uint64_t n, const uint8_t* hit, const uint8_t* key, const int32_t* qt,
+                                                    const int64_t* qlo, const int64_t* qhi, uint32_t nq, int nkeys, uint32_t* counts) {
+    extern __shared__ uint32_t s_cnt[];   // [4][nkeys] (nkeys > 1 only)
+    const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const bool live = q < nq;
+    WaveKeyCounts kc;
+    kc.open(s_cnt, nkeys);
+    if (live) wave_window_walk(tid, pos, n, qt[q], qlo[q], qhi[q], [&](uint64_t i, int64_t, bool in) { kc.add(in && hit[i] != 0, key, i); });
+    kc.close(live, counts, q);
+}
+
+// the store and the queries of the two walk entries on the device
+struct WalkBufs {
+    DevBuf tid, pos, qt, qlo, qhi;
+    int open(const int32_t* h_tid, const int32_t* h_pos, uint64_t n_upper, const int32_t* h_qt, const int64_t* h_qlo, const int64_t* h_qhi, uint32_t nq) {
+        CK(tid.alloc(n_upper * 4));
+        CK(pos.alloc(n_upper * 4));
+        CK(qt.alloc((size_t)nq * 4));
+        CK(qlo.alloc((size_t)nq * 8));
+        CK(qhi.alloc((size_t)nq * 8));
+        if (n_upper) {
+            CK(hipMemcpy(tid.p, h_tid, n_upper * 4, hipMemcpyHostToDevice));
+            CK(hipMemcpy(pos.p, h_pos, n_upper * 4, hipMemcpyHostToDevice));
+        }
+        CK(hipMemcpy(qt.p, h_qt, (size_t)nq * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(qlo.p, h_qlo, (size_t)nq * 8, hipMemcpyHostToDevice));
+        CK(hipMemcpy(qhi.p, h_qhi, (size_t)nq * 8, hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -234,6 +292,58 @@ int prims_search(const int32_t* tid, const int32_t* pos, uint64_t n, uint64_t n_
     CK(hipGetLastError());
     CK(hipStreamSynchronize(nullptr));
     CK(hipMemcpy(out, dout.p, (size_t)nq * 64 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// tid / pos: [n_upper] records sorted by (tid, pos), of which the first n are the store; visits: [nq][n_upper] (zero before the launch),
+// steps, flags: [nq][64] (filled before the launch)
+int prims_walk(const int32_t* tid, const int32_t* pos, uint64_t n, uint64_t n_upper, const int32_t* qt, const int64_t* qlo, const int64_t* qhi, uint32_t nq,
+               uint32_t* visits, uint32_t* steps, uint32_t* flags) {
+    if (n > n_upper) return (int)hipErrorInvalidValue;
+    if (!nq) return 0;
+    WalkBufs b;
+    if (const int rc = b.open(tid, pos, n_upper, qt, qlo, qhi, nq)) return rc;
+    DevBuf dv, ds, df;
+    const size_t vbytes = (size_t)nq * n_upper * 4, lbytes = (size_t)nq * 64 * 4;
+    CK(dv.alloc(vbytes));
+    CK(ds.alloc(lbytes));
+    CK(df.alloc(lbytes));
+    if (vbytes) CK(hipMemset(dv.p, 0, vbytes));
+    CK(hipMemset(ds.p, kFill, lbytes));
+    CK(hipMemset(df.p, kFill, lbytes));
+    hipLaunchKernelGGL(walk_kernel, dim3((nq + 3) / 4), dim3(256), 0, nullptr, b.tid.as<int32_t>(), b.pos.as<int32_t>(), n, n_upper, b.qt.as<int32_t>(),
+                       b.qlo.as<int64_t>(), b.qhi.as<int64_t>(), nq, dv.as<uint32_t>(), ds.as<uint32_t>(), df.as<uint32_t>());
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(nullptr));
+    if (vbytes) CK(hipMemcpy(visits, dv.p, vbytes, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(steps, ds.p, lbytes, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(flags, df.p, lbytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// hit / key: [n] bytes; counts: [rows][nkeys] with rows = nq rounded up to whole blocks of four, filled before the launch: the rows of
+// the waves without a query come back as they went
+int prims_key_counts(const int32_t* tid, const int32_t* pos, uint64_t n, const uint8_t* hit, const uint8_t* key, const int32_t* qt, const int64_t* qlo,
+                     const int64_t* qhi, uint32_t nq, int nkeys, uint32_t* counts) {
+    if (nkeys < 1 || nkeys > 255) return (int)hipErrorInvalidValue;
+    if (!nq) return 0;
+    WalkBufs b;
+    if (const int rc = b.open(tid, pos, n, qt, qlo, qhi, nq)) return rc;
+    DevBuf dh, dk, dc;
+    const size_t cbytes = (size_t)((nq + 3) / 4 * 4) * nkeys * 4;
+    CK(dh.alloc(n));
+    CK(dk.alloc(n));
+    CK(dc.alloc(cbytes));
+    if (n) {
+        CK(hipMemcpy(dh.p, hit, n, hipMemcpyHostToDevice));
+        CK(hipMemcpy(dk.p, key, n, hipMemcpyHostToDevice));
+    }
+    CK(hipMemset(dc.p, kFill, cbytes));
+    hipLaunchKernelGGL(count_kernel, dim3((nq + 3) / 4), dim3(256), nkeys > 1 ? (size_t)4 * nkeys * 4 : 0, nullptr, b.tid.as<int32_t>(), b.pos.as<int32_t>(), n,
+                       dh.as<uint8_t>(), dk.as<uint8_t>(), b.qt.as<int32_t>(), b.qlo.as<int64_t>(), b.qhi.as<int64_t>(), nq, nkeys, dc.as<uint32_t>());
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(nullptr));
+    CK(hipMemcpy(counts, dc.p, cbytes, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,10 +1,11 @@
-"""Sizes, values and CPU references of tests/test_gpu_prims.py, which holds csrc/bdx_scan.h and csrc/bdx_wave_search.h to them
-through tests/prims/prims.hip.  Nothing here needs a GPU: tests/test_prims_cases.py checks the references against plain loops
-and the tables against the edges they are there for.
+"""Sizes, values and CPU references of tests/test_gpu_prims.py, which holds csrc/bdx_scan.h, csrc/bdx_wave_search.h and
+csrc/bdx_window.h to them through tests/prims/prims.hip.  Nothing here needs a GPU: tests/test_prims_cases.py checks the
+references against plain loops and the tables against the edges they are there for.
 
 Scans: elements are uint32 words, one or four columns; the reference is numpy's cumulative sum in uint32 per column, so a sum
 that wraps 2^32 is part of what is expected.  Search: a store sorted by (tid, pos); the reference is bisect_left over the
-(tid, pos) tuples."""
+(tid, pos) tuples.  Window walk: queries (t, wlo, whi) over such a store; the reference is numpy's searchsorted on the combined
+key: the records [L, R) and (R - L) // 64 + 1 steps.  Key counters: numpy's bincount over [L, R)."""
 import bisect
 
 import numpy as np
@@ -210,3 +211,120 @@ def queries(tid, pos, n=None, seed=0, extra=()):
 def run_ends(n):
     """records at and next to both ends of every run of runs_layout(n)"""
     return [i for length, start in runs_layout(n) for i in (start - 1, start, start + 1, start + length - 2, start + length - 1, start + length)]
+
+
+# ---- window walk and key counters ------------------------------------------------------------------------------------------
+
+WALK_STORES = [0, 1, 63, 64, 65, 128, 129, 64 * 65]
+WALK_COUNTS = [0, 1, 63, 64, 65, 128]        # records in a window: none, one, and either side of one and two whole steps
+WHI_WIDE = 2**31 - 2 + 2**30                 # the largest whi a kernel makes (pos 2^31 - 1, window 2^30): not a 32-bit number
+WALK_RUN_STORE = 64 * 65                     # holds the runs of 1, 64 and 65 equal positions of runs_layout
+WALK_TID_STORES = [5 * 64, 5 * 65, 5 * 128]  # `tids` stores whose chromosomes hold 64, 65 and 128 records
+COUNT_NKEYS = [1, 2, 64, 65, 255]
+COUNT_STORE = 700
+
+
+def walk_reference(tid, pos, qt, qlo, qhi, n=None):
+    """(L, R, steps) per query (t, wlo, whi) over the first n records: L the first record not below (t, wlo), R the first index
+    >= L whose record is off t or behind whi (n if none is), and the (R - L) // 64 + 1 steps the walk takes"""
+    n = len(tid) if n is None else n
+    key = tid[:n].astype(np.int64) * (1 << 32) + pos[:n]
+    t = np.asarray(qt, np.int64) * (1 << 32)
+    # (a bound outside the int32 range stands for the nearest value outside it: no pos lies in between)
+    lo = t + np.clip(np.asarray(qlo, np.int64), -(1 << 31), 1 << 31)
+    hi = t + np.clip(np.asarray(qhi, np.int64), -(1 << 31) - 1, (1 << 31) - 1)
+    L = np.searchsorted(key, lo, "left").astype(np.int64)
+    R = np.maximum(L, np.searchsorted(key, hi, "right").astype(np.int64))
+    return L, R, (R - L) // 64 + 1
+
+
+def _windows_at(pos, n, t):
+    """windows of every count of WALK_COUNTS at the first record, ending at the last, and in the middle of a store of distinct positions
+    three apart"""
+    q = []
+    for k in WALK_COUNTS:
+        if k > n:
+            continue
+        for a in sorted({0, n - k, (n - k) // 2}):
+            if k:
+                q.append((t, int(pos[a]), int(pos[a + k - 1])))
+            elif a < n:
+                q.append((t, int(pos[a]) + 1, int(pos[a]) + 2))       # between two records (behind the last one for a == n - 1)
+        if k == 0 and n:
+            q.append((t, int(pos[0]) - 2, int(pos[0]) - 1))           # in front of the first record
+    return q
+
+
+def walk_cases():
+    """[(label, family, n_upper, n, [(t, wlo, whi)])]: the stores and windows at which the walk can go wrong"""
+    far = 1 << 40
+    out = []
+    for n in WALK_STORES:
+        tid, pos = store("distinct", n)   # tid 7, pos = 3 i - 1000: negative up to record 333
+        q = _windows_at(pos, n, 7)
+        q += [(7, -far, WHI_WIDE), (7, -(1 << 31) - 5, -1), (7, -2000, WHI_WIDE), (7, 5, 4), (7, WHI_WIDE, -far), (7, -1000, -1001),
+              (6, -far, WHI_WIDE), (8, -far, WHI_WIDE), (0, 0, 0), (2**31 - 1, -far, far), (-1, -far, far)]
+        out.append(("distinct-%d" % n, "distinct", n, n, q))
+    # the store ends inside the window although the memory behind it holds records that would lie inside
+    _, pos = store("distinct", 129 + 64)
+    out.append(("prefix-128", "distinct", 129 + 64, 128, [(7, -far, WHI_WIDE), (7, int(pos[64]), int(pos[191])), (7, int(pos[127]), int(pos[128])), (7, int(pos[128]), WHI_WIDE)]))
+    out.append(("prefix-0", "distinct", 64, 0, [(7, -far, WHI_WIDE), (7, -1000, -1000)]))
+    # a window that ends with its chromosome while the next one starts at positions <= whi; absent chromosomes; one behind the last
+    for n in WALK_TID_STORES:
+        tid, pos = store("tids", n)
+        per = n // len(TIDS)
+        q = []
+        for c, t in enumerate(TIDS):
+            end = (c + 1) * per
+            for k in (1, 2, 63, 64, 65, 66, 128):
+                if k <= per:
+                    q.append((t, int(pos[end - k]), WHI_WIDE))
+            q += [(t, -far, WHI_WIDE), (t, -1, -1), (t, int(pos[end - 1]) + 1, WHI_WIDE)]
+        q += [(t, -far, WHI_WIDE) for t in (0, 3, 4, 7, 8, 10, 11)]
+        out.append(("tids-%d" % n, "tids", n, n, q))
+    # runs of equal positions across wlo and across whi
+    n = WALK_RUN_STORE
+    tid, pos = store("runs", n)
+    q = []
+    for length, start in runs_layout(n):
+        v, before, after = int(pos[start]), int(pos[start - 1]), int(pos[start + length])
+        q += [(7, v, v), (7, v + 1, after), (7, v + 1, WHI_WIDE), (7, before, v), (7, before, v - 1), (7, -far, v), (7, -far, v - 1), (7, v, after)]
+    out.append(("runs-%d" % n, "runs", n, n, q))
+    return out
+
+
+def walk_arrays(queries):
+    return (np.array([t for t, _, _ in queries], np.int32), np.array([lo for _, lo, _ in queries], np.int64), np.array([hi for _, _, hi in queries], np.int64))
+
+
+def count_store(n=COUNT_STORE):
+    """a `tids` store with a hit byte (0, or 1 / 2 / 255: three records in four are hits) and a key byte per record: half of them
+    0 ... 3, the others over the whole range; the first chromosome's first records are hits with the last key of every COUNT_NKEYS,
+    with key 0 and with key 255 (out of range for every nkeys) whatever the draw"""
+    tid, pos = store("tids", n)
+    rng = np.random.default_rng([77, n])
+    hit = rng.choice(np.array([0, 1, 2, 255], np.uint8), n)
+    key = np.where(rng.random(n) < 0.5, rng.integers(0, 4, n), rng.integers(0, 256, n)).astype(np.uint8)
+    fixed = [255, 0] + [k - 1 for k in COUNT_NKEYS if k > 1]
+    key[:len(fixed)], hit[:len(fixed)] = fixed, 1
+    return tid, pos, hit, key
+
+
+def count_queries(tid, pos):
+    """five windows: a whole chromosome, an absent one (a row of zeros), 64 records, everything of the first chromosome from its start,
+    the last chromosome up to the store's end"""
+    n = len(tid)
+    per = n // len(TIDS)
+    far = 1 << 40
+    return [(TIDS[0], -far, WHI_WIDE), (3, -far, WHI_WIDE), (TIDS[2], int(pos[2 * per + 10]), int(pos[2 * per + 73])), (TIDS[0], -1, int(pos[per - 1])),
+            (TIDS[-1], int(pos[n - 65]), WHI_WIDE)]
+
+
+def count_reference(tid, pos, hit, key, qt, qlo, qhi, nkeys):
+    """[nq][nkeys] uint32: the hits of [L, R) per key, a key >= nkeys counted as key 0"""
+    L, R, _ = walk_reference(tid, pos, qt, qlo, qhi)
+    out = np.zeros((len(qt), nkeys), np.uint32)
+    for q, (a, b) in enumerate(zip(L, R)):
+        k = key[a:b][hit[a:b] != 0].astype(np.int64)
+        out[q] = np.bincount(np.where(k < nkeys, k, 0), minlength=nkeys)
+    return out

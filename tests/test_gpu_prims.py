@@ -1,7 +1,8 @@
 """The shared primitives of pass 1 and of the query kernels on their own, through tests/prims/prims.hip: the three-launch scan
 (scan_launch, as K9 calls it), the look-back scan (scan_launch_lb, the three instantiations of K3), the walk itself as
-k6_place_kernel calls it (lookback_exclusive) and the 64-ary search of K8 / KS / KI (wave_lower_bound), each against the CPU
-references of tests/prims_cases.py at the sizes where their routes, windows and rounds change.  Every comparison is exact.
+k6_place_kernel calls it (lookback_exclusive), the 64-ary search of K8 / KS / KI (wave_lower_bound), the window walk they build
+on it (wave_window_walk) and the per-wave key counters of K8 / KS (WaveKeyCounts), each against the CPU references of
+tests/prims_cases.py at the sizes where their routes, windows, rounds and steps change.  Every comparison is exact.
 
 The look-back launches keep to the scan's preconditions (state sized for n_upper and zero once, a fresh stamp per launch); the
 harness refuses a call that would not, and no such launch is ever made."""
@@ -24,6 +25,7 @@ _u32p = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
 _u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
+_u8p = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 
 
 @pytest.fixture(scope="module")
@@ -45,6 +47,8 @@ def lib():
     so.prims_lb_state_free.restype = None
     so.prims_lb_head.argtypes = [_u32p, _u32p, u32, u32, vp, u32]
     so.prims_search.argtypes = [_i32p, _i32p, u64, u64, _i32p, _i64p, u32, _u64p]
+    so.prims_walk.argtypes = [_i32p, _i32p, u64, u64, _i32p, _i64p, _i64p, u32, _u32p, _u32p, _u32p]
+    so.prims_key_counts.argtypes = [_i32p, _i32p, u64, _u8p, _u8p, _i32p, _i64p, _i64p, u32, ctypes.c_int, _u32p]
     return so
 
 
@@ -302,3 +306,82 @@ def test_wave_search_beyond_2_26_records(lib):
     want = pc.search_reference(pc.keys_of(tid, pos, as_view=True), qt, qp)
     assert (want > 1 << 26).sum() > 10 and (want == n).sum() >= 3 and (want == 0).sum() >= 3
     check_search(got, want, qt, qp, "large")
+
+
+# ---- window walk and key counters ------------------------------------------------------------------------------------------
+
+WALK_CASES = {case[0]: case for case in pc.walk_cases()}
+WALK_FLAGS = "a body call without all 64 lanes (1) / lane l not at lane 0's index + l (2) / s not the record's pos or a record past n (4)"
+
+
+def run_walk(lib, tid, pos, n, queries):
+    qt, qlo, qhi = pc.walk_arrays(queries)
+    nq = len(qt)
+    visits, steps, flags = np.zeros((nq, len(tid)), np.uint32), np.zeros((nq, 64), np.uint32), np.zeros((nq, 64), np.uint32)
+    assert lib.prims_walk(tid, pos, n, len(tid), qt, qlo, qhi, nq, visits, steps, flags) == 0
+    return visits, steps, flags
+
+
+def check_walk(got, tid, pos, n, queries, what):
+    visits, steps, flags = got
+    L, R, want_steps = pc.walk_reference(tid, pos, *pc.walk_arrays(queries), n)
+    bad = np.flatnonzero((flags != 0).any(axis=1))
+    assert bad.size == 0, (what, WALK_FLAGS, "first query", queries[bad[0]], flags[bad[0]].tolist())
+    bad = np.flatnonzero((steps != want_steps[:, None]).any(axis=1))
+    assert bad.size == 0, (what, "steps: first wrong query", queries[bad[0]], "got", steps[bad[0]].tolist(), "want", int(want_steps[bad[0]]))
+    idx = np.arange(len(tid))
+    want = ((idx >= L[:, None]) & (idx < R[:, None])).astype(np.uint32)
+    bad = np.flatnonzero((visits != want).any(axis=1))
+    assert bad.size == 0, (what, "visits: first wrong query", queries[bad[0]], "want each of", (int(L[bad[0]]), int(R[bad[0]])), "once; differs at",
+                           np.flatnonzero(visits[bad[0]] != want[bad[0]])[:8].tolist())
+
+
+@pytest.mark.parametrize("label", list(WALK_CASES))
+def test_window_walk(lib, label):
+    """wave_window_walk over stores of 0 ... 64 * 65 records and windows of 0, 1, 63, 64, 65 and 128 records at the store's first
+    record, ending at its last (the extra step of a window of whole steps then runs wholly behind n) and in the middle; windows that
+    end with their chromosome while the next one starts at positions <= whi; absent chromosomes; runs of equal positions at wlo - 1,
+    wlo, whi and whi + 1; wlo negative, whi = 2^31 - 2 + 2^30, wlo > whi; a store that ends inside the window.  Per query: every
+    record of [L, R) handed to the body once with `in` and no other, (R - L) / 64 + 1 steps on every lane, all 64 lanes in every
+    body call, consecutive records in consecutive lanes"""
+    _, family, n_upper, n, queries = WALK_CASES[label]
+    tid, pos = pc.store(family, n_upper)
+    check_walk(run_walk(lib, tid, pos, n, queries), tid, pos, n, queries, label)
+
+
+@pytest.mark.parametrize("nq", pc.QUERY_COUNTS)
+def test_window_walk_with_idle_waves_and_a_second_block(lib, nq):
+    """one query (three waves of the block leave at once), four (a full block), five (one wave of a second block)"""
+    for label in ("distinct-129", "tids-%d" % pc.WALK_TID_STORES[0]):
+        _, family, n_upper, n, queries = WALK_CASES[label]
+        tid, pos = pc.store(family, n_upper)
+        for first in (0, 9, len(queries) - nq):
+            q = queries[first:first + nq]
+            assert len(q) == nq
+            check_walk(run_walk(lib, tid, pos, n, q), tid, pos, n, q, (label, nq, first))
+
+
+@pytest.fixture(scope="module")
+def count_case():
+    tid, pos, hit, key = pc.count_store()
+    for a in (tid, pos, hit, key):
+        a.setflags(write=False)
+    return tid, pos, hit, key, pc.count_queries(tid, pos)
+
+
+@pytest.mark.parametrize("nq", pc.QUERY_COUNTS)
+@pytest.mark.parametrize("nkeys", pc.COUNT_NKEYS)
+def test_wave_key_counts(lib, count_case, nkeys, nq):
+    """WaveKeyCounts under the walk, as K8 and KS use it: one key by ballot + popcount, 2, 64, 65 and 255 keys through the per-wave LDS
+    rows, hits with a key >= nkeys counted as key 0, against numpy.bincount over [L, R); with one query and with five the last block
+    has three waves without a query, which reach both barriers and leave their rows of the prefilled output untouched"""
+    tid, pos, hit, key, queries = count_case
+    qt, qlo, qhi = pc.walk_arrays(queries[:nq])
+    rows = (nq + 3) // 4 * 4
+    got = np.zeros((rows, nkeys), np.uint32)
+    assert lib.prims_key_counts(tid, pos, len(tid), hit, key, qt, qlo, qhi, nq, nkeys, got) == 0
+    want = pc.count_reference(tid, pos, hit, key, qt, qlo, qhi, nkeys)
+    bad = np.flatnonzero((got[:nq] != want).any(axis=1))
+    assert bad.size == 0, (nkeys, nq, "first wrong query", queries[bad[0]], "keys", np.flatnonzero(got[bad[0]] != want[bad[0]])[:8].tolist(),
+                           "got", got[bad[0]][got[bad[0]] != want[bad[0]]][:8].tolist(), "want", want[bad[0]][got[bad[0]] != want[bad[0]]][:8].tolist())
+    assert (got[nq:] == pc.FILL).all(), (nkeys, nq, "a wave without a query wrote its row")

@@ -1,4 +1,4 @@
-"""tests/prims_cases.py on its own: the two references against plain loops, and the case tables against the edges that
+"""tests/prims_cases.py on its own: the references against plain loops, and the case tables against the edges that
 tests/test_gpu_prims.py relies on them to hold (a table that lost an edge would let the GPU tests pass for nothing)."""
 import numpy as np
 import pytest
@@ -59,6 +59,48 @@ def test_search_reference_is_the_first_record_not_below(family):
         if n > 10:  # a prefix of the store
             want = [naive_lower_bound(tid.tolist(), pos.tolist(), n - 7, int(t), int(p)) for t, p in zip(qt, qp)]
             assert pc.search_reference(pc.keys_of(tid, pos), qt, qp, n - 7).tolist() == want
+
+
+def naive_walk(tid, pos, n, t, wlo, whi):
+    L = R = naive_lower_bound(tid, pos, n, t, wlo)
+    while R < n and tid[R] == t and pos[R] <= whi:
+        R += 1
+    return L, R, (R - L) // 64 + 1
+
+
+def test_walk_reference_is_the_plain_loop():
+    for label, family, n_upper, n, queries in pc.walk_cases():
+        tid, pos = pc.store(family, n_upper)
+        qt, qlo, qhi = pc.walk_arrays(queries)
+        L, R, steps = pc.walk_reference(tid, pos, qt, qlo, qhi, n)
+        want = [naive_walk(tid.tolist(), pos.tolist(), n, t, lo, hi) for t, lo, hi in queries]
+        assert list(zip(L.tolist(), R.tolist(), steps.tolist())) == want, label
+    # a grid of windows over a store with runs, and bounds far outside 32 bits on a store whose positions reach both ends of the int32 range
+    tid, pos = pc.store("runs", 700)
+    pos = pos.copy()
+    pos[0], pos[-1] = -2**31, 2**31 - 1
+    far = 1 << 40
+    q = [(7, int(p) + d, int(p2) + e) for p in pos[::37] for p2 in pos[5::91] for d in (-1, 0, 1) for e in (-1, 0, 1)]
+    q += [(7, -far, far), (7, -2**31, 2**31 - 1), (7, -2**31 - 1, -2**31), (7, 2**31 - 1, pc.WHI_WIDE), (7, 2**31, far), (6, -far, far), (8, -far, far)]
+    L, R, steps = pc.walk_reference(tid, pos, *pc.walk_arrays(q))
+    assert list(zip(L.tolist(), R.tolist(), steps.tolist())) == [naive_walk(tid.tolist(), pos.tolist(), 700, *x) for x in q]
+
+
+def test_count_reference_is_the_plain_loop():
+    tid, pos, hit, key = pc.count_store()
+    queries = pc.count_queries(tid, pos)
+    qt, qlo, qhi = pc.walk_arrays(queries)
+    for nkeys in pc.COUNT_NKEYS:
+        want = []
+        for t, lo, hi in queries:
+            L, R, _ = naive_walk(tid.tolist(), pos.tolist(), len(tid), t, lo, hi)
+            row = [0] * nkeys
+            for i in range(L, R):
+                if hit[i]:
+                    row[int(key[i]) if key[i] < nkeys else 0] += 1
+            want.append(row)
+        got = pc.count_reference(tid, pos, hit, key, qt, qlo, qhi, nkeys)
+        assert got.dtype == np.uint32 and got.tolist() == want
 
 
 # ---- the tables ------------------------------------------------------------------------------------------------------------
@@ -176,3 +218,90 @@ def test_large_store_is_a_formula_over_the_index():
         assert tid[i] == (i >> 24) * 2 + 1 and pos[i] == ((i & ((1 << 24) - 1)) >> 1) * 3 - 1
     k = tid.astype(np.int64) * (1 << 32) + pos
     assert (np.diff(k) >= 0).all() and pos[0] == -1 and pos[1 << 24] == -1
+
+
+def walk_table():
+    """every case of walk_cases with its store and reference: (label, tid, pos, n, queries, L, R, steps)"""
+    for label, family, n_upper, n, queries in pc.walk_cases():
+        tid, pos = pc.store(family, n_upper)
+        yield (label, tid, pos, n, queries) + pc.walk_reference(tid, pos, *pc.walk_arrays(queries), n)
+
+
+def test_walk_cases_hold_every_store_count_and_place():
+    assert pc.WALK_STORES == [0, 1, 63, 64, 65, 128, 129, 64 * 65] and pc.WALK_COUNTS == [0, 1, 63, 64, 65, 128]
+    assert pc.WHI_WIDE == 2**31 - 2 + 2**30 and pc.WHI_WIDE >= 1 << 31
+    table = {row[0]: row for row in walk_table()}
+    assert {"distinct-%d" % n for n in pc.WALK_STORES} <= set(table)
+    for n in pc.WALK_STORES:
+        _, tid, pos, m, queries, L, R, steps = table["distinct-%d" % n]
+        assert m == n == len(tid)
+        on7 = np.array([t == 7 for t, _, _ in queries])
+        for k in pc.WALK_COUNTS:
+            if k > n:
+                continue
+            has = (R - L == k) & on7
+            assert (has & (L == 0)).any(), (n, k, "at the first record")
+            assert (has & (R == n)).any(), (n, k, "ending at the last record")
+            if n - k >= 2 and k:
+                assert (has & (L > 0) & (R < n)).any(), (n, k, "in the middle")
+        assert any(lo < 0 for _, lo, _ in queries) and any(hi == pc.WHI_WIDE for _, _, hi in queries) and any(lo > hi for _, lo, hi in queries)
+        assert any(t < 7 for t, _, _ in queries) and any(t > 7 for t, _, _ in queries)
+        assert (steps == (R - L) // 64 + 1).all() and (R >= L).all()
+    # the extra step wholly behind n: whole steps of records that end with the store
+    _, _, _, _, _, L, R, steps = table["distinct-%d" % (64 * 65)]
+    assert ((R == 64 * 65) & (R - L == 64)).any() and ((R == 64 * 65) & (R - L == 128)).any() and (steps == 66).any()
+    # a store that ends inside the window while records that would lie inside follow it in memory
+    _, tid, pos, n, queries, L, R, _ = table["prefix-128"]
+    assert n == 128 < len(tid) and (R == n).any() and any(hi >= pos[n] and lo <= pos[n] for _, lo, hi in queries) and (R <= n).all()
+    assert table["prefix-0"][3] == 0 and (table["prefix-0"][7] == 1).all()
+
+
+def test_walk_cases_stop_on_the_chromosome_and_cut_runs_whole():
+    table = {row[0]: row for row in walk_table()}
+    counts = set()
+    for n in pc.WALK_TID_STORES:
+        _, tid, pos, _, queries, L, R, _ = table["tids-%d" % n]
+        for (t, lo, hi), a, b in zip(queries, L.tolist(), R.tolist()):
+            # the window's last record is the chromosome's last and the next chromosome starts at a position <= whi
+            if a < b < n and tid[b] != t and tid[b - 1] == t and pos[b] <= hi:
+                counts.add(b - a)
+        present = set(tid.tolist())
+        assert any(t not in present and min(present) < t < max(present) and a == b for (t, _, _), a, b in zip(queries, L, R))   # absent
+        assert any(t > max(present) and a == b == n for (t, _, _), a, b in zip(queries, L, R))                               # behind the last
+        assert any(t < min(present) and a == b == 0 for (t, _, _), a, b in zip(queries, L, R))
+    assert {1, 2, 63, 64, 65, 66, 128} <= counts, counts
+    _, tid, pos, n, queries, L, R, _ = table["runs-%d" % pc.WALK_RUN_STORE]
+    layout = pc.runs_layout(n)
+    assert {length for length, _ in layout} == {1, 64, 65}
+    got = set(zip(L.tolist(), R.tolist()))
+    for length, start in layout:
+        end = start + length
+        assert (start, end) in got                                  # wlo == whi == the run's position: all of it, nothing else
+        assert any(a == end for a, _ in got)                        # the run at wlo - 1: none of it
+        assert any(b == end and a < start for a, b in got)          # the run at whi: all of it
+        assert any(b == start and a < start for a, b in got)        # the run at whi + 1: none of it
+        assert not any(start < a < end or start < b < end for a, b in got), "a window cuts a run of equal positions"
+
+
+def test_count_cases_hold_every_key_count_and_out_of_range_keys():
+    assert pc.COUNT_NKEYS == [1, 2, 64, 65, 255]
+    tid, pos, hit, key = pc.count_store()
+    assert hit.dtype == np.uint8 and key.dtype == np.uint8 and len(hit) == len(key) == len(tid) == pc.COUNT_STORE
+    assert set(np.unique(hit)) == {0, 1, 2, 255} and 0.6 < (hit != 0).mean() < 0.9 and (key < 4).mean() > 0.4 and (key >= 65).mean() > 0.3
+    queries = pc.count_queries(tid, pos)
+    assert len(queries) == 5       # one, four and five queries are its first one, four and all
+    qt, qlo, qhi = pc.walk_arrays(queries)
+    L, R, _ = pc.walk_reference(tid, pos, qt, qlo, qhi)
+    assert (R - L)[1] == 0 and 64 in (R - L).tolist() and (R == len(tid)).any() and (L == 0).any()
+    for nkeys in pc.COUNT_NKEYS:
+        ref = pc.count_reference(tid, pos, hit, key, qt, qlo, qhi, nkeys)
+        assert ref.shape == (5, nkeys) and ref[1].sum() == 0 and ref[0].sum() > 0
+        for q in (0, 2, 3, 4):
+            sl = slice(L[q], R[q])
+            assert ref[q].sum() == (hit[sl] != 0).sum()
+            if q == 0 or nkeys < 255:                                # hits with a key out of range: key 255 in the first window, whatever nkeys
+                assert ((key[sl] >= nkeys) & (hit[sl] != 0)).any()
+            assert ref[q, 0] == (((key[sl] >= nkeys) | (key[sl] == 0)) & (hit[sl] != 0)).sum()
+        if nkeys > 1:
+            assert np.count_nonzero(ref[:, 1:].sum(axis=0)) >= min(nkeys - 1, 16)   # (the counts are spread over the keys ...
+            assert ref[0, nkeys - 1] > 0                                             # ... and the first query has the last one)
