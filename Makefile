@@ -42,8 +42,9 @@ bin/bdx-ci-check: $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp
 
-# test tooling: the shared scan, wave-search and window-walk headers on their own behind plain C entry points (tests/test_gpu_prims.py)
-tests/prims/libbdx_prims.so: tests/prims/prims.hip $(CSRC)/bdx_scan.h $(CSRC)/bdx_wave_search.h $(CSRC)/bdx_window.h $(CSRC)/bdx_dev.h include/bdx.h
+# test tooling: the shared scan, wave-search, window-walk and insertion-merge headers on their own behind plain C entry points
+# (tests/test_gpu_prims.py, tests/test_gpu_insert.py)
+tests/prims/libbdx_prims.so: tests/prims/prims.hip $(CSRC)/bdx_scan.h $(CSRC)/bdx_wave_search.h $(CSRC)/bdx_window.h $(CSRC)/bdx_insert.h $(CSRC)/bdx_k3.h $(CSRC)/bdx_dev.h include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -shared -o $@ $<
 
 # measurement tool (bench.py): the feeder's ceilings -- page cache -> pinned -> HBM

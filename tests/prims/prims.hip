@@ -1,15 +1,21 @@
-// Test-only harness (tests/test_gpu_prims.py) around the shared primitive headers, included unchanged: csrc/bdx_scan.h
-// (the three-launch scan, the look-back scan and its walk), csrc/bdx_wave_search.h and csrc/bdx_window.h (the window walk of the
-// query kernels and their per-wave key counters).  Built into tests/prims/libbdx_prims.so;
+// Test-only harness (tests/test_gpu_prims.py, tests/test_gpu_insert.py) around the shared primitive headers, included unchanged:
+// csrc/bdx_scan.h (the three-launch scan, the look-back scan and its walk), csrc/bdx_wave_search.h and csrc/bdx_window.h (the window
+// walk of the query kernels and their per-wave key counters), and csrc/bdx_insert.h (K6's order-key insertion merge: k6_ranksort_kernel
+// and k6_insert_kernel through the header's own two launches, and its bucket function).  Built into tests/prims/libbdx_prims.so;
 // nothing of it is part of libbdx.so.  Every entry point takes host pointers, does its own allocations and copies, waits for
 // the stream and returns HIP's error code (hipErrorInvalidValue for a call that breaks a precondition of the look-back scan:
 // such a launch would spin, so it is refused here and never made).  Elements are uint32_t words, a U4 four of them in a row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string.h>
+
+#include <algorithm>
 #include <new>
 #include <unordered_set>
+#include <vector>
 
+#include "bdx_insert.h"
 #include "bdx_scan.h"
 #include "bdx_wave_search.h"
 #include "bdx_window.h"
@@ -344,6 +350,188 @@ int prims_key_counts(const int32_t* tid, const int32_t* pos, uint64_t n, const u
     CK(hipGetLastError());
     CK(hipStreamSynchronize(nullptr));
     CK(hipMemcpy(counts, dc.p, cbytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- K6's order-key insertion merge (csrc/bdx_insert.h) ---------------------------------------------------------------------
+
+namespace {
+
+constexpr size_t kInsGuard = 256;   // bytes of 0xA5 behind every array of the buffer set
+
+struct PinBuf {
+    void* p = nullptr;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault); }
+    template <class T> T* as() const { return (T*)p; }
+};
+
+// One buffer set, kept from call to call as a context's is: the arrays of StageBufs::b_ins in size_k6's order (old_key [p2] u64 |
+// hs_key_dev [sv] u64 | old_slot [p2] | ins_T, ins_src, ins_pre_l, ins_pre_c [sv + 1] each | sorted_key [nsort] u64 | sorted_slot
+// [nsort] | rank_part [kK6RankSlices][nsort]), a guard behind each; the staging records, the counters, and the host's list in pinned memory
+struct InsHandle {
+    uint32_t sv_cap = 0, p2 = 0, nsort = 0, stage_n = 0;
+    bool with_rank = false;
+    DevBuf ins, stage, counts;
+    PinBuf hs_key, hs_cnt;
+    enum { kOldKey, kHsKeyDev, kOldSlot, kInsT, kInsSrc, kPreL, kPreC, kSortedKey, kSortedSlot, kRankPart, kArrays };
+    size_t off[kArrays] = {}, bytes[kArrays] = {}, total = 0;
+    template <class T> T* at(int i) const { return (T*)((char*)ins.p + off[i]); }
+    void lay_out() {
+        const size_t sv = sv_cap, each[kArrays] = {(size_t)p2 * 8, sv * 8, (size_t)p2 * 4, (sv + 1) * 4, (sv + 1) * 4, (sv + 1) * 4, (sv + 1) * 4,
+                                                   (size_t)nsort * 8, (size_t)nsort * 4, with_rank ? (size_t)nsort * 4 * kK6RankSlices : 0};
+        size_t o = 0;
+        for (int i = 0; i < kArrays; ++i) {
+            off[i] = o; bytes[i] = each[i];
+            o = (o + each[i] + kInsGuard + 7) & ~(size_t)7;
+        }
+        total = o;
+    }
+    size_t guard_bytes(int i) const { return (i + 1 < kArrays ? off[i + 1] : total) - off[i] - bytes[i]; }
+};
+
+__global__ __launch_bounds__(256) void ins_bucket_kernel(const uint64_t* keys, uint32_t n, uint32_t n_regions, int period_arg, uint32_t* out) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t period = (uint32_t)max(period_arg, 1);   // (as InsertJob reads K6Arrays::period)
+    out[i] = ins_bucket_of(keys[i], period, ins_bucket_span(n_regions, period));
+}
+
+// the kernel's preconditions: keys of the device's list that differ, none sharing (T, own, start) with a key of the host's (a start vertex
+// is walked by one side), the host's ascending, nothing beyond a capacity, counts that fit their 16 bits
+bool ins_admits(const InsHandle* h, const uint64_t* old_key, const uint32_t* old_slot, const uint32_t* cnt_by_slot, uint32_t nd, const uint64_t* hs_key, uint32_t nh) {
+    if (nd > h->p2 || nh > h->sv_cap) return false;
+    // (the rank sort takes 2,049 ... kK6RankSortMax entries before anything looks at sv_cap, and rank_part is sized for min(sv_cap, kK6RankSortMax))
+    if (h->with_rank && nd > kInsLds && nd <= kK6RankSortMax && nd > h->nsort) return false;
+    for (uint32_t j = 1; j < nh; ++j)
+        if (hs_key[j] < hs_key[j - 1]) return false;
+    std::vector<uint64_t> k(old_key, old_key + nd);
+    std::sort(k.begin(), k.end());
+    for (uint32_t d = 1; d < nd; ++d)
+        if (k[d] == k[d - 1]) return false;
+    std::unordered_set<uint64_t> host;
+    for (uint32_t j = 0; j < nh; ++j) host.insert(hs_key[j] >> kKeyShiftStart);
+    for (uint32_t d = 0; d < nd; ++d) {
+        if (host.count(old_key[d] >> kKeyShiftStart)) return false;
+        if (old_slot[d] >= h->stage_n) return false;
+        if (cnt_by_slot[2 * (size_t)old_slot[d]] >= 65536u || cnt_by_slot[2 * (size_t)old_slot[d] + 1] >= 65536u) return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// out: [11] kInsThreads, kInsLds, kInsBucketMax, kInsCntLds, kInsBuckets, kInsBucketDepth, kK6RankSortMax, kK6RankSlices, kRankGrid, kRankTile, kScanBlock
+void prims_insert_constants(uint32_t* out) {
+    const uint32_t v[11] = {kInsThreads, kInsLds, kInsBucketMax, kInsCntLds, kInsBuckets, kInsBucketDepth, kK6RankSortMax, kK6RankSlices, kRankGrid, kRankTile, (uint32_t)kScanBlock};
+    memcpy(out, v, sizeof(v));
+}
+
+// the header's bucket function over an array, a lane per key
+int prims_insert_bucket(const uint64_t* keys, uint32_t n, uint32_t n_regions, int period, uint32_t* out_bucket) {
+    if (!n) return 0;
+    DevBuf dk, db;
+    CK(dk.alloc((size_t)n * 8));
+    CK(db.alloc((size_t)n * 4));
+    CK(hipMemcpy(dk.p, keys, (size_t)n * 8, hipMemcpyHostToDevice));
+    CK(hipMemset(db.p, kFill, (size_t)n * 4));
+    hipLaunchKernelGGL(ins_bucket_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, dk.as<uint64_t>(), n, n_regions, period, db.as<uint32_t>());
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(nullptr));
+    CK(hipMemcpy(out_bucket, db.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// a buffer set for up to sv_cap merged entries; staging slots: 2 * sv_cap (a candidate consumes a read pair); everything starts out as 0xA5 bytes
+int prims_insert_open(uint32_t sv_cap, int with_rank_part, void** out) {
+    if (!sv_cap || sv_cap > (1u << 20)) return (int)hipErrorInvalidValue;
+    InsHandle* h = new (std::nothrow) InsHandle;
+    if (!h) return (int)hipErrorOutOfMemory;
+    h->sv_cap = sv_cap;
+    h->p2 = 1;
+    while (h->p2 < sv_cap) h->p2 <<= 1;
+    h->nsort = std::min(sv_cap, kK6RankSortMax);
+    h->stage_n = 2 * sv_cap;
+    h->with_rank = with_rank_part != 0;
+    h->lay_out();
+    hipError_t e = h->ins.alloc(h->total);
+    if (e == hipSuccess) e = hipMemset(h->ins.p, kFill, h->total);
+    if (e == hipSuccess) e = h->stage.alloc((size_t)h->stage_n * sizeof(SvOut));
+    if (e == hipSuccess) e = hipMemset(h->stage.p, kFill, (size_t)h->stage_n * sizeof(SvOut));
+    if (e == hipSuccess) e = h->counts.alloc(sizeof(StageCounts));
+    if (e == hipSuccess) e = h->hs_key.alloc((size_t)sv_cap * 8);
+    if (e == hipSuccess) e = h->hs_cnt.alloc((size_t)sv_cap * 4);
+    if (e != hipSuccess) { delete h; return (int)e; }
+    *out = h;
+    return 0;
+}
+void prims_insert_close(void* handle) { delete (InsHandle*)handle; }
+
+// old_key / old_slot: [nd] the device's list, any order; cnt_by_slot: [2 * sv_cap][2] lib_count, cn_count of the staging record of every slot;
+// hs_key: [nh] ascending, hs_cnt: [nh] lib_count | cn_count << 16.  out_T / out_src / out_pre_l / out_pre_c: [sv_cap + 1] the four arrays as
+// the launch left them (0xA5 bytes before it); out_counts: n_ins (0xA5A5A5A5 before the launch), overflow (0 before it), and 1 where a guard byte changed
+int prims_insert_run(void* handle, const uint64_t* old_key, const uint32_t* old_slot, const uint32_t* cnt_by_slot, uint32_t nd, const uint64_t* hs_key,
+                     const uint32_t* hs_cnt, uint32_t nh, uint32_t n_regions, int period, int ins_plain, uint32_t* out_T, uint32_t* out_src, uint32_t* out_pre_l,
+                     uint32_t* out_pre_c, uint32_t* out_counts) {
+    InsHandle* h = (InsHandle*)handle;
+    if (!h || !ins_admits(h, old_key, old_slot, cnt_by_slot, nd, hs_key, nh)) return (int)hipErrorInvalidValue;
+    const size_t sv1 = (size_t)h->sv_cap + 1;
+    for (int i = 0; i < InsHandle::kArrays; ++i) CK(hipMemset((char*)h->ins.p + h->off[i] + h->bytes[i], kFill, h->guard_bytes(i)));
+    for (int i = InsHandle::kInsT; i <= InsHandle::kPreC; ++i) CK(hipMemset((char*)h->ins.p + h->off[i], kFill, h->bytes[i]));
+    if (nd) {
+        CK(hipMemcpy(h->at<uint64_t>(InsHandle::kOldKey), old_key, (size_t)nd * 8, hipMemcpyHostToDevice));
+        CK(hipMemcpy(h->at<uint32_t>(InsHandle::kOldSlot), old_slot, (size_t)nd * 4, hipMemcpyHostToDevice));
+    }
+    {
+        std::vector<SvOut> st(h->stage_n);
+        memset(st.data(), kFill, st.size() * sizeof(SvOut));
+        for (uint32_t s = 0; s < h->stage_n; ++s) {
+            st[s].sv.lib_count = (int32_t)std::min(cnt_by_slot[2 * (size_t)s], 65535u);   // (a slot no entry names may hold anything)
+            st[s].sv.cn_count = (int32_t)std::min(cnt_by_slot[2 * (size_t)s + 1], 65535u);
+        }
+        CK(hipMemcpy(h->stage.p, st.data(), st.size() * sizeof(SvOut), hipMemcpyHostToDevice));
+    }
+    if (nh) {
+        memcpy(h->hs_key.p, hs_key, (size_t)nh * 8);
+        memcpy(h->hs_cnt.p, hs_cnt, (size_t)nh * 4);
+    }
+    StageCounts sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.n_old = nd; sc.n_regions = n_regions; sc.n_ins = 0xA5A5A5A5u;
+    CK(hipMemcpy(h->counts.p, &sc, sizeof(sc), hipMemcpyHostToDevice));
+    K6Arrays a;
+    memset(&a, 0, sizeof(a));
+    a.sv_cap = h->sv_cap;
+    a.old_key = h->at<uint64_t>(InsHandle::kOldKey); a.hs_key_dev = h->at<uint64_t>(InsHandle::kHsKeyDev); a.old_slot = h->at<uint32_t>(InsHandle::kOldSlot);
+    a.ins_T = h->at<uint32_t>(InsHandle::kInsT); a.ins_src = h->at<uint32_t>(InsHandle::kInsSrc);
+    a.ins_pre_l = h->at<uint32_t>(InsHandle::kPreL); a.ins_pre_c = h->at<uint32_t>(InsHandle::kPreC);
+    a.sorted_key = h->at<uint64_t>(InsHandle::kSortedKey); a.sorted_slot = h->at<uint32_t>(InsHandle::kSortedSlot);
+    a.rank_part = h->with_rank ? h->at<uint32_t>(InsHandle::kRankPart) : nullptr;
+    a.sv_stage = h->stage.as<SvOut>();
+    a.hs_key = h->hs_key.as<uint64_t>(); a.hs_cnt = h->hs_cnt.as<uint32_t>(); a.nh = nh;
+    a.counts = h->counts.as<StageCounts>();
+    a.period = period; a.ins_plain = ins_plain;
+    if (a.rank_part) launch_k6_ranksort(a, nullptr);
+    launch_k6_insert(a, nullptr);
+    CK(hipGetLastError());
+    CK(hipStreamSynchronize(nullptr));
+    CK(hipMemcpy(out_T, a.ins_T, sv1 * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(out_src, a.ins_src, sv1 * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(out_pre_l, a.ins_pre_l, sv1 * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(out_pre_c, a.ins_pre_c, sv1 * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(&sc, h->counts.p, sizeof(sc), hipMemcpyDeviceToHost));
+    out_counts[0] = sc.n_ins; out_counts[1] = sc.overflow; out_counts[2] = 0;
+    std::vector<unsigned char> g;
+    for (int i = 0; i < InsHandle::kArrays; ++i) {
+        g.resize(h->guard_bytes(i));
+        CK(hipMemcpy(g.data(), (char*)h->ins.p + h->off[i] + h->bytes[i], g.size(), hipMemcpyDeviceToHost));
+        for (unsigned char b : g)
+            if (b != kFill) out_counts[2] = 1;
+    }
     return 0;
 }
 
