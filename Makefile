@@ -6,9 +6,9 @@ HOST := breakdancer_amd/host
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Iinclude
 KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/kq_queries.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/bdx_api.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
-HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp
+HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp $(HOST)/table.cpp $(HOST)/store_counts.cpp $(HOST)/inputs.cpp
 
-all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-feed-probe tests/prims/libbdx_prims.so oracle
+all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-table-check bin/bdx-feed-probe tests/prims/libbdx_prims.so oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -24,9 +24,9 @@ breakdancer_amd/libbdx.so: $(OBJS)
 
 HOSTFLAGS := -O2 -std=c++17 -ffp-contract=off -Wall -Iinclude -pthread
 
-bin/breakdancer-max: $(HOSTCOMMON) $(HOST)/main.cpp $(wildcard $(HOST)/*.h) $(CSRC)/bdx_exclude.h breakdancer_amd/libbdx.so
+bin/breakdancer-max: $(HOSTCOMMON) $(HOST)/main.cpp $(HOST)/phases.cpp $(wildcard $(HOST)/*.h) $(CSRC)/bdx_exclude.h breakdancer_amd/libbdx.so
 	@mkdir -p bin
-	g++ $(HOSTFLAGS) -o $@ $(HOSTCOMMON) $(HOST)/main.cpp -Lbreakdancer_amd -lbdx -lz -Wl,-rpath,'$$ORIGIN/../breakdancer_amd' -Wl,-rpath,/opt/rocm/lib
+	g++ $(HOSTFLAGS) -o $@ $(HOSTCOMMON) $(HOST)/main.cpp $(HOST)/phases.cpp -Lbreakdancer_amd -lbdx -lz -Wl,-rpath,'$$ORIGIN/../breakdancer_amd' -Wl,-rpath,/opt/rocm/lib
 
 bin/bdx-inflate-check: $(HOST)/inflate_check_main.cpp $(HOST)/fast_inflate.cpp $(HOST)/fast_inflate.h $(HOST)/bgzf.h
 	@mkdir -p bin
@@ -41,6 +41,11 @@ bin/bdx-sites-check: $(HOST)/sites_check_main.cpp $(HOST)/sites.cpp $(HOST)/site
 bin/bdx-ci-check: $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/ci_check_main.cpp $(HOST)/vcf.cpp
+
+# test tooling: the table formatter (table.cpp) on its own, without libbdx (tests/test_table.py builds it again under the sanitizers)
+bin/bdx-table-check: $(HOST)/table_check_main.cpp $(HOST)/table.cpp $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/table.h $(HOST)/options.h $(HOST)/config.h include/bdx.h
+	@mkdir -p bin
+	g++ $(HOSTFLAGS) -o $@ $(HOST)/table_check_main.cpp $(HOST)/table.cpp $(HOST)/options.cpp $(HOST)/config.cpp
 
 # test tooling: the shared scan, wave-search, window-walk and insertion-merge headers on their own behind plain C entry points
 # (tests/test_gpu_prims.py, tests/test_gpu_insert.py)
@@ -64,7 +69,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-sites-check bin/bdx-ci-check tests/prims/libbdx_prims.so
+	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-table-check tests/prims/libbdx_prims.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -1,30 +1,18 @@
 // bdx-dump-reads: prints the producer's merged SoA stream (no GPU involved).  Used by the CPU tests to check the
 // BGZF/BAM decoder, the reader filter, RG->library resolution and the merge order against an independent decode.
 #include <cstdio>
-#include <fstream>
 #include <iostream>
 #include <stdexcept>
 
-#include "config.h"
-#include "exclude.h"
-#include "options.h"
+#include "inputs.h"
 #include "producer.h"
 
 int main(int argc, char** argv) {
     try {
         bdhost::Options opts(argc, argv);
-        std::ifstream in(opts.bam_config_path.c_str());
-        if (!in.is_open()) throw std::runtime_error("unable to open config file '" + opts.bam_config_path + "'");
-        bdhost::BamConfig cfg(in, opts.o.cut_sd);
-        bdhost::ExcludeTable exclude_table;   // --exclude: the masked stream
-        const bdhost::ExcludeTable* exclude = nullptr;
-        if (!opts.exclude.empty()) {
-            std::vector<std::string> names;
-            std::vector<uint32_t> lengths;
-            bdhost::read_targets(cfg, names, lengths);
-            bdhost::read_exclude_bed(opts.exclude, names, exclude_table);
-            exclude = &exclude_table;
-        }
+        const bdhost::BamConfig cfg = bdhost::open_config(opts.bam_config_path, opts.o.cut_sd);
+        const std::unique_ptr<bdhost::ExcludeTable> exclude_table = bdhost::open_exclude(opts.exclude, bdhost::FirstHeader(cfg));   // --exclude: the masked stream
+        const bdhost::ExcludeTable* exclude = exclude_table.get();
         bdhost::ReadStream rs;
         if (getenv("BDX_DUMP_MERGE")) bdhost::produce_merged_by_columns(cfg, opts.chr, exclude, 4, rs);   // (the device path's merge, on host-decoded columns)
         else bdhost::produce(cfg, opts.chr, exclude, 4, rs);

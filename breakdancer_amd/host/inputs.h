@@ -1,0 +1,86 @@
+// What a run is given, settled before the GPU is touched: the BDX_* environment knobs, the options (or the -R cache's), the
+// configuration, and the opened or parsed option inputs (--vcf, --exclude, --sites, --ci).  bdx-dump-reads shares the two helpers.
+#pragma once
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "bdx.h"
+#include "cache.h"
+#include "config.h"
+#include "exclude.h"
+#include "options.h"
+#include "sites.h"
+#include "vcf.h"
+
+namespace bdhost {
+
+// the configuration file at `path`; text (may be null) receives its contents, which the -C cache keeps
+BamConfig open_config(const std::string& path, int cut_sd, std::string* text = nullptr);
+
+// Reference sequences of the first BAM of the configuration, the one -o, --exclude and --sites are resolved against.  The header is
+// parsed when first asked for and once only: a run that needs no names opens no file here.
+class FirstHeader {
+public:
+    explicit FirstHeader(const BamConfig& cfg) : cfg_(cfg) {}
+    const std::vector<std::string>& names() const { load(); return names_; }
+    const std::vector<uint32_t>& lengths() const { load(); return lengths_; }
+
+private:
+    void load() const;
+    const BamConfig& cfg_;
+    mutable bool loaded_ = false;
+    mutable std::vector<std::string> names_;
+    mutable std::vector<uint32_t> lengths_;
+};
+
+// --exclude: the BED file at `path` ("": none, an empty pointer) -- a malformed line fails with FILE:LINE
+std::unique_ptr<ExcludeTable> open_exclude(const std::string& path, const FirstHeader& header);
+
+// Every BDX_* knob of the command, read once (README.md's table).
+struct Env {
+    std::vector<int> gpus;       // BDX_GPUS: "4" -> devices 0,1,2,3; "0,2,5" -> that list (a device may repeat: several ranks then share it)
+    bool decode_host = false;    // BDX_DECODE=host
+    int threads = 0;             // BDX_THREADS (0: not set)
+    int read_threads = 0;        // BDX_READ_THREADS (0: not set)
+    bool timing = false;         // BDX_TIMING
+    bool keep_results = false;   // BDX_TRIM=0
+    bool format_threads_set = false;
+    int format_threads = 0;      // BDX_FORMAT_THREADS
+    bool foreground = false;     // BDX_FOREGROUND
+    bool clean_exit = false;     // BDX_CLEAN_EXIT
+};
+Env read_env();
+
+struct Inputs {
+    // Fails in this order, each before the GPU is touched: option parsing, -R / config, (no BAM files: see no_bams), --vcf open, --exclude
+    // parse, --sites-vcf open and --sites parse, --ci window.
+    Inputs(int argc, char** argv, const Env& env);
+    Inputs(const Inputs&) = delete;
+    Inputs& operator=(const Inputs&) = delete;
+
+    Pass1Cache cache;            // -R <cache>: options, configuration and pass-1 statistics of the run that wrote the cache (ConfigLoader.cpp:19-23)
+    bool restored = false;
+    Options opts;
+    std::string config_text;
+    BamConfig cfg;
+    FirstHeader header;
+    bool no_bams = false;        // the configuration names no BAM file: nothing below was opened or parsed
+    bool want_dumps = false;     // -g / -d
+    std::unique_ptr<VcfWriter> vcf;            // --vcf: opened at once -- an unwritable path fails here
+    std::unique_ptr<ExcludeTable> exclude;     // --exclude
+    std::unique_ptr<VcfWriter> sites_vcf;      // --sites-vcf, --sites: likewise opened and parsed here
+    SiteTable site_table;
+    int32_t sites_window = 0;
+    int32_t ci_window = 0;       // --ci: without a finite cutoff the run ends here
+    unsigned io_threads = 0;     // decode threads of the host producer
+    std::vector<bdx_lib> libs;
+    std::vector<int> devices;    // BDX_GPUS
+    bool sharded = false;        // ONE whole-genome run with the chromosomes spread over several GPUs
+};
+
+// CPUs this process can use: hardware threads, capped by the cgroup v2 / v1 CPU quota if one is set
+unsigned usable_cpus();
+
+}  // namespace bdhost

@@ -1087,11 +1087,16 @@ void read_targets(const BamConfig& cfg, std::vector<std::string>& names, std::ve
     lengths = rd.target_lengths();
 }
 
-int region_tid(const BamConfig& cfg, const std::string& chr) {
-    if (cfg.num_bams() == 0) return -1;
-    ColumnReader rd(cfg.bam_files()[0], 1, nullptr);
+int region_tid(const std::vector<std::string>& names, const std::string& chr) {
+    struct Names {
+        const std::vector<std::string>& names;
+        int tid_of(const std::string& name) const {   // (the first of equal names, as tid_of of the readers)
+            const auto f = std::find(names.begin(), names.end(), name);
+            return f == names.end() ? -1 : (int)(f - names.begin());
+        }
+    } header{names};
     int tid = -1, beg = 0, end = 0;
-    return parse_region(rd, chr, tid, beg, end) ? tid : -1;
+    return parse_region(header, chr, tid, beg, end) ? tid : -1;
 }
 
 void produce_merged_by_columns(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, ReadStream& out) {

@@ -70,8 +70,8 @@ size_t produce_sharded_on_device(const BamConfig& cfg, const ExcludeTable* ex, i
 void release_device_decoders();
 // reference sequences of the first BAM of the configuration (names and lengths from its header; io/BamMerger.cpp:78)
 void read_targets(const BamConfig& cfg, std::vector<std::string>& names, std::vector<uint32_t>& lengths);
-// the reference sequence an "-o" argument selects in the first BAM's header, as the producer parses it (-1: none)
-int region_tid(const BamConfig& cfg, const std::string& chr);
+// the reference sequence an "-o" argument selects among the first BAM's sequence names, as the producer parses it (-1: none)
+int region_tid(const std::vector<std::string>& names, const std::string& chr);
 void produce(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, ReadStream& out);
 // BamMerger's order worked out from the files' (tid, pos, flag) columns alone: entry i of the merged stream is record src_index[i] of
 // file src_file[i] (what the device path hands to bdx_merge_decoded).  emitted_last (two files): the file that emitted the stream's last

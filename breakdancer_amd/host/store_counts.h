@@ -1,0 +1,43 @@
+// --vcf / --sites / --ci: the counts over the records a finished run holds on the GPU (K8, KS, KI of include/bdx.h), turned into the
+// records VcfWriter prints (vcf.h).
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "bdx.h"
+#include "config.h"
+#include "options.h"
+#include "sites.h"
+#include "vcf.h"
+
+namespace bdhost {
+
+// throws std::runtime_error naming `what`, the status and the context's last error unless rc is BDX_OK (ctx may be null)
+void check(bdx_ctx* ctx, int rc, const char* what);
+
+// The contexts a finished run left behind: the single context, or the ranks of a sharded run (each holds its chromosomes' records).
+struct RunContexts {
+    bdx_ctx* ctx;
+    const std::vector<bdx_dist*>& ranks;
+    const std::vector<int>& rank_of;   // (sharded runs) chromosome -> rank
+    int only_tid;                      // >= 0: the -o chromosome, the only one the run read
+    bool held(int t) const { return t >= 0 && (only_tid < 0 || t == only_tid) && (ranks.empty() || (size_t)t < rank_of.size()); }
+};
+
+// --vcf: one record per printed row (svs[rows[k]] is row k + 1 of the table).  DV: the dominant type's pairs of the sample (library with
+// -a, else BAM file); DR: the normal pairs covering the record's junctions, counted on the GPU.
+std::vector<VcfRecord> vcf_records(const Options& opts, const BamConfig& cfg, const std::vector<bdx_sv>& svs, const std::vector<size_t>& rows,
+                                   const std::vector<int32_t>& li, const std::vector<int32_t>& lp, const RunContexts& rc);
+
+// --sites-vcf: one record per kept line of the --sites table, as the file gave it, DV and DR counted on the GPU.
+std::vector<VcfRecord> site_records(const Options& opts, const BamConfig& cfg, const SiteTable& table, int32_t window, const RunContexts& rc);
+
+// --ci: CIPOS / CIEND of --vcf and --sites-vcf records from the breakpoint bounds their supporting pairs give.
+void fill_ci(const Options& opts, const RunContexts& rc, int32_t window, std::vector<VcfRecord>& out);
+
+// How far a supporting mate can start from a breakpoint it brackets: the ceiling of the largest finite library uppercutoff, the window
+// of --sites and --ci when theirs is not given.
+int32_t cutoff_window(const BamConfig& cfg, const char* option);
+
+}  // namespace bdhost
