@@ -329,6 +329,22 @@ class BreakDancer:
         self._chk(self.lib.bdx_site_breakpoint_bounds(self.h, p(s), len(s), int(window), p(out)), "bdx_site_breakpoint_bounds")
         return out
 
+    def count_interval_reads(self, intervals, by_library=False):
+        """Passing read starts of the last run inside given intervals (bdx_count_interval_reads; the rule is in include/bdx.h):
+        `intervals` is an array of _lib.INTERVAL_DTYPE, or a sequence of (tid, beg, end), 0-based and half-open.  A record counts when it
+        lies on tid, beg <= pos < end and K1 let it pass the filter chain -- a density of read starts, not a per-base pileup.  Returns an
+        (n, nkeys) uint32 array: per library with by_library, else per BAM file."""
+        if isinstance(intervals, np.ndarray) and intervals.dtype == L.INTERVAL_DTYPE:
+            iv = np.ascontiguousarray(intervals)
+        else:
+            rows = [tuple(int(v) for v in r) for r in intervals]
+            iv = np.array(rows, dtype=L.INTERVAL_DTYPE) if rows else np.zeros(0, dtype=L.INTERVAL_DTYPE)
+        nkeys = self.nlibs if by_library else self.nbams
+        out = np.zeros((len(iv), nkeys), np.uint32)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.bdx_count_interval_reads(self.h, p(iv), len(iv), int(bool(by_library)), p(out)), "bdx_count_interval_reads")
+        return out
+
     def set_stage_timing(self, on=True):
         """HIP events between the stages (compact / regions / join timings); costs a few microseconds per event."""
         self._chk(self.lib.bdx_set_stage_timing(self.h, int(on)), "bdx_set_stage_timing")

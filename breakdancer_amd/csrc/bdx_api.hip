@@ -92,7 +92,7 @@ struct bdx_ctx {
                                       // in its high half (FinalizeParams::count_host; read by wait_count)
     uint32_t seq = 0;
     // test / measurement switches (bdx_set_debug): all off by default
-    int dbg_no_stash = 0, dbg_max_chunks = 0, dbg_ins_plain = 0, dbg_gather_walk = 0, dbg_regions_copy = 0, dbg_asm_plain = 0;
+    int dbg_no_stash = 0, dbg_max_chunks = 0, dbg_ins_plain = 0, dbg_gather_walk = 0, dbg_regions_copy = 0, dbg_asm_plain = 0, dbg_depth_plain = 0;
     uint32_t lb_seq = 0;              // launches of look-back scans so far: every launch stamps its words with its own number (bdx_scan.h)
     float k1_ms_last = 0;
     bool k1_timed = false;
@@ -195,6 +195,7 @@ struct bdx_ctx {
 
     // ---- bdx_count_junction_pairs, bdx_count_site_pairs, bdx_site_breakpoint_bounds (run_query) ----
     size_t cls_n = (size_t)-1;        // reads the class bytes in b_cls describe (set by a completed pass 1; -1: none)
+    DevBuf b_qtab;                    // bdx_count_interval_reads' table of one call (scratch: rebuilt by every call)
     DevBuf b_qin, b_qout;             // a call's uploads (queries or sites, and behind them KI's table of the libraries' U) and its results.
                                       // One pair serves the three: every call ends with hipStreamSynchronize, so none can see another's data
     // ---- bdx_set_mark_duplicates ----
@@ -2101,7 +2102,7 @@ int bdx_set_debug(bdx_ctx* c, const char* name, int value) {
     if (!c || !name) return BDX_EINVAL;
     struct { const char* n; int* p; } ints[] = {{"no_stash", &c->dbg_no_stash}, {"max_chunks", &c->dbg_max_chunks}, {"spec_test", &c->spec_test},
                                                  {"big_walk", &c->big_walk_mode}, {"ins_plain", &c->dbg_ins_plain}, {"regions_copy", &c->dbg_regions_copy},
-                                                 {"asm_plain", &c->dbg_asm_plain}, {"gather_walk", &c->dbg_gather_walk}};
+                                                 {"asm_plain", &c->dbg_asm_plain}, {"gather_walk", &c->dbg_gather_walk}, {"depth_plain", &c->dbg_depth_plain}};
     for (auto& e : ints)
         if (!strcmp(name, e.n)) { *e.p = value; return BDX_OK; }
     if (!strcmp(name, "bucketed_join")) { c->bucketed_join = value != 0; return BDX_OK; }
@@ -2162,9 +2163,9 @@ int bdx_classify(const bdx_opts* opts, const bdx_lib* libs, int nlibs, const bdx
     return bdx_get_read_class(c, cls_out, b->n);
 }
 
-// ---- queries over the resident store: K8, KS, KI (kq_queries.hip) ----
+// ---- queries over the resident store: K8, KS, KI (kq_queries.hip) and KR (kr_depth.hip) ----
 
-// What the three calls check first, in this order: a context, no sizing pass in flight, a run that classified the store.  *none: n == 0, nothing to do.
+// What the calls check first, in this order: a context, no sizing pass in flight, a run that classified the store.  *none: n == 0, nothing to do.
 static int check_query_state(bdx_ctx* c, size_t n, bool* none) {
     *none = false;
     if (!c) return BDX_EINVAL;
@@ -2277,6 +2278,32 @@ int bdx_site_breakpoint_bounds(bdx_ctx* c, const bdx_site* sites, size_t n, int3
     });
 }
 
+// Passing read starts inside given intervals (KR, kr_depth.hip): the table of passing records in front of every chunk of the store is built
+// by the call itself, in a scratch buffer, ahead of the queries on the same stream; "depth_plain" answers without one.
+int bdx_count_interval_reads(bdx_ctx* c, const bdx_interval* iv, size_t n, int by_library, uint32_t* counts) {
+    bool none;
+    BDX_TRY(check_query_state(c, n, &none));
+    if (none) return BDX_OK;
+    if (!iv || !counts) return fail(c, BDX_EINVAL, "null array");
+    if (n > ((size_t)1 << 31)) return fail(c, BDX_ELIMIT, "more than 2^31 intervals in one call");
+    for (size_t i = 0; i < n; ++i)
+        if (iv[i].tid < 0 || iv[i].beg < 0 || iv[i].end < iv[i].beg)
+            return fail(c, BDX_EINVAL, "interval " + std::to_string(i) + ": tid < 0, beg < 0 or end < beg");
+    const int nkeys = by_library ? c->nlibs : c->nbams;
+    const uint32_t nchunks = (uint32_t)((c->n + BDX_DEPTH_CHUNK - 1) / BDX_DEPTH_CHUNK);
+    const bool table = !c->dbg_depth_plain && nchunks;
+    if (table) {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, c->b_qtab.ensure((size_t)nkeys * ((size_t)nchunks + 1) * 4));
+    }
+    return run_query(c, {{iv, n * sizeof(bdx_interval)}}, counts, n * (size_t)nkeys * 4, [&](const char* in, void* results, hipStream_t s) {
+        const KrParams p{store_view(c), key_column(c, by_library, nkeys), (const KrInterval*)in, (uint32_t)n, nkeys, nchunks,
+                         table ? c->b_qtab.as<uint32_t>() : nullptr, (uint32_t*)results};
+        launch_kr_table(p, s);
+        launch_kr_query(p, s);
+    });
+}
+
 int bdx_set_process_option(const char* name, int value) {
     if (!name) return BDX_EINVAL;
     if (!strcmp(name, "pin_malloc")) { PinBuf::registered_switch().store(value == 0); return BDX_OK; }
@@ -2286,7 +2313,7 @@ int bdx_set_process_option(const char* name, int value) {
 int bdx_warm_up(int device) {
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
     warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k9(nullptr);
-    warm_kx(nullptr); warm_kq(nullptr);
+    warm_kx(nullptr); warm_kq(nullptr); warm_kr(nullptr);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? BDX_OK : BDX_EHIP;
 }
 

@@ -243,6 +243,21 @@ struct KiParams {
     KiBounds* out;                      // [nq]
 };
 
+// KR (kr_depth.hip): passing read starts inside given intervals, per interval and key (bdx_count_interval_reads)
+struct KrInterval {                     // = bdx_interval (include/bdx.h)
+    int32_t tid, beg, end;              // 0-based, half-open
+};
+struct KrParams {
+    StoreView st;
+    const uint8_t* key;                 // library or source-file column; read only when nkeys > 1
+    const KrInterval* iv;
+    uint32_t nq;
+    int nkeys;                          // 1..255
+    uint32_t nchunks;                   // chunks of BDX_DEPTH_CHUNK records the store is cut into (the last one partial)
+    uint32_t* table;                    // [nkeys][nchunks + 1]: passing records of the key in front of each chunk; null: every interval is walked
+    uint32_t* counts;                   // [nq][nkeys]
+};
+
 // KD (kd_markdup.hip): duplicate marking over the resident store (bdx_set_mark_duplicates, bdx_mark_duplicates)
 constexpr int kDupT = 64;               // neighbours a record looks at each way; runs of more records go through the table
 struct KdCounts {
@@ -277,6 +292,8 @@ void launch_kd_apply(const KdParams& p, uint16_t* flag, uint8_t* mask, hipStream
 void launch_k8(const K8Params& p, hipStream_t s);
 void launch_ks(const KsParams& p, hipStream_t s);
 void launch_ki(const KiParams& p, hipStream_t s);
+void launch_kr_table(const KrParams& p, hipStream_t s);   // chunk counts and their prefix per key: before launch_kr_query when p.table
+void launch_kr_query(const KrParams& p, hipStream_t s);
 void launch_k1(const K1Params& p, int grid, size_t lds, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 size_t k1_lds_bytes(int nlibs, int nbams, int nkeys);
 void launch_finalize(const FinalizeParams& p, hipStream_t s, bool second_level = true);

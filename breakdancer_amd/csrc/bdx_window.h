@@ -36,7 +36,23 @@ __device__ __forceinline__ void wave_window_walk(const int32_t* __restrict__ tid
     }
 }
 
-// ---- per-wave counters per key (K8, KS) -------------------------------------------------------------------------------------------
+// ---- the index walk (KR: kr_depth.hip) ----------------------------------------------------------------------------------------------
+// One wavefront visits the records [L, R) of the store, the range given by index: the lanes stride it 64 records at a time and
+// body(i, in) is called once per lane per step -- i the lane's record index, in whether i < R.  The contract:
+//   * all 64 lanes call it, and the body is called on all 64 lanes of every step, those with in == false too (the bodies hold ballots);
+//   * the indices seen with in == true are exactly [L, R), each once, consecutive from lane 0 on, the first step starting at L;
+//   * (R - L + 63) / 64 steps: none when L >= R;
+//   * the walk itself loads nothing: what the body loads at an index with in == true lies below R.
+template <class Body>
+__device__ __forceinline__ void wave_index_walk(uint64_t L, uint64_t R, Body&& body) {
+    const int lane = lane_id();
+    for (uint64_t base = L; base < R; base += 64) {
+        const uint64_t i = base + (uint64_t)lane;
+        body(i, i < R);
+    }
+}
+
+// ---- per-wave counters per key (K8, KS, KR) -------------------------------------------------------------------------------------------
 // One key: a ballot + popcount per step into a register.  Several (at most 255): the wave's row of [waves][nkeys] words of dynamic LDS
 // and one LDS atomic per hit.  open() and close() hold a workgroup barrier each when nkeys > 1, so every wave of the block calls both,
 // the waves without a query too (`live` false); add() is called on all 64 lanes (it holds the ballot).

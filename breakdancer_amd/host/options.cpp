@@ -67,6 +67,8 @@ void print_usage(const bdx_opts& o) {
     fprintf(stderr, "       --sites-window INT how far from a breakpoint a supporting read may start [the largest library uppercutoff]\n");
     fprintf(stderr, "       --ci           add CIPOS / CIEND (and CIN) to every --vcf / --sites-vcf record: the breakpoint intervals its supporting pairs allow\n");
     fprintf(stderr, "       --ci-window INT    how far from a breakpoint a supporting read of --ci may start [the largest library uppercutoff]\n");
+    fprintf(stderr, "       --depth        add RCI / RCF / RDR to every sample of a --vcf / --sites-vcf record: passing read starts inside the record, in its flanks, and their ratio\n");
+    fprintf(stderr, "       --depth-flank INT  the width of either flank of --depth [%d]\n", Options::kDepthFlankDefault);
     fprintf(stderr, "       --mark-dup     flag duplicate read pairs (same library, positions and strands of both mates) on the GPU; they are ignored like reads with SAM flag 0x400\n");
     fprintf(stderr, "\n");
 }
@@ -77,11 +79,12 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
     // (the reference's letters parse exactly as with getopt; the long options are this tool's own)
-    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow };
+    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank };
     static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude},
                                          {"sites", required_argument, nullptr, kSites}, {"sites-vcf", required_argument, nullptr, kSitesVcf},
                                          {"sites-window", required_argument, nullptr, kSitesWindow}, {"mark-dup", no_argument, nullptr, kMarkDup},
                                          {"ci", no_argument, nullptr, kCi}, {"ci-window", required_argument, nullptr, kCiWindow},
+                                         {"depth", no_argument, nullptr, kDepth}, {"depth-flank", required_argument, nullptr, kDepthFlank},
                                          {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
@@ -107,6 +110,20 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
         }
         if (c == kCi) {
             ci = true;
+            continue;
+        }
+        if (c == kDepth) {
+            depth = true;
+            continue;
+        }
+        if (c == kDepthFlank) {
+            char* end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < 1 || v > (1L << 30)) {
+                fprintf(stderr, "--depth-flank takes an integer from 1 to 2^30, not '%s'.\n", optarg);
+                exit(1);
+            }
+            depth_flank = (int)v;
             continue;
         }
         if (c == kSitesWindow || c == kCiWindow) {
@@ -142,6 +159,10 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     }
     if ((ci && vcf.empty() && sites_vcf.empty()) || (!ci && ci_window >= 0)) {
         fprintf(stderr, "--ci needs --vcf FILE or --sites-vcf FILE to write to (and --ci-window goes with --ci).\n");
+        exit(1);
+    }
+    if ((depth && vcf.empty() && sites_vcf.empty()) || (!depth && depth_flank >= 0)) {
+        fprintf(stderr, "--depth needs --vcf FILE or --sites-vcf FILE to write to (and --depth-flank goes with --depth).\n");
         exit(1);
     }
     o.chr_restricted = chr.empty() ? 0 : 1;

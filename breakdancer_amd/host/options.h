@@ -1,6 +1,6 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
 // (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf, --exclude, --sites / --sites-vcf /
-// --sites-window, --mark-dup and --ci / --ci-window.
+// --sites-window, --mark-dup, --ci / --ci-window and --depth / --depth-flank.
 #pragma once
 #include <string>
 #include <vector>
@@ -24,6 +24,10 @@ struct Options {
     int sites_window = -1;       // --sites-window: how far from a breakpoint a supporting read may start (-1: from the libraries' cutoffs)
     bool ci = false;             // --ci: CIPOS / CIEND / CIN of every --vcf / --sites-vcf record from its supporting pairs (bdx_site_breakpoint_bounds)
     int ci_window = -1;          // --ci-window: how far from a breakpoint such a pair's read may start (-1: from the libraries' cutoffs)
+    bool depth = false;          // --depth: RCI / RCF / RDR of every --vcf / --sites-vcf record: passing read starts inside and beside it (bdx_count_interval_reads)
+    int depth_flank = -1;        // --depth-flank: the width of either flank (-1: kDepthFlankDefault)
+    static constexpr int kDepthFlankDefault = 1000;
+    int flank() const { return depth_flank > 0 ? depth_flank : kDepthFlankDefault; }
     bdx_opts o;                  // numeric options in the C-ABI layout
     std::vector<std::string> orig_argv;
     int device = 0;              // env BDX_DEVICE

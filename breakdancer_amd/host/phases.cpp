@@ -299,6 +299,18 @@ Genotypes count_on_store(const Inputs& in, const Env& env, const Session& s, con
             fprintf(stderr, "[bdx timing] --ci: breakpoint bounds of %zu records (window %d, %zu with supporting pairs) %.4f s\n",
                     gt.vcf_rows.size() + gt.site_rows.size(), in.ci_window, with, secs(tv, now()));
     }
+    if (opts.depth) {
+        const auto tv = now();
+        const size_t ns = sample_names(opts, in.cfg).size();
+        size_t with = 0;
+        for (auto* rows : {&gt.vcf_rows, &gt.site_rows}) {
+            fill_depth(opts, rc, opts.flank(), in.header.lengths(), ns, *rows);
+            for (auto const& r : *rows) with += r.has_depth;
+        }
+        if (env.timing)
+            fprintf(stderr, "[bdx timing] --depth: read starts inside and beside %zu records (flank %d, %zu with both ends on one sequence) %.4f s\n",
+                    gt.vcf_rows.size() + gt.site_rows.size(), opts.flank(), with, secs(tv, now()));
+    }
     return gt;
 }
 
@@ -359,10 +371,12 @@ void write_vcfs(const Inputs& in, Genotypes& gt) {
     const std::vector<std::string> samples = sample_names(opts, in.cfg);
     const VcfCi ci_info{in.ci_window};
     const VcfCi* ci = opts.ci ? &ci_info : nullptr;
-    if (in.vcf) in.vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.vcf_rows), opts.exclude, nullptr, opts.mark_dup, ci);
+    const VcfDepth depth_info{opts.flank()};
+    const VcfDepth* depth = opts.depth ? &depth_info : nullptr;
+    if (in.vcf) in.vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.vcf_rows), opts.exclude, nullptr, opts.mark_dup, ci, depth);
     if (in.sites_vcf) {
         const VcfSites info{opts.sites, in.sites_window};
-        in.sites_vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.site_rows), opts.exclude, &info, opts.mark_dup, ci);
+        in.sites_vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.site_rows), opts.exclude, &info, opts.mark_dup, ci, depth);
     }
 }
 

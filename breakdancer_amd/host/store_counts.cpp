@@ -190,6 +190,36 @@ void fill_ci(const Options& opts, const RunContexts& rc, int32_t window, std::ve
     }
 }
 
+// Every record with both ends on one sequence the run read and pos1 != pos2 gives three intervals of read starts -- its inside and its two
+// flanks (vcf.h depth_spans), clamped to the sequence -- and all of them go to the GPU in one call (KR, bdx_count_interval_reads; a sharded
+// run's on the rank that holds the sequence).  RCI is the inside's count per sample, RCF the two flanks' together.
+void fill_depth(const Options& opts, const RunContexts& rc, int32_t flank, const std::vector<uint32_t>& lengths, size_t ns, std::vector<VcfRecord>& out) {
+    const bool by_lib = opts.o.cn_lib != 0;
+    std::vector<bdx_interval> q;
+    std::vector<int32_t> q_tid;
+    std::vector<size_t> q_row;
+    for (size_t k = 0; k < out.size(); ++k) {
+        VcfRecord& r = out[k];
+        if (r.chr1 != r.chr2 || r.pos1 == r.pos2 || !rc.held(r.chr1) || (size_t)r.chr1 >= lengths.size()) continue;
+        r.has_depth = true;
+        r.spans = depth_spans(r.pos1, r.pos2, flank, std::min<int64_t>(lengths[r.chr1], 2147483646));
+        r.rci.assign(ns, 0); r.rcf.assign(ns, 0);
+        const DepthSpans& s = r.spans;
+        for (const bdx_interval& iv : {bdx_interval{r.chr1, (int32_t)s.in_beg, (int32_t)s.in_end}, bdx_interval{r.chr1, (int32_t)s.left_beg, (int32_t)s.left_end},
+                                       bdx_interval{r.chr1, (int32_t)s.right_beg, (int32_t)s.right_end}}) {
+            q.push_back(iv); q_tid.push_back(r.chr1); q_row.push_back(k);
+        }
+    }
+    std::vector<uint32_t> counts;
+    count_on_ranks(rc, q_tid, ns, "bdx_count_interval_reads", counts, [&](bdx_ctx* c, const std::vector<size_t>& m, uint32_t* cnt) {
+        std::vector<bdx_interval> mine(m.size());
+        for (size_t j = 0; j < m.size(); ++j) mine[j] = q[m[j]];
+        return bdx_count_interval_reads(c, mine.data(), m.size(), by_lib ? 1 : 0, cnt);
+    });
+    for (size_t i = 0; i < q.size(); ++i)
+        for (size_t k = 0; k < ns; ++k) (i % 3 == 0 ? out[q_row[i]].rci : out[q_row[i]].rcf)[k] += counts[i * ns + k];
+}
+
 int32_t cutoff_window(const BamConfig& cfg, const char* option) {
     double ub = -1.0;
     for (size_t i = 0; i < cfg.num_libs(); ++i) {

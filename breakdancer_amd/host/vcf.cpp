@@ -32,6 +32,24 @@ CiOffsets ci_offsets(int64_t lo, int64_t hi, int64_t P) {
     return c;
 }
 
+DepthSpans depth_spans(int64_t pos1, int64_t pos2, int64_t flank, int64_t contig_len) {
+    const int64_t len = std::max<int64_t>(contig_len, 0);
+    auto clamp = [&](int64_t p) { return std::min(std::max<int64_t>(p, 1), len + 1); };   // (1-based; len + 1: the end of a half-open bound)
+    const int64_t lo = std::min(pos1, pos2), hi = std::max(pos1, pos2);
+    DepthSpans s;
+    s.in_beg = clamp(lo) - 1; s.in_end = clamp(hi) - 1;
+    s.left_beg = clamp(lo - flank) - 1; s.left_end = s.in_beg;
+    s.right_beg = s.in_end; s.right_end = clamp(hi + flank) - 1;
+    return s;
+}
+
+std::string depth_ratio(int64_t rci, int64_t rcf, int64_t len_in, int64_t len_flank) {
+    if (rci < 0 || rcf <= 0 || len_in <= 0 || len_flank <= 0) return ".";
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.3f", (double)rci * (double)len_flank / ((double)len_in * (double)rcf));
+    return buf;
+}
+
 VcfWriter::VcfWriter(const std::string& path) : path_(path) {
     f_ = fopen(path.c_str(), "w");
     if (!f_) throw std::runtime_error("unable to open VCF output file '" + path + "'");
@@ -43,7 +61,7 @@ VcfWriter::~VcfWriter() {
 
 void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                       const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude,
-                      const VcfSites* sites, bool mark_dup, const VcfCi* ci) {
+                      const VcfSites* sites, bool mark_dup, const VcfCi* ci, const VcfDepth* depth) {
     if (!f_) throw std::runtime_error("VCF output file '" + path_ + "' is already closed");
     FILE* f = f_;
     fprintf(f, "##fileformat=VCFv4.2\n##source=breakdancer-max-mi355x\n##command=");
@@ -53,6 +71,7 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
     if (sites) fprintf(f, "##sites=%s\n##sites_window=%d\n", sites->file.c_str(), sites->window);
     if (mark_dup) fprintf(f, "##mark_dup=1\n");
     if (ci) fprintf(f, "##ci_window=%d\n", ci->window);
+    if (depth) fprintf(f, "##depth_flank=%d\n", depth->flank);
     for (size_t t = 0; t < contigs.size(); ++t)
         fprintf(f, "##contig=<ID=%s,length=%u>\n", contigs[t].c_str(), t < lengths.size() ? lengths[t] : 0u);
     fputs("##FILTER=<ID=PASS,Description=\"All filters passed\">\n"
@@ -88,6 +107,11 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
     fputs(sites ? "##FORMAT=<ID=DV,Number=1,Type=Integer,Description=\"Read pairs of the site's type with one mate starting within sites_window of each breakpoint\">\n"
                 : "##FORMAT=<ID=DV,Number=1,Type=Integer,Description=\"Read pairs supporting the call (the dominant type's pairs)\">\n",
           f);
+    if (depth)
+        fputs("##FORMAT=<ID=RCI,Number=1,Type=Integer,Description=\"Read starts inside the record: reads that passed the caller's filters and start at min(POS, POS2) <= p < max(POS, POS2) (a read-start count, not a per-base depth)\">\n"
+              "##FORMAT=<ID=RCF,Number=1,Type=Integer,Description=\"Read starts in the record's two flanks of depth_flank bases each, clamped to the contig\">\n"
+              "##FORMAT=<ID=RDR,Number=1,Type=Float,Description=\"Read-start density inside the record over that of its flanks: (RCI / inside length) / (RCF / flank length)\">\n",
+              f);
     fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT");
     for (auto const& s : samples) fprintf(f, "\t%s", s.c_str());
     fprintf(f, "\n");
@@ -111,7 +135,7 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
             fprintf(f, ";CIPOS=%lld,%lld;%s=%lld,%lld;CIN=%u", (long long)c1.a, (long long)c1.b, r.chr2 == r.chr1 && r.pos2 >= r.pos1 ? "CIEND" : "CIPOS2",
                     (long long)c2.a, (long long)c2.b, r.ci_n);
         }
-        fputs("\tGT:GQ:PL:DR:DV", f);
+        fputs(depth ? "\tGT:GQ:PL:DR:DV:RCI:RCF:RDR" : "\tGT:GQ:PL:DR:DV", f);
         for (size_t k = 0; k < samples.size(); ++k) {
             const int64_t dr = k < r.dr.size() ? r.dr[k] : -1, dv = k < r.dv.size() ? r.dv[k] : 0;
             const Genotype g = call_genotype(dr, dv);
@@ -124,6 +148,11 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
             else fprintf(f, "%lld:", (long long)dr);
             if (dv < 0) fputs(".", f);
             else fprintf(f, "%lld", (long long)dv);
+            if (depth) {
+                const int64_t rci = r.has_depth && k < r.rci.size() ? r.rci[k] : -1, rcf = r.has_depth && k < r.rcf.size() ? r.rcf[k] : -1;
+                if (rci < 0 || rcf < 0) fputs(":.:.:.", f);
+                else fprintf(f, ":%lld:%lld:%s", (long long)rci, (long long)rcf, depth_ratio(rci, rcf, r.spans.len_in(), r.spans.len_flank()).c_str());
+            }
         }
         fputs("\n", f);
     }

@@ -5,6 +5,8 @@
 // no score, orientation counts, NREADS or BDAF, and its ID is SITE<k>.
 // --ci: either output's records gain CIPOS / CIEND (CIPOS2 where the record prints no END) and CIN from the breakpoint bounds their
 // supporting pairs give (bdx_site_breakpoint_bounds).
+// --depth: either output's samples gain RCI / RCF / RDR behind DV: the passing read starts inside the record and in its two flanks,
+// counted on the GPU (bdx_count_interval_reads), and the ratio of the two densities.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -32,6 +34,20 @@ struct CiOffsets {
 };
 CiOffsets ci_offsets(int64_t lo, int64_t hi, int64_t P);
 
+// --depth: the three intervals of read starts a record with both ends on one sequence is counted over, 0-based and half-open as
+// bdx_count_interval_reads takes them.  With lo = min(pos1, pos2), hi = max(pos1, pos2) (1-based, as printed) and flank F the record's
+// inside is the starts P = pos + 1 with lo <= P < hi, its flanks lo - F <= P < lo and hi <= P < hi + F; every bound is clamped to
+// [1, contig_len + 1] first, so that no interval leaves the sequence (and none is negative when a position lies outside it).
+struct DepthSpans {
+    int64_t in_beg = 0, in_end = 0, left_beg = 0, left_end = 0, right_beg = 0, right_end = 0;
+    int64_t len_in() const { return in_end - in_beg; }
+    int64_t len_flank() const { return (left_end - left_beg) + (right_end - right_beg); }
+};
+DepthSpans depth_spans(int64_t pos1, int64_t pos2, int64_t flank, int64_t contig_len);
+// RDR as printed: (rci / len_in) / (rcf / len_flank) with three decimals (printf's rounding of the double rci * len_flank / (len_in * rcf));
+// "." when rcf == 0 or either length is 0 (or below), or a count is unknown (< 0)
+std::string depth_ratio(int64_t rci, int64_t rcf, int64_t len_in, int64_t len_flank);
+
 // one printed row of the table
 struct VcfRecord {
     size_t row = 0;                  // 1-based row number among the printed rows (ID = BDX<row>)
@@ -44,6 +60,9 @@ struct VcfRecord {
     bool has_ci = false;             // --ci: the record's supporting pairs bound its breakpoints (none do: no CI keys) ...
     uint32_t ci_n = 0;               // ... their number (CIN) ...
     int ci_lo1 = 0, ci_hi1 = 0, ci_lo2 = 0, ci_hi2 = 0;   // ... and the bounds at (chr1, pos1) and at (chr2, pos2), as the record prints its ends
+    bool has_depth = false;          // --depth: both ends on one sequence the run read, pos1 != pos2 (otherwise '.' in all three fields) ...
+    DepthSpans spans;                // ... what was counted over ...
+    std::vector<int64_t> rci, rcf;   // ... and the counts per sample: inside, and in the two flanks together
 };
 
 // what makes an output a --sites-vcf one: the records are given sites (ID SITE<row>, QUAL '.', INFO without ORI1 / ORI2 / NREADS / BDAF)
@@ -57,6 +76,11 @@ struct VcfCi {
     int32_t window = 0;              // the window the supporting pairs were looked for with
 };
 
+// what makes an output a --depth one: the ##depth_flank= line, the RCI / RCF / RDR header lines and the three FORMAT fields
+struct VcfDepth {
+    int32_t flank = 0;               // the width of either flank
+};
+
 class VcfWriter {
 public:
     // opens (truncates) the file at once: an unwritable path fails before any work is done
@@ -67,10 +91,11 @@ public:
     // header + records, sorted by (chr1, pos1) with ties in row order; `contigs` are the reference sequences (names are also the
     // records' CHROM / CHR2 values); exclude: the --exclude file of the run ("": none) for the ##exclude= line; sites: non-null for a
     // --sites-vcf output; mark_dup: the run marked duplicates (--mark-dup), for the ##mark_dup=1 line; ci: non-null for a run
-    // with --ci; the file is closed afterwards
+    // with --ci, depth: for a run with --depth; the file is closed afterwards
     void write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude = "",
-               const VcfSites* sites = nullptr, bool mark_dup = false, const VcfCi* ci = nullptr);
+               const VcfSites* sites = nullptr, bool mark_dup = false, const VcfCi* ci = nullptr,
+               const VcfDepth* depth = nullptr);
 
 private:
     std::string path_;

@@ -260,6 +260,7 @@ int bdx_set_host_walk(bdx_ctx* ctx, int on);
  *   "regions_copy"   1: the host copies the region table before its share of the walk (small tables), 2: never (large ones)
  *   "asm_plain"      the walk's candidate assembly merges its parts by the three-way merge (the route of one library, or of many)
  *   "gather_walk"    sharded runs: 1 = rank 0 walks the gathered components on its device, 2 = on its host (by their number otherwise)
+ *   "depth_plain"    bdx_count_interval_reads walks every interval record by record, without the chunk table (the route of an interval that holds no whole chunk)
  * BDX_EINVAL for any other name. */
 int bdx_set_debug(bdx_ctx* ctx, const char* name, int value);
 int bdx_get_walk_split(const bdx_ctx* ctx, uint32_t* n_sv_device, uint32_t* n_sv_host, uint32_t* n_groups_host);
@@ -547,6 +548,28 @@ int bdx_count_site_pairs(bdx_ctx* ctx, const bdx_site* sites, size_t n, int32_t 
  * same context (bdx_trim_results included). */
 typedef struct bdx_site_bounds { uint32_t n; int32_t lo1, hi1, lo2, hi2; } bdx_site_bounds;   /* 20 bytes */
 int bdx_site_breakpoint_bounds(bdx_ctx* ctx, const bdx_site* sites, size_t n, int32_t window, bdx_site_bounds* out);
+
+/* Passing read starts inside given intervals: no counterpart in the reference, which says nothing about read depth (the input of --depth's
+ * RCI / RCF / RDR).  The rule, written down here once:
+ *   Record i of the resident store counts for interval (tid, [beg, end)) -- 0-based, half-open, as in --exclude's mask -- when
+ *   tid[i] == tid, beg <= pos[i] < end and cls[i] & BDX_CLS_PASS: the records K1 let pass the pass-2 filter chain, the reads the caller
+ *   itself works with (paired, both ends mapped, not a duplicate -- SAM flag 0x400, bdx_set_mark_duplicates' marks included --, mapping
+ *   quality above the library's minimum, |isize| <= -m or CTX), normal and anomalous alike.
+ * Only what the record itself carries is looked at (as in the other rules): qlen is not used -- it is not resident for pinned pushes -- and
+ * no CIGAR.  The count is a density of READ STARTS, NOT a per-base pileup of the kind samtools depth or mosdepth give: a read that starts
+ * in front of beg and reaches into the interval does not count, one that starts inside and reaches out of it does.
+ * counts[i * nkeys + k]: the records of key k (library with by_library, else BAM file; nkeys = nlibs / nbams; a key index out of range
+ * counts as 0; a context with one key never reads the key column) that count for interval i.  beg == end counts 0; a tid the context
+ * holds no reads of, or beyond the header, counts 0.  After bdx_run, or on a rank's context (bdx_dist_chromosome) after bdx_dist_run: that
+ * rank's chromosomes.  With opts.transchr_rearrange (-t) no same-chromosome read passes; the call is legal and says so.
+ * The cost per interval does not grow with the interval: every call first counts the passing records per chunk of BDX_DEPTH_CHUNK
+ * consecutive records and key (KR, csrc/kr_depth.hip; about a byte per record and key column), and an interval takes its whole chunks from
+ * that table and walks only its two edges.  Nothing is kept between calls.
+ * BDX_ESTATE before a run has classified the reads the context holds (or while a sizing pass is in flight); n == 0 is BDX_OK even with
+ * null pointers; BDX_EINVAL for a null array with n > 0, tid < 0, beg < 0 or end < beg; BDX_ELIMIT above 2^31 intervals.  Not beside
+ * another call on the same context (bdx_trim_results included). */
+#define BDX_DEPTH_CHUNK 2048   /* an implementation constant, published for the tests (they place intervals on and around chunk boundaries) */
+int bdx_count_interval_reads(bdx_ctx* ctx, const bdx_interval* iv, size_t n, int by_library, uint32_t* counts); /* [n][nkeys] */
 
 /* Duplicate marking: no counterpart in the reference, which only ignores reads that already carry SAM flag 0x400
  * (io/IlluminaPEReadClassifier.cpp:66-74; K1 restates that).  The rule, written down here once:
