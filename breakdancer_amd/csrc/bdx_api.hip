@@ -56,6 +56,10 @@ struct StageBufs {
 };
 
 constexpr int kNumStages = 12;
+// bdx_ctx::stage_ms, in the order bdx_get_timings hands them out (include/bdx.h)
+enum StageMs { kMsClassify, kMsCompact, kMsCut, kMsJoinAssemble, kMsGroupsWait, kMsHostWalk, kMsFinish, kMsRun, kMsTableWait, kMsMerge, kMsScores };
+// the words of bdx_ctx::h_flags: a kernel (or a stream write) sets each to the run's sequence number once what it names is complete
+enum ReadyWord { kPass1Ready, kGroupsReady, kTableReady, kRegionsReady };
 constexpr int kK1MaxGrid = 8192;  // measured best on MI355X (tools/k1_probe.hip; again at the end of round 2: 2048 74.6 us, 4096 70.9,
                                   // 8192 69.9, 12288 72.5, 16384 73.4): 256 CUs x 32 workgroups queued, 4 independent waves each
 constexpr uint32_t kK1EventPeriod = 4;  // K1 is bracketed by HIP events on every n-th run (an event pair idles the GPU ~10 us)
@@ -87,7 +91,7 @@ struct bdx_ctx {
     PinBuf h_p1, h_cnt, h_counts, h_terms;
     PinBuf h_hs_rec, h_hs_aux, h_hs_lists, h_printed;
     StageBufs sb;                     // K2 .. K6: what a sizing pass grows
-    PinBuf h_flags;                   // [0] pass 1 ready, [1] host's groups ready, [2] final table ready, [3] region table ready (= run sequence number)
+    PinBuf h_flags;                   // one word per ReadyWord: pass 1, the host's groups, the final table, the region table (= run sequence number)
     PinBuf h_count;                   // [kMaxChunks] 64-bit words: finalize_kernel's chunk totals of anomalous reads, each stamped with the run sequence number
                                       // in its high half (FinalizeParams::count_host; read by wait_count)
     uint32_t seq = 0;
@@ -322,11 +326,22 @@ struct StageDims {
     int walks_big() const { return big_walk >= 0 ? big_walk : (k6_regions() > 500000u ? 1 : 0); }
 };
 
+// a join of `n` entries on this context takes the direct table (else the partitioned LDS join)
+bool joins_direct(const bdx_ctx* c, uint32_t n) { return c->force_direct_join || (!c->bucketed_join && n <= kDirectJoinMax); }
+
+// Capacity of the later stages for `count` anomalous reads: the count plus the headroom an enqueue-ahead run of the same input asks for,
+// so that its buffers are the buffers of the run before it.  Not clamped: each caller has its own answer beyond kMaxAnomalous.
+uint64_t with_headroom(uint64_t count) { return count + count / 8 + 1024; }
+// The prior a first run of `n_reads` reads sizes the later stages by, where it takes one (plan_sizing has the measurements), and
+// what bdx_reserve and the BAM decoder's sizing thread therefore allocate: if they disagreed, the first run would reallocate inside the
+// timed step.  divisor: 32; BDX_SPEC_TEST's 4096 makes it too small on purpose.
+uint64_t prior_anomalous(uint64_t n_reads, uint32_t divisor = 32) { return n_reads / divisor + 4096; }
+
 // ... of a context that takes `na` anomalous reads of its own through all four stages (bdx_run, the sizing passes)
 StageDims stage_dims(const bdx_ctx* c, uint32_t na) {
     StageDims d;
     d.na = na; d.nkeys = c->nkeys; d.nlibs = c->nlibs; d.use_check = c->use_check;
-    d.k2_clears_join = c->force_direct_join || (!c->bucketed_join && na <= kDirectJoinMax);
+    d.k2_clears_join = joins_direct(c, na);
     d.groups_in_hbm = c->groups_in_hbm; d.table_in_hbm = c->table_in_hbm; d.k6_cap = c->k6_cap;
     d.big_walk = c->big_walk_mode >= 0 ? c->big_walk_mode : (c->last_big_groups >= 0 ? (c->last_big_groups > 2000 ? 1 : 0) : -1);
     d.join_n = d.join_own = na; d.join_slots = d.k2_clears_join ? direct_join_slots(na) : 0;
@@ -334,7 +349,6 @@ StageDims stage_dims(const bdx_ctx* c, uint32_t na) {
 }
 
 int pass1_prepare(bdx_ctx* c, uint32_t tiles_cap);
-int presize_stages(bdx_ctx* c, const StageDims& dm);
 int presize_stages_here(bdx_ctx* c, const StageDims& dm);
 int pass1_classify(bdx_ctx* c, uint32_t upto, bool timed);
 
@@ -500,10 +514,10 @@ int bdx_reserve(bdx_ctx* c, size_t n_reads) {
     HIPCHK(c, hipSetDevice(c->device));
     BDX_TRY(alloc_reads(c, n_reads));
     // The buffers of the stages behind pass 1 as well, for the prior a first run sizes them by (1/32 of the reads anomalous, see
-    // bdx_run): ~60 device and pinned allocations, 3-4 ms at 15 M reads, most of it page pinning -- here they happen while the
+    // plan_sizing): ~60 device and pinned allocations, 3-4 ms at 15 M reads, most of it page pinning -- here they happen while the
     // caller still decodes or copies, not inside its first bdx_run.  Small inputs size theirs exactly, when they run.
     if (n_reads >= (1u << 20) && !c->ran) {
-        const uint64_t prior = (uint64_t)n_reads / 32 + 4096;
+        const uint64_t prior = prior_anomalous(n_reads);
         if (prior <= kMaxAnomalous) return presize_stages_here(c, stage_dims(c, (uint32_t)prior));
     }
     return BDX_OK;
@@ -609,9 +623,9 @@ namespace {
 
 // Spin on a word of pinned host memory that a kernel sets once its results are written there.  Much shorter than the
 // wake-up of a blocking stream / event wait; falls back to the caller's blocking wait if the word does not show up.
-bool wait_flag(const bdx_ctx* c, int idx, uint32_t value) {
+bool wait_flag(const bdx_ctx* c, ReadyWord w, uint32_t value) {
     if (!c->poll || !c->h_flags.p) return false;
-    volatile uint32_t* f = (volatile uint32_t*)c->h_flags.p + idx;
+    volatile uint32_t* f = (volatile uint32_t*)c->h_flags.p + w;
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spin = 0;; ++spin) {
         if (*f == value) { std::atomic_thread_fence(std::memory_order_acquire); return true; }
@@ -643,8 +657,18 @@ bool wait_count(const bdx_ctx* c, uint64_t* n_anom) {
 
 // behind a poll that timed out and a stream that has drained: was the word written at all?  (A kernel that was never launched -- a
 // launch that failed, a stage that returned early -- leaves zeros where its results should be; they must not pass for an empty input.)
-bool flag_arrived(const bdx_ctx* c, int idx) {
-    return !c->poll || !c->h_flags.p || ((volatile uint32_t*)c->h_flags.p)[idx] == c->seq;
+// always_set: the word is written whether or not the host polls for it, so it is looked at without polling too (the pass-1 record's)
+bool flag_arrived(const bdx_ctx* c, ReadyWord w, bool always_set = false) {
+    return (!c->poll && !always_set) || !c->h_flags.p || ((volatile uint32_t*)c->h_flags.p)[w] == c->seq;
+}
+
+// The wait for a ready word of this run: poll; failing that, wait for `ev` (polling off, and the caller recorded one in the word's place:
+// signal_ready) or else for the stream; then the word must be there, or the run fails with `missing`.
+int await_ready(bdx_ctx* c, ReadyWord w, hipEvent_t ev, const char* missing, bool always_set = false) {
+    if (wait_flag(c, w, c->seq)) return BDX_OK;
+    hipStream_t s = c->stream;
+    if (!c->poll && ev) HIPCHK(c, hipEventSynchronize(ev)); else HIPCHK(c, hipStreamSynchronize(s));
+    return flag_arrived(c, w, always_set) ? BDX_OK : fail(c, BDX_EINTERNAL, missing);
 }
 
 // Tell the host that everything enqueued so far has completed: a stream write-value into a polled pinned word, or (polling
@@ -653,9 +677,9 @@ bool flag_arrived(const bdx_ctx* c, int idx) {
 // orders them).  On this runtime the write-value command is itself a one-thread kernel (__amd_rocclr_streamOpsWrite in
 // the kernel trace, ~4 us on the stream), so where another kernel follows anyway its first thread sets the word instead
 // (K6Arrays::flag_regions / flag_groups); the command remains for the end of the run.
-int signal_ready(bdx_ctx* c, int idx, hipEvent_t ev) {
+int signal_ready(bdx_ctx* c, ReadyWord w, hipEvent_t ev) {
     if (c->poll) {
-        if (hipStreamWriteValue32(c->stream, c->h_flags.as<uint32_t>() + idx, c->seq, 0) == hipSuccess) return BDX_OK;
+        if (hipStreamWriteValue32(c->stream, c->h_flags.as<uint32_t>() + w, c->seq, 0) == hipSuccess) return BDX_OK;
         (void)hipGetLastError();
         c->poll = false;  // not supported here: blocking waits from now on
     }
@@ -669,11 +693,6 @@ int signal_ready(bdx_ctx* c, int idx, hipEvent_t ev) {
 float ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
     return std::chrono::duration<float, std::milli>(b - a).count();
 }
-
-// K1 + finalize: class bytes, per-tile tables, *local* pass-1 counters
-// post_count: finalize_kernel also posts the chunk totals of anomalous reads to h_count (the caller reads them with wait_count)
-int do_pass1(bdx_ctx* c, uint32_t na_cap = 0, bool wait = true, bool defer_second = false, bool post_count = false);
-int wait_pass1(bdx_ctx* c);
 
 
 // The segment table of the name keys (read lengths, second hashes) that the caller's pinned batches still hold (bdx_push), in b_seg:
@@ -832,11 +851,57 @@ int pass1_classify(bdx_ctx* c, uint32_t upto, bool timed) {
     return BDX_OK;
 }
 
-int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second, bool post_count) {
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
+// K1 + finalize: class bytes, per-tile tables, *local* pass-1 counters.  Enqueues only: wait_pass1 receives the record.
+struct Pass1Launch {
+    uint32_t na_cap = 0;        // enqueue-ahead: the count the later stages behind this launch were sized for (finalize2_kernel neutralises them beyond it)
+    bool defer_second = false;  // ... and K2's launch takes the second level of the finalisation along
+    bool post_count = false;    // finalize_kernel also posts the chunk totals of anomalous reads to h_count (the caller reads them with wait_count)
+};
+// the finalisation behind K1 over c->ntiles tiles: a new run sequence number, the scan of the tile totals, the record and the counters
+int pass1_finalize(bdx_ctx* c, const Pass1Launch& opt) {
     const int nlibs = c->nlibs, nbams = c->nbams, nkeys = c->nkeys;
     const int ncols = 2 + nkeys, ncnt = nlibs * kNumFlags + nlibs + nbams;
+    const uint32_t ntiles = c->ntiles;
+    FinalizeParams fp{};
+    fp.ntiles = ntiles; fp.tstride = c->tstride; fp.nblk = 0;
+    fp.nfold = std::max<uint32_t>(1, std::min<uint32_t>(64, (ntiles + 1023) / 1024));
+    HIPCHK(c, c->b_fold.ensure((size_t)nbams * fp.nfold * sizeof(MonoRec)));
+    fp.fold_part = c->b_fold.as<MonoRec>();
+    fp.nlibs = nlibs; fp.nbams = nbams; fp.nkeys = nkeys; fp.ncols = ncols; fp.ncnt = ncnt; fp.w0 = c->w0;
+    fp.tile_tot = c->b_tile_tot.as<uint32_t>(); fp.tile_pre = c->b_tile_pre.as<uint32_t>(); fp.tile_mono = c->b_tile_mono.as<MonoRec>();
+    {   // the tile-total columns are scanned in chunks of whole rounds of a workgroup (4096 super tiles), at most kMaxChunks of them
+        const uint32_t nsuper = (ntiles + kK2TilesPerWave - 1) / kK2TilesPerWave;
+        const uint32_t round = 4096;
+        const uint32_t rounds = std::max<uint32_t>(1, (nsuper + round - 1) / round);
+        // (tests: chunks of several rounds at small sizes)
+        const uint32_t max_chunks = c->dbg_max_chunks > 0 ? (uint32_t)std::min(c->dbg_max_chunks, (int)kMaxChunks) : (uint32_t)kMaxChunks;
+        fp.chunk_super = round * ((rounds + max_chunks - 1) / max_chunks);
+        fp.nchunk = std::max<uint32_t>(1, (nsuper + fp.chunk_super - 1) / fp.chunk_super);
+        HIPCHK(c, c->b_chunk_tot.ensure((size_t)ncols * kMaxChunks * 8));
+        fp.chunk_tot = c->b_chunk_tot.as<uint32_t>();
+        fp.chunk_base = fp.chunk_tot + (size_t)ncols * kMaxChunks;
+    }
+    fp.blk_cnt = c->b_blk_cnt.as<uint32_t>(); fp.cnt = c->b_cnt.as<uint32_t>(); fp.p1 = c->b_p1.as<Pass1>();
+    HIPCHK(c, c->b_kdens.ensure(64 * 4));
+    fp.libs = c->b_libs.as<DevLib>(); fp.cn_lib = c->opts.cn_lib; fp.key_density = c->b_kdens.as<float>();
+    fp.cnt_host = c->h_cnt.as<uint32_t>(); fp.p1_host = c->h_p1.as<Pass1>();  // written by the kernel: no copy commands
+    memset(c->h_p1.p, 0, sizeof(Pass1));
+    HIPCHK(c, c->h_flags.ensure(64));
+    ++c->seq;
+    fp.flag_host = c->h_flags.as<uint32_t>(); fp.flag_value = c->seq;
+    fp.na_cap = opt.na_cap;
+    fp.count_host = opt.post_count && c->poll ? c->h_count.as<uint64_t>() : nullptr; fp.count_stamp = c->seq;
+    c->count_chunks = fp.count_host ? fp.nchunk : 0;
+    // enqueue-ahead: K2 follows without a host decision in between, so its launch takes the one-workgroup second level along
+    c->fp_deferred = fp;
+    c->finalize2_deferred = opt.defer_second;
+    launch_finalize(fp, c->stream, !opt.defer_second);
+    return BDX_OK;
+}
+
+int do_pass1(bdx_ctx* c, const Pass1Launch& opt) {
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
     if (c->n >= ((size_t)1 << 32)) return fail(c, BDX_ELIMIT, "more than 2^32 - 1 reads in one context (read indices and the prefix counters are 32-bit)");
     const uint32_t ntiles = (uint32_t)((c->n + kTile - 1) / kTile);
     c->ntiles = ntiles;
@@ -863,69 +928,29 @@ int do_pass1(bdx_ctx* c, uint32_t na_cap, bool wait, bool defer_second, bool pos
     if (c->mark_dup && c->k1_done == 0) {   // classification starts from tile 0: the marks are in the flag column before K1 reads it
         BDX_TRY(mark_duplicates(c));
     }
-    const uint32_t tstride = c->tstride;
     const bool time_k1 = (c->stage_timing || c->seq % kK1EventPeriod == 0) && c->k1_done == 0 && ntiles > 0;
-    {
-        BDX_TRY(pass1_classify(c, ntiles, time_k1));
-    }
-    FinalizeParams fp{};
-    fp.ntiles = ntiles; fp.tstride = tstride; fp.nblk = 0;
-    fp.nfold = std::max<uint32_t>(1, std::min<uint32_t>(64, (ntiles + 1023) / 1024));
-    HIPCHK(c, c->b_fold.ensure((size_t)nbams * fp.nfold * sizeof(MonoRec)));
-    fp.fold_part = c->b_fold.as<MonoRec>();
-    fp.nlibs = nlibs; fp.nbams = nbams; fp.nkeys = nkeys; fp.ncols = ncols; fp.ncnt = ncnt; fp.w0 = c->w0;
-    fp.tile_tot = c->b_tile_tot.as<uint32_t>(); fp.tile_pre = c->b_tile_pre.as<uint32_t>(); fp.tile_mono = c->b_tile_mono.as<MonoRec>();
-    {   // the tile-total columns are scanned in chunks of whole rounds of a workgroup (4096 super tiles), at most kMaxChunks of them
-        const uint32_t nsuper = (ntiles + kK2TilesPerWave - 1) / kK2TilesPerWave;
-        const uint32_t round = 4096;
-        const uint32_t rounds = std::max<uint32_t>(1, (nsuper + round - 1) / round);
-        // (tests: chunks of several rounds at small sizes)
-        const uint32_t max_chunks = c->dbg_max_chunks > 0 ? (uint32_t)std::min(c->dbg_max_chunks, (int)kMaxChunks) : (uint32_t)kMaxChunks;
-        fp.chunk_super = round * ((rounds + max_chunks - 1) / max_chunks);
-        fp.nchunk = std::max<uint32_t>(1, (nsuper + fp.chunk_super - 1) / fp.chunk_super);
-        HIPCHK(c, c->b_chunk_tot.ensure((size_t)ncols * kMaxChunks * 8));
-        fp.chunk_tot = c->b_chunk_tot.as<uint32_t>();
-        fp.chunk_base = fp.chunk_tot + (size_t)ncols * kMaxChunks;
-    }
-    fp.blk_cnt = c->b_blk_cnt.as<uint32_t>(); fp.cnt = c->b_cnt.as<uint32_t>(); fp.p1 = c->b_p1.as<Pass1>();
-    HIPCHK(c, c->b_kdens.ensure(64 * 4));
-    fp.libs = c->b_libs.as<DevLib>(); fp.cn_lib = c->opts.cn_lib; fp.key_density = c->b_kdens.as<float>();
-    fp.cnt_host = c->h_cnt.as<uint32_t>(); fp.p1_host = c->h_p1.as<Pass1>();  // written by the kernel: no copy commands
-    memset(c->h_p1.p, 0, sizeof(Pass1));
-    HIPCHK(c, c->h_flags.ensure(64));
-    ++c->seq;
-    fp.flag_host = c->h_flags.as<uint32_t>(); fp.flag_value = c->seq;
-    fp.na_cap = na_cap;
-    fp.count_host = post_count && c->poll ? c->h_count.as<uint64_t>() : nullptr; fp.count_stamp = c->seq;
-    c->count_chunks = fp.count_host ? fp.nchunk : 0;
-    // enqueue-ahead: K2 follows without a host decision in between, so its launch takes the one-workgroup second level along
-    c->fp_deferred = fp;
-    c->finalize2_deferred = defer_second;
-    launch_finalize(fp, s, !defer_second);
+    BDX_TRY(pass1_classify(c, ntiles, time_k1));
+    BDX_TRY(pass1_finalize(c, opt));
     c->k1_timed = time_k1;
-    return wait ? wait_pass1(c) : BDX_OK;
+    return BDX_OK;
 }
 
 // the pass-1 record and counters, written into pinned memory by finalize2_kernel
 int wait_pass1(bdx_ctx* c) {
     const int ncnt = c->nlibs * kNumFlags + c->nlibs + c->nbams;
-    if (!wait_flag(c, 0, c->seq)) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        // (the word is set by the kernel that writes the record, whether or not the host polls for it: a stream that has drained without it
-        // means that kernel was never launched -- an empty pass-1 record must not pass for a BAM without reads)
-        if (c->h_flags.p && *((volatile uint32_t*)c->h_flags.p) != c->seq) return fail(c, BDX_EINTERNAL, "the pass-1 record did not arrive: its kernel was not launched");
-    }
+    // (always_set: the word is set by the kernel that writes the record, whether or not the host polls for it: a stream that has drained
+    // without it means that kernel was never launched -- an empty pass-1 record must not pass for a BAM without reads)
+    BDX_TRY(await_ready(c, kPass1Ready, nullptr, "the pass-1 record did not arrive: its kernel was not launched", /*always_set=*/true));
     c->p1 = *c->h_p1.as<Pass1>();
     c->cnt_local.assign(c->h_cnt.as<uint32_t>(), c->h_cnt.as<uint32_t>() + ncnt);
     if (c->k1_timed) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->k1_ms_last = ms;
     }
-    c->stage_ms[0] = c->k1_ms_last;  // the latest measured launch
+    c->stage_ms[kMsClassify] = c->k1_ms_last;  // the latest measured launch
     if (c->p1.n_anom > kMaxAnomalous) return fail(c, BDX_ELIMIT, "more than 2^31 anomalous reads in one context");
-    // capacity of the later stages: the count plus the headroom an enqueue-ahead run of the same input will ask for, so that
-    // its buffers are these buffers (an enqueue-ahead run has set its guess already)
-    if (!c->na_alloc && c->p1.n_anom) c->na_alloc = (uint32_t)std::min<uint64_t>((uint64_t)c->p1.n_anom + c->p1.n_anom / 8 + 1024, kMaxAnomalous);
+    // capacity of the later stages (an enqueue-ahead run has set its guess already)
+    if (!c->na_alloc && c->p1.n_anom) c->na_alloc = (uint32_t)std::min<uint64_t>(with_headroom(c->p1.n_anom), kMaxAnomalous);
     c->cls_n = c->n;
     return BDX_OK;
 }
@@ -1190,7 +1215,7 @@ int do_cut(bdx_ctx* c, const uint32_t* tid_tail, RegionDst dst) {
         if (for_k6) {  // the device-side SV assembly reads the region table back: a copy in HBM
             k3.r_rec_dev = b.b_r_rec.as<RegionRec>(); k3.r_pk_dev = b.b_r_pk.as<uint32_t>(); k3.out_deg = b.b_out_deg.as<uint32_t>();
             // with the direct join right behind K3, that kernel forwards the table to the host
-            k3.host_copy_later = (!c->bucketed_join && na <= kDirectJoinMax) ? 1 : 0;
+            k3.host_copy_later = joins_direct(c, na) ? 1 : 0;
             memset(b.h_counts0.p, 0, sizeof(StageCounts));
             k3.counts_host = b.h_counts0.as<StageCounts>();
         } else {
@@ -1200,10 +1225,10 @@ int do_cut(bdx_ctx* c, const uint32_t* tid_tail, RegionDst dst) {
         HIPCHK(c, next_lb_stamp(c, &k3.lb_stamp));
         k3.counts = c->b_counts.as<StageCounts>();
         // single-context runs that take the direct join let that kernel do k3_region_of_kernel's work
-        c->region_of_fused = for_k6 && !c->bucketed_join && na <= kDirectJoinMax;
+        c->region_of_fused = for_k6 && joins_direct(c, na);
         launch_k3(k3, c->cp, c->b_p1.as<Pass1>(), na, c->opts.min_len, c->opts.seq_coverage_lim, c->nkeys, tid_tail, !c->region_of_fused, s);
         if (for_k6 && !k3.host_copy_later) {  // the region table is in pinned memory
-            BDX_TRY(signal_ready(c, 3, c->ev_regions));
+            BDX_TRY(signal_ready(c, kRegionsReady, c->ev_regions));
         }
     }
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[4], s));
@@ -1216,7 +1241,7 @@ int do_join_local(bdx_ctx* c, uint32_t n, const Entries& en, const uint32_t* n_p
     K4Arrays& k4 = c->k4;
     k4 = K4Arrays{};
     if (!n) return BDX_OK;
-    const bool direct = c->force_direct_join || (!c->bucketed_join && n <= kDirectJoinMax);
+    const bool direct = joins_direct(c, n);
     StageDims dm = stage_dims(c, c->na_alloc);
     dm.join_n = n;
     dm.join_own = en.n_local ? std::min<uint32_t>(n, std::max<uint32_t>(c->na_alloc, 1u)) : n;
@@ -1289,21 +1314,10 @@ void decode_groups(bdx_ctx* c, const GroupRec* gr, uint32_t ng, uint32_t ph) {
     }
 }
 
-// K6 on the context's own regions: pair groups per region, SV assembly of the components that need no traversal, everything else listed
-// for the host walk; then (do_k6_table) the dense results and K5 for the device-assembled SVs.  k6_prepare lays out K6's arrays and run
-// constants and launches nothing; the callers then launch what they mean (k6_pairs, k6_then_walk below).
-// rounds: min-label propagation rounds (0: kK6LabelRounds, or kK6LabelRoundsBig with the general walk)
-int k6_prepare(bdx_ctx* c, bool force_host, int rounds) {
-    hipStream_t s = c->stream;
-    K6Arrays& a = c->k6;
-    a = K6Arrays{};
-    const StageDims dm = stage_dims(c, c->na_alloc);
-    const uint32_t na = dm.k6_regions();
-    if (!na) return BDX_OK;
-    BDX_TRY(size_k6(c->sb, dm, s, &c->err));
+// K6's arrays for `na` regions, in the buffers size_k6 has sized: capacities, the carved-up scratch, inputs from K3 / K4, outputs
+void k6_layout(const bdx_ctx* c, K6Arrays& a, const StageDims& dm, uint32_t na) {
     const StageBufs& b = c->sb;
     const K6Caps k = k6_caps(dm);
-    const int nkeys = c->nkeys, nlibs = c->nlibs;
     const size_t cap = na, p2 = k.p2, svc = k.sv, nsort = k.nsort;
     a.sv_cap = k.sv; a.term_cap = k.term; a.cn_cap = k.cn; a.lib_stride = k.lib_stride;
     a.old_key = b.b_ins.as<uint64_t>(); a.hs_key_dev = a.old_key + p2;
@@ -1342,6 +1356,21 @@ int k6_prepare(bdx_ctx* c, bool force_host, int rounds) {
     a.t_lambda = b.b_t_lambda.as<double>(); a.t_k = b.b_t_k.as<int32_t>();
     a.g_rec = c->k4.g_rec; a.g_cap = c->k4.g_cap;
     a.lb_state = b.b_ws6.as<unsigned long long>();
+    a.counts_host2 = b.h_counts2.as<StageCounts>();
+}
+
+// K6 on the context's own regions: pair groups per region, SV assembly of the components that need no traversal, everything else listed
+// for the host walk; then (do_k6_table) the dense results and K5 for the device-assembled SVs.  k6_prepare lays out K6's arrays and run
+// constants and launches nothing; the callers then launch what they mean (k6_pairs, k6_then_walk below).
+// rounds: min-label propagation rounds (0: kK6LabelRounds, or kK6LabelRoundsBig with the general walk)
+int k6_prepare(bdx_ctx* c, bool force_host, int rounds) {
+    K6Arrays& a = c->k6;
+    a = K6Arrays{};
+    const StageDims dm = stage_dims(c, c->na_alloc);
+    const uint32_t na = dm.k6_regions();
+    if (!na) return BDX_OK;
+    BDX_TRY(size_k6(c->sb, dm, c->stream, &c->err));
+    k6_layout(c, a, dm, na);
     HIPCHK(c, next_lb_stamp(c, &a.lb_stamp));
     a.counts = c->b_counts.as<StageCounts>();
     // run constants: the flag histogram is the device's own reduced counter table (a single-context run adopts its own
@@ -1350,11 +1379,10 @@ int k6_prepare(bdx_ctx* c, bool force_host, int rounds) {
     a.key_density = c->b_kdens.as<float>();
     a.lib_mean = c->b_lib_mean.as<float>();
     a.counts_host = c->h_counts.as<StageCounts>();
-    a.counts_host2 = b.h_counts2.as<StageCounts>();
     memset(c->h_counts.p, 0, sizeof(StageCounts));
-    memset(b.h_counts2.p, 0, sizeof(StageCounts));
+    memset(a.counts_host2, 0, sizeof(StageCounts));
     a.p1 = c->b_p1.as<Pass1>();
-    a.nlibs = nlibs; a.nkeys = nkeys; a.min_read_pair = c->opts.min_read_pair; a.chr_restricted = c->opts.chr_restricted;
+    a.nlibs = c->nlibs; a.nkeys = c->nkeys; a.min_read_pair = c->opts.min_read_pair; a.chr_restricted = c->opts.chr_restricted;
     a.period = std::max(1, c->opts.buffer_size + 1);
     a.force_host = force_host ? 1 : 0;
     a.ins_plain = c->dbg_ins_plain;
@@ -1363,8 +1391,8 @@ int k6_prepare(bdx_ctx* c, bool force_host, int rounds) {
     a.propagation_rounds = rounds ? rounds : (a.big_walk ? kK6LabelRoundsBig : kK6LabelRounds);
     if (c->poll) {  // ready words set by the kernels themselves (first thread of k6_pairs_kernel / first wave of k6_walk_kernel)
         a.flag_value = c->seq;
-        a.flag_groups = c->h_flags.as<uint32_t>() + 1;
-        if (c->k3.host_copy_later) a.flag_regions = c->h_flags.as<uint32_t>() + 3;
+        a.flag_groups = c->h_flags.as<uint32_t>() + kGroupsReady;
+        if (c->k3.host_copy_later) a.flag_regions = c->h_flags.as<uint32_t>() + kRegionsReady;
         a.mirror_in_walk = force_host ? 0 : 1;  // (k6_walk_kernel follows k6_emit_kernel unless everything goes to the host)
     }
     return BDX_OK;
@@ -1380,7 +1408,7 @@ int k6_then_walk(bdx_ctx* c, void (*first)(const K6Arrays&, uint32_t, hipStream_
     const K6Arrays& a = c->k6;
     if (!a.cap) return BDX_OK;
     first(a, a.cap, c->stream);
-    if (!c->poll) BDX_TRY(signal_ready(c, 1, c->ev_groups));
+    if (!c->poll) BDX_TRY(signal_ready(c, kGroupsReady, c->ev_groups));
     launch_k6_walk(a, a.cap, c->stream);
     return BDX_OK;
 }
@@ -1411,14 +1439,8 @@ int presize_stages_here(bdx_ctx* c, const StageDims& dm) {
     return r;
 }
 
-// second half of K6, enqueued once the host walk has produced its share: the host's SV candidates (pinned memory) are
-// interleaved with the device's by the compaction, K5 scores every term, the score kernel finishes every candidate --
-// the final table is assembled by the device in pinned host memory, in the reference's output order.
-int do_k6_table(bdx_ctx* c) {
-    hipStream_t s = c->stream;
-    K6Arrays& a = c->k6;
-    const uint32_t na = a.cap;
-    if (!na) return BDX_OK;
+// the host walk's SV candidates with their order keys and lists, in pinned memory for the table stage (a.hs_*)
+int stage_host_svs(bdx_ctx* c, K6Arrays& a) {
     const WalkResult& H = c->walk;
     const uint32_t nh = (uint32_t)H.svs.size(), nt = (uint32_t)H.terms.size(), nc = (uint32_t)H.cn_key.size();
     a.nh = nh;
@@ -1451,6 +1473,18 @@ int do_k6_table(bdx_ctx* c) {
         a.hs_rec = c->h_hs_rec.as<SvOut>(); a.hs_key = hkey; a.hs_cnt = hcnt;
         a.hs_lambda = lam; a.hs_lib_index = li; a.hs_lib_pairs = lp; a.hs_cn_key = ck; a.hs_cn_value = cv;
     }
+    return BDX_OK;
+}
+
+// second half of K6, enqueued once the host walk has produced its share: the host's SV candidates (pinned memory) are
+// interleaved with the device's by the compaction, K5 scores every term, the score kernel finishes every candidate --
+// the final table is assembled by the device in pinned host memory, in the reference's output order.
+int do_k6_table(bdx_ctx* c) {
+    hipStream_t s = c->stream;
+    K6Arrays& a = c->k6;
+    const uint32_t na = a.cap;
+    if (!na) return BDX_OK;
+    BDX_TRY(stage_host_svs(c, a));
     // (K5 runs inside the table kernel.  The terms' log tails go to the host for Fisher's combination only -- BreakDancer.cpp:71-81 uses the
     // host's exp / log --; otherwise they are 8 bytes per term over PCIe that nobody reads)
     a.ltail_host = c->table_in_hbm ? c->sb.b_ltail_out.as<double>() : (c->opts.fisher ? c->sb.h_ltail_dev.as<double>() : nullptr);
@@ -1461,12 +1495,12 @@ int do_k6_table(bdx_ctx* c) {
     // The word the host polls for the end of the run is set by a one-thread kernel behind the table kernel (a kernel boundary
     // orders it behind that kernel's stores to host memory).  A stream write-value command does the same as a one-thread kernel of
     // the runtime's own, but starts 5 us after the kernel before it has ended; back-to-back launches follow each other at once.
-    if (c->poll) { a.flag_done = c->h_flags.as<uint32_t>() + 2; a.flag_value = c->seq; }
+    if (c->poll) { a.flag_done = c->h_flags.as<uint32_t>() + kTableReady; a.flag_value = c->seq; }
     a.wire_rows = c->table_in_hbm ? 0 : 1;   // (a table that stays in HBM for rank 0's merge keeps its full rows)
     c->rows_packed = a.wire_rows != 0;
     launch_k6_table(a, na, std::log(10), c->opts.score_threshold, c->opts.fisher ? 0 : 1, s);
     if (!a.flag_done) {  // (without polling: finish_table waits for the stream)
-        BDX_TRY(signal_ready(c, 2, nullptr));
+        BDX_TRY(signal_ready(c, kTableReady, nullptr));
     }
     return BDX_OK;
 }
@@ -1516,12 +1550,8 @@ int materialize(bdx_ctx* c) {
 
 // end of a single-context run: wait for the device's table
 int finish_table(bdx_ctx* c) {
-    hipStream_t s = c->stream;
     const auto tf0 = std::chrono::steady_clock::now();
-    if (!wait_flag(c, 2, c->seq)) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (!flag_arrived(c, 2)) return fail(c, BDX_EINTERNAL, "the SV table did not arrive: its kernels were not launched");
-    }
+    BDX_TRY(await_ready(c, kTableReady, nullptr, "the SV table did not arrive: its kernels were not launched"));
     const auto tf1 = std::chrono::steady_clock::now();
     static_assert(sizeof(HostSv) == sizeof(SvOut) && offsetof(HostSv, grp_mask) == offsetof(SvOut, grp_mask) &&
                       offsetof(HostSv, start) == offsetof(SvOut, start), "SV record layout");
@@ -1546,9 +1576,9 @@ int finish_table(bdx_ctx* c) {
         finish_scores(c->opts, c->log_tail.data(), c->walk.svs.data(), c->walk.svs.size(), &c->n_printed);
     }
     const auto tf2 = std::chrono::steady_clock::now();
-    c->stage_ms[8] = ms_between(tf0, tf1);
-    c->stage_ms[9] = ms_between(tf1, tf2);
-    c->stage_ms[10] = 0;
+    c->stage_ms[kMsTableWait] = ms_between(tf0, tf1);
+    c->stage_ms[kMsMerge] = ms_between(tf1, tf2);
+    c->stage_ms[kMsScores] = 0;
     c->ran = true;
     return BDX_OK;
 }
@@ -1566,6 +1596,9 @@ int host_walk(bdx_ctx* c, int32_t last_maxq, bool any_anomalous) {
     return BDX_OK;
 }
 
+// h_terms for `nt` terms: [nt] lambda (double) | [nt] k (int32) | the log tails K5 writes back, on the next 8-byte boundary
+double* terms_log_tail(const bdx_ctx* c, size_t nt) { return (double*)((char*)c->h_terms.p + ((nt * 12 + 7) & ~(size_t)7)); }
+
 // K5 for the host walk's terms (the read-level replay: the whole walk is the host's)
 int score_host_terms(bdx_ctx* c) {
     hipStream_t s = c->stream;
@@ -1576,9 +1609,8 @@ int score_host_terms(bdx_ctx* c) {
         HIPCHK(c, c->h_terms.ensure((size_t)nt * 20 + 16));
         double* hl = c->h_terms.as<double>();
         int32_t* hk = (int32_t*)(hl + nt);
-        double* ho = (double*)((char*)c->h_terms.p + (((size_t)nt * 12 + 7) & ~(size_t)7));
         for (uint32_t i = 0; i < nt; ++i) { hl[i] = c->walk.terms[i].lambda; hk[i] = c->walk.terms[i].k; }
-        launch_k5(hl, hk, ho, nt, s);
+        launch_k5(hl, hk, terms_log_tail(c, nt), nt, s);
     }
     return BDX_OK;
 }
@@ -1589,7 +1621,7 @@ int finish_host_walk(bdx_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());
     const uint32_t nt = (uint32_t)c->walk.terms.size();
-    const double* host_tail = nt ? (const double*)((char*)c->h_terms.p + (((size_t)nt * 12 + 7) & ~(size_t)7)) : nullptr;
+    const double* host_tail = nt ? terms_log_tail(c, nt) : nullptr;
     c->log_tail.assign(host_tail, host_tail + nt);
     finish_scores(c->opts, c->log_tail.data(), c->walk.svs.data(), c->walk.svs.size(), &c->n_printed);
     c->n_sv_host = c->n_sv_total = (uint32_t)c->walk.svs.size();
@@ -1711,53 +1743,54 @@ int replay_reads(bdx_ctx* c, uint32_t ph) {
     return BDX_OK;
 }
 
-}  // namespace
+// ---- bdx_run's phases: the sizing plan, one function per route, the hand-over to the host, the end of the run ----
 
-extern "C" {
+// The very first anomalous read "breaks" an empty accumulator (start = end = -1, no reads).  With a negative
+// -s that empty candidate passes process_breakpoint's test (0 > min_len, coverage 0) and the reference
+// registers a read-less region 0 (BreakDancer.cpp:216-231, 244-252); every real region id shifts by one.
+bool phantom_region_opt(const bdx_ctx* c) { return 0 > c->opts.min_len && 0.0f < (float)c->opts.seq_coverage_lim; }
+// shifted region ids and a non-positive -r are left to the host walk entirely
+bool host_walks_all(const bdx_ctx* c) { return c->host_walk_only || phantom_region_opt(c) || c->opts.min_read_pair < 1; }
 
-int bdx_run(bdx_ctx* c) {
-    if (!c) return BDX_EINVAL;
-    NOT_WHILE_SIZING(c);
-    const auto t_begin = std::chrono::steady_clock::now();
-    hipStream_t s = c->stream;
-    // The very first anomalous read "breaks" an empty accumulator (start = end = -1, no reads).  With a negative
-    // -s that empty candidate passes process_breakpoint's test (0 > min_len, coverage 0) and the reference
-    // registers a read-less region 0 (BreakDancer.cpp:216-231, 244-252); every real region id shifts by one.
-    const bool ph_opt = 0 > c->opts.min_len && 0.0f < (float)c->opts.seq_coverage_lim;
-    // shifted region ids and a non-positive -r are left to the host walk entirely
-    const bool force_host = c->host_walk_only || ph_opt || c->opts.min_read_pair < 1;
-    // K2 .. K6 (first half) for c->na_alloc anomalous reads
-    auto enqueue_middle = [&]() -> int {
-        BDX_TRY(do_compact(c));
-        BDX_TRY(do_cut(c, nullptr, RegionDst::HostAndHbm));
-        if (!c->na_alloc) return BDX_OK;
-        // the region table is final after K3: the host takes its copy while the device joins the mates
-        Entries en{};
-        en.key = c->cp.key; en.check = c->cp.check; en.region = c->k3.region_of; en.meta = c->cp.meta; en.isize = c->cp.isize;
-        if (c->region_of_fused) {
-            en.cand = c->k3.cand; en.c_rid = c->k3.c_rid; en.region_out = c->k3.region_of;
-            en.k6_scratch = c->k3.out_deg; en.scratch_cap = c->k3.cap;
-            // (the join kernel forwards the region table to pinned host memory.  A kernel of its own on the copy stream, beside the join, was
-            // measured in round 6: 1.525 against 1.530 ms at a genome share -- the join does not wait for those 5.7 MB; profiles/r06_genome_ab.txt)
-            if (c->k3.host_copy_later) {
-                en.r_rec_dev = c->k3.r_rec_dev; en.r_pk_dev = c->k3.r_pk_dev; en.r_rec_host = c->k3.r_rec; en.r_pk_host = c->k3.r_pk;
-                en.counts = c->b_counts.as<StageCounts>(); en.nkeys2 = 2 * c->nkeys;
-            }
+// K2 .. K6 (first half) for c->na_alloc anomalous reads
+int enqueue_middle(bdx_ctx* c, bool force_host) {
+    BDX_TRY(do_compact(c));
+    BDX_TRY(do_cut(c, nullptr, RegionDst::HostAndHbm));
+    if (!c->na_alloc) return BDX_OK;
+    // the region table is final after K3: the host takes its copy while the device joins the mates
+    Entries en{};
+    en.key = c->cp.key; en.check = c->cp.check; en.region = c->k3.region_of; en.meta = c->cp.meta; en.isize = c->cp.isize;
+    if (c->region_of_fused) {
+        en.cand = c->k3.cand; en.c_rid = c->k3.c_rid; en.region_out = c->k3.region_of;
+        en.k6_scratch = c->k3.out_deg; en.scratch_cap = c->k3.cap;
+        // (the join kernel forwards the region table to pinned host memory.  A kernel of its own on the copy stream, beside the join, was
+        // measured in round 6: 1.525 against 1.530 ms at a genome share -- the join does not wait for those 5.7 MB; profiles/r06_genome_ab.txt)
+        if (c->k3.host_copy_later) {
+            en.r_rec_dev = c->k3.r_rec_dev; en.r_pk_dev = c->k3.r_pk_dev; en.r_rec_host = c->k3.r_rec; en.r_pk_host = c->k3.r_pk;
+            en.counts = c->b_counts.as<StageCounts>(); en.nkeys2 = 2 * c->nkeys;
         }
-        BDX_TRY(do_join_local(c, c->na_alloc, en, &c->b_p1.as<Pass1>()->n_anom));
-        if (c->k3.host_copy_later && !c->poll) {  // the join kernel has forwarded the region table to pinned memory
-            BDX_TRY(signal_ready(c, 3, c->ev_regions));  // (polling: the next kernel, k6_pairs_kernel, sets the ready word itself)
-        }
-        BDX_TRY(k6_prepare(c, force_host, 0));
-        return k6_then_walk(c, launch_k6_groups);
-    };
-    // enqueue-ahead when this context has just run an input of the same size
-    uint32_t guess = 0;
-    const bool restored = !c->ov_cnt.empty();  // (restored statistics are adopted between pass 1 and the rest: nothing ahead)
-    if (!restored && c->speculate == 2 && c->ran && c->last_n == c->n && c->last_na) {
-        guess = c->spec_test ? std::max(1u, c->last_na / 2) : c->last_na + c->last_na / 8 + 1024;
-        if (guess > kMaxAnomalous) guess = 0;
-    } else if (!restored && c->speculate && c->n >= (1u << 20) && (c->speculate == 1 || c->n < (1u << 25))) {
+    }
+    BDX_TRY(do_join_local(c, c->na_alloc, en, &c->b_p1.as<Pass1>()->n_anom));
+    if (c->k3.host_copy_later && !c->poll) {  // the join kernel has forwarded the region table to pinned memory
+        BDX_TRY(signal_ready(c, kRegionsReady, c->ev_regions));  // (polling: the next kernel, k6_pairs_kernel, sets the ready word itself)
+    }
+    BDX_TRY(k6_prepare(c, force_host, 0));
+    return k6_then_walk(c, launch_k6_groups);
+}
+
+// How a run sizes the stages behind pass 1.  Restored: pass-1 statistics were restored, which are adopted between pass 1 and the rest --
+// nothing ahead.  Ahead: sized by `guess` and enqueued before the pass-1 record is back.  Exact: from the count pass 1 delivers.
+enum class Sizing { Restored, Ahead, Exact };
+struct SizingPlan { Sizing route; uint32_t guess; };
+
+// ... decided from the context's state alone; launches nothing, changes nothing
+SizingPlan plan_sizing(const bdx_ctx* c) {
+    if (!c->ov_cnt.empty()) return {Sizing::Restored, 0};
+    uint64_t guess = 0;
+    if (c->speculate == 2 && c->ran && c->last_n == c->n && c->last_na) {
+        // this context has just run an input of the same size
+        guess = c->spec_test ? std::max(1u, c->last_na / 2) : with_headroom(c->last_na);
+    } else if (c->speculate && c->n >= (1u << 20) && (c->speculate == 1 || c->n < (1u << 25))) {
         // no history: a prior.  Anomalous reads are a few percent of a sorted BAM at most (1 % at configs[1]); 1/32 of the
         // reads covers that with room, costs a few microseconds of oversized grids when it is generous, and one more pass
         // over the (short) later stages when it is not.  Small inputs are not worth it: their whole run is launch latency.
@@ -1767,129 +1800,173 @@ int bdx_run(bdx_ctx* c) {
         // and a prior twice the truth, eighteen times with -t, costs its oversized grids and tables: 1.534 against 1.514 ms, 0.92 against 0.83 with -t.
         // The compaction ALONE ahead under the prior, the rest sized exactly, was built too: 1.656 against 1.612 ms, 0.90 against 0.83 -- the tables K2
         // clears for K3 and K4 are sized by the guess.  profiles/r06_genome_ab.txt)
-        const uint64_t prior = (uint64_t)c->n / (c->spec_test ? 4096 : 32) + 4096;
-        guess = prior > kMaxAnomalous ? 0 : (uint32_t)prior;
+        guess = prior_anomalous(c->n, c->spec_test ? 4096 : 32);
     }
-    int rc;
-    if (restored) {
-        // restored pass-1 statistics (a cache written by an earlier run: ConfigLoader.cpp:19-23): the classifier still runs --
-        // pass 2 needs its class bytes -- but window, densities, lambda and the printed counters come from the cache
-        BDX_TRY(do_pass1(c));
-        BDX_TRY(set_pass1(c, c->ov_cnt.data(), c->ov_covered, window_from(c, c->ov_cnt.data(), c->ov_covered), true));
-        HIPCHK(c, hipMemcpyAsync(c->b_cnt.p, c->ov_cnt.data(), c->ov_cnt.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->b_kdens.p, c->key_density.data(), c->key_density.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        BDX_TRY(enqueue_middle());
-    } else if (guess) {
-        BDX_TRY(do_pass1(c, guess, false, true));
-        c->na_alloc = guess;
-        BDX_TRY(enqueue_middle());
+    if (!guess || guess > kMaxAnomalous) return {Sizing::Exact, 0};
+    return {Sizing::Ahead, (uint32_t)guess};
+}
+
+// the run adopts the statistics of its own pass 1 (the device copy already holds them)
+int adopt_own_pass1(bdx_ctx* c) { return set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false); }
+
+// Restored pass-1 statistics (a cache written by an earlier run: ConfigLoader.cpp:19-23): the classifier still runs --
+// pass 2 needs its class bytes -- but window, densities, lambda and the printed counters come from the cache
+int run_restored(bdx_ctx* c, bool force_host) {
+    hipStream_t s = c->stream;
+    BDX_TRY(do_pass1(c, {}));
+    BDX_TRY(wait_pass1(c));
+    BDX_TRY(set_pass1(c, c->ov_cnt.data(), c->ov_covered, window_from(c, c->ov_cnt.data(), c->ov_covered), true));
+    HIPCHK(c, hipMemcpyAsync(c->b_cnt.p, c->ov_cnt.data(), c->ov_cnt.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->b_kdens.p, c->key_density.data(), c->key_density.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return enqueue_middle(c, force_host);
+}
+
+// Enqueue-ahead: the later stages go out behind pass 1, sized by `guess`, and the record is received behind them
+int run_ahead(bdx_ctx* c, uint32_t guess, bool force_host) {
+    hipStream_t s = c->stream;
+    BDX_TRY(do_pass1(c, {.na_cap = guess, .defer_second = true}));
+    c->na_alloc = guess;
+    BDX_TRY(enqueue_middle(c, force_host));
+    BDX_TRY(wait_pass1(c));
+    BDX_TRY(adopt_own_pass1(c));
+    if (c->p1.n_anom <= guess) return BDX_OK;
+    // more anomalous reads than guessed: the enqueued stages saw none; run them properly
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipMemcpy(&c->b_p1.as<Pass1>()->n_anom, &c->p1.n_anom, 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(c->b_counts.p, 0, sizeof(StageCounts)));
+    ++c->seq;  // fresh ready-words: the ones of the neutralised launches are already set
+    c->na_alloc = c->p1.n_anom;
+    return enqueue_middle(c, force_host);
+}
+
+// Exact sizing: the later stages are sized and launched from the count finalize_kernel posts, while finalize2_kernel still runs;
+// the record and what the host derives from it come behind the launches
+int run_exact(bdx_ctx* c, bool force_host) {
+    hipStream_t s = c->stream;
+    BDX_TRY(do_pass1(c, {.post_count = true}));
+    uint64_t count = 0;
+    if (!wait_count(c, &count)) {  // (polling off, or the words did not arrive in time: the record first)
         BDX_TRY(wait_pass1(c));
-        BDX_TRY(set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false));
-        if (c->p1.n_anom > guess) {  // more anomalous reads than guessed: the enqueued stages saw none; run them properly
-            HIPCHK(c, hipStreamSynchronize(s));
-            HIPCHK(c, hipMemcpy(&c->b_p1.as<Pass1>()->n_anom, &c->p1.n_anom, 4, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemset(c->b_counts.p, 0, sizeof(StageCounts)));
-            ++c->seq;  // fresh ready-words: the ones of the neutralised launches are already set
-            c->na_alloc = c->p1.n_anom;
-            BDX_TRY(enqueue_middle());
-        }
-    } else {
-        // exact sizing: the later stages are sized and launched from the count finalize_kernel posts, while finalize2_kernel still runs;
-        // the record and what the host derives from it come behind the launches
-        BDX_TRY(do_pass1(c, 0, /*wait=*/false, false, /*post_count=*/true));
-        uint64_t count = 0;
-        if (wait_count(c, &count)) {
-            if (count > kMaxAnomalous) {
-                HIPCHK(c, hipStreamSynchronize(s));
-                return fail(c, BDX_ELIMIT, "more than 2^31 anomalous reads in one context");
-            }
-            if (count) c->na_alloc = (uint32_t)std::min<uint64_t>(count + count / 8 + 1024, kMaxAnomalous);
-            BDX_TRY(enqueue_middle());
-            BDX_TRY(wait_pass1(c));
-            if (c->p1.n_anom != count) {
-                HIPCHK(c, hipStreamSynchronize(s));
-                return fail(c, BDX_EINTERNAL, "the count of anomalous reads posted ahead of the pass-1 record differs from the record's");
-            }
-            BDX_TRY(set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false));
-        } else {  // (polling off, or the words did not arrive in time: the record first)
-            BDX_TRY(wait_pass1(c));
-            BDX_TRY(set_pass1(c, c->cnt_local.data(), c->p1.covered_ref_len, c->p1.window, false));
-            BDX_TRY(enqueue_middle());
-        }
+        BDX_TRY(adopt_own_pass1(c));
+        return enqueue_middle(c, force_host);
+    }
+    if (count > kMaxAnomalous) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        return fail(c, BDX_ELIMIT, "more than 2^31 anomalous reads in one context");
+    }
+    if (count) c->na_alloc = (uint32_t)std::min<uint64_t>(with_headroom(count), kMaxAnomalous);
+    BDX_TRY(enqueue_middle(c, force_host));
+    BDX_TRY(wait_pass1(c));
+    if (c->p1.n_anom != count) {
+        HIPCHK(c, hipStreamSynchronize(s));
+        return fail(c, BDX_EINTERNAL, "the count of anomalous reads posted ahead of the pass-1 record differs from the record's");
+    }
+    return adopt_own_pass1(c);
+}
+
+// K1 .. K6 (first half) by the plan's route; what the next run of the same input is sized from
+int enqueue_device_half(bdx_ctx* c, const SizingPlan& plan, bool force_host) {
+    hipStream_t s = c->stream;
+    switch (plan.route) {
+        case Sizing::Restored: BDX_TRY(run_restored(c, force_host)); break;
+        case Sizing::Ahead: BDX_TRY(run_ahead(c, plan.guess, force_host)); break;
+        case Sizing::Exact: BDX_TRY(run_exact(c, force_host)); break;
     }
     c->last_n = c->n;
     c->last_na = c->p1.n_anom;
-    const uint32_t na = c->p1.n_anom;
-    const uint32_t ph = (na && ph_opt) ? 1u : 0u;
     if (c->stage_timing) HIPCHK(c, hipEventRecord(c->ev[5], s));
-    const auto t_h0 = std::chrono::steady_clock::now();
-    auto t_h1 = t_h0;
-    if (na) {
-        if (!wait_flag(c, 3, c->seq)) {
-            if (c->poll) HIPCHK(c, hipStreamSynchronize(s)); else HIPCHK(c, hipEventSynchronize(c->ev_regions));
-            if (!flag_arrived(c, 3)) return fail(c, BDX_EINTERNAL, "the region table did not arrive: its kernels were not launched");
-        }
-        // (the table sits in pinned memory the device has just written: one streaming copy into ordinary memory is much
-        // cheaper than the walk's scattered reads of it)
-        if ((uint64_t)c->sb.h_counts0.as<StageCounts>()->n_regions + ph > kMaxRegions) {   // (region ids are 26-bit fields of the packed group key)
-            HIPCHK(c, hipStreamSynchronize(s));
-            return fail(c, BDX_ELIMIT, "more than 2^26 - 2 accepted regions in one context");
-        }
-        // The host's share of the walk reads the table where the device left it, in pinned memory.  (Until round 6 the table was copied into
-        // ordinary memory first -- "one streaming copy is cheaper than the walk's scattered reads", true when the host walked every component:
-        // 5.7 MB at a genome share, 0.28 ms of this thread between the join kernel's end and the pair groups' arrival 0.14 ms later; the
-        // host's walk of its ~1,200 groups then started late and the device stood idle in front of the table stage.)  A large share
-        // (debug "regions_copy" = 1: always) still gets its copy, once the groups have said how large it is.
-        const uint32_t nr_host = c->sb.h_counts0.as<StageCounts>()->n_regions;
-        // (a small table is copied at once, as ever: its copy fits between the join kernel's end and the groups' arrival -- 32 k regions are 70 us)
-        const bool copy_first = c->dbg_regions_copy == 1 || (c->dbg_regions_copy == 0 && nr_host < kBorrowRegionsMin);
-        if (copy_first) decode_regions(c, c->sb.h_regs.as<RegionRec>(), c->sb.h_pk.as<uint32_t>(), nr_host, ph, false);
-        if (!wait_flag(c, 1, c->seq)) {
-            if (c->poll) HIPCHK(c, hipStreamSynchronize(s)); else HIPCHK(c, hipEventSynchronize(c->ev_groups));
-            if (!flag_arrived(c, 1)) return fail(c, BDX_EINTERNAL, "the pair groups did not arrive: their kernels were not launched");
-        }
-        c->counts = *c->h_counts.as<StageCounts>();
-        if (!copy_first) decode_regions(c, c->sb.h_regs.as<RegionRec>(), c->sb.h_pk.as<uint32_t>(), nr_host, ph,
-                                        c->dbg_regions_copy == 2 || (uint64_t)c->counts.n_groups * 8 < nr_host);   // (borrowed while the walk touches a fraction of the table:
-                                        // a walk of 20 k groups over 15 k regions was 46 us faster on its copy)
-        if (c->counts.irregular) {  // a read name seen more than twice: the pair model does not hold (see bdx_walk_reads.cpp)
-            t_h1 = std::chrono::steady_clock::now();
-            BDX_TRY(replay_reads(c, ph));
-            const auto t_r = std::chrono::steady_clock::now();
-            c->stage_ms[4] = ms_between(t_h0, t_h1); c->stage_ms[5] = ms_between(t_h1, t_r); c->stage_ms[7] = ms_between(t_begin, t_r);
-            return BDX_OK;
-        }
-        if (c->counts.overflow) return fail(c, BDX_EINTERNAL, "group list overflow");
-        decode_groups(c, c->sb.h_groups.as<GroupRec>(), c->counts.n_groups, ph);
-        c->last_big_groups = (int64_t)c->counts.n_groups + c->counts.n_groups_big;  // (the host's share: mostly such components)
+    return BDX_OK;
+}
+
+// The region table and the host's share of the pair groups, as the device completes them: c->reg / c->rpk, c->counts and -- unless a
+// read name was seen more than twice (c->counts.irregular: the caller replays) -- c->parts.  ph: 1 with the phantom region 0
+int receive_regions_and_groups(bdx_ctx* c, uint32_t ph) {
+    hipStream_t s = c->stream;
+    BDX_TRY(await_ready(c, kRegionsReady, c->ev_regions, "the region table did not arrive: its kernels were not launched"));
+    const uint32_t nr_host = c->sb.h_counts0.as<StageCounts>()->n_regions;
+    if ((uint64_t)nr_host + ph > kMaxRegions) {   // (region ids are 26-bit fields of the packed group key)
+        HIPCHK(c, hipStreamSynchronize(s));
+        return fail(c, BDX_ELIMIT, "more than 2^26 - 2 accepted regions in one context");
     }
-    t_h1 = std::chrono::steady_clock::now();
+    // The host's share of the walk reads the table where the device left it, in pinned memory.  (Until round 6 the table was copied into
+    // ordinary memory first -- "one streaming copy is cheaper than the walk's scattered reads", true when the host walked every component:
+    // 5.7 MB at a genome share, 0.28 ms of this thread between the join kernel's end and the pair groups' arrival 0.14 ms later; the
+    // host's walk of its ~1,200 groups then started late and the device stood idle in front of the table stage.)  A large share
+    // (debug "regions_copy" = 1: always) still gets its copy, once the groups have said how large it is.
+    // (a small table is copied at once, as ever: its copy fits between the join kernel's end and the groups' arrival -- 32 k regions are 70 us)
+    const bool copy_first = c->dbg_regions_copy == 1 || (c->dbg_regions_copy == 0 && nr_host < kBorrowRegionsMin);
+    if (copy_first) decode_regions(c, c->sb.h_regs.as<RegionRec>(), c->sb.h_pk.as<uint32_t>(), nr_host, ph, false);
+    BDX_TRY(await_ready(c, kGroupsReady, c->ev_groups, "the pair groups did not arrive: their kernels were not launched"));
+    c->counts = *c->h_counts.as<StageCounts>();
+    if (!copy_first) decode_regions(c, c->sb.h_regs.as<RegionRec>(), c->sb.h_pk.as<uint32_t>(), nr_host, ph,
+                                    c->dbg_regions_copy == 2 || (uint64_t)c->counts.n_groups * 8 < nr_host);   // (borrowed while the walk touches a fraction of the table:
+                                    // a walk of 20 k groups over 15 k regions was 46 us faster on its copy)
+    if (c->counts.irregular) return BDX_OK;
+    if (c->counts.overflow) return fail(c, BDX_EINTERNAL, "group list overflow");
+    decode_groups(c, c->sb.h_groups.as<GroupRec>(), c->counts.n_groups, ph);
+    c->last_big_groups = (int64_t)c->counts.n_groups + c->counts.n_groups_big;  // (the host's share: mostly such components)
+    return BDX_OK;
+}
+
+// host-side time stamps of a run: its begin, the hand-over to the host, the start and the end of the host walk (bdx_get_timings [4] .. [7])
+using RunTime = std::chrono::steady_clock::time_point;
+struct RunClock { RunTime begin, h0, h1, h2; };
+RunTime run_now() { return std::chrono::steady_clock::now(); }
+
+// a read name seen more than twice: the pair model does not hold (see bdx_walk_reads.cpp) and the run ends through the read-level replay
+int finish_by_replay(bdx_ctx* c, uint32_t ph, const RunClock& t) {
+    BDX_TRY(replay_reads(c, ph));
+    const RunTime t_r = run_now();
+    c->stage_ms[kMsGroupsWait] = ms_between(t.h0, t.h1); c->stage_ms[kMsHostWalk] = ms_between(t.h1, t_r); c->stage_ms[kMsRun] = ms_between(t.begin, t_r);
+    return BDX_OK;
+}
+
+void record_timings(bdx_ctx* c, const RunClock& t) {
+    const RunTime t_end = run_now();
+    if (c->stage_timing) {
+        (void)hipEventSynchronize(c->ev[5]);  // (complete by now; makes the elapsed-time queries valid)
+        auto evms = [&](int a, int b) { float ms = 0; (void)hipEventElapsedTime(&ms, c->ev[a], c->ev[b]); return ms; };
+        c->stage_ms[kMsCompact] = evms(2, 3);
+        c->stage_ms[kMsCut] = evms(3, 4);
+        c->stage_ms[kMsJoinAssemble] = evms(4, 5);
+    }
+    c->stage_ms[kMsGroupsWait] = ms_between(t.h0, t.h1);
+    c->stage_ms[kMsHostWalk] = ms_between(t.h1, t.h2);
+    c->stage_ms[kMsFinish] = ms_between(t.h2, t_end);
+    c->stage_ms[kMsRun] = ms_between(t.begin, t_end);
+}
+
+}  // namespace
+
+extern "C" {
+
+// plan, route, receive, host walk, table or host finish, support, timings
+int bdx_run(bdx_ctx* c) {
+    if (!c) return BDX_EINVAL;
+    NOT_WHILE_SIZING(c);
+    RunClock t;
+    t.begin = run_now();
+    BDX_TRY(enqueue_device_half(c, plan_sizing(c), host_walks_all(c)));
+    const uint32_t na = c->p1.n_anom;
+    const uint32_t ph = (na && phantom_region_opt(c)) ? 1u : 0u;
+    t.h0 = run_now();
+    if (na) BDX_TRY(receive_regions_and_groups(c, ph));
+    t.h1 = run_now();
+    if (na && c->counts.irregular) return finish_by_replay(c, ph, t);
     BDX_TRY(host_walk(c, c->counts.last_maxq, na != 0));
-    const auto t_h2 = std::chrono::steady_clock::now();
+    t.h2 = run_now();
     if (na) {
         BDX_TRY(do_k6_table(c));
-        rc = finish_table(c);
+        BDX_TRY(finish_table(c));
     } else {
-        rc = finish_host_walk(c);
+        BDX_TRY(finish_host_walk(c));
     }
-    if (rc != BDX_OK) return rc;
     if (c->collect_support) {
         materialize(c);
         BDX_TRY(collect_support(c, ph));
     }
-    const auto t_end = std::chrono::steady_clock::now();
-    if (c->stage_timing) {
-        (void)hipEventSynchronize(c->ev[5]);  // (complete by now; makes the elapsed-time queries valid)
-        auto evms = [&](int a, int b) { float ms = 0; (void)hipEventElapsedTime(&ms, c->ev[a], c->ev[b]); return ms; };
-        c->stage_ms[1] = evms(2, 3);
-        c->stage_ms[2] = evms(3, 4);
-        c->stage_ms[3] = evms(4, 5);
-    }
-    c->stage_ms[4] = ms_between(t_h0, t_h1);
-    c->stage_ms[5] = ms_between(t_h1, t_h2);
-    c->stage_ms[6] = ms_between(t_h2, t_end);
-    c->stage_ms[7] = ms_between(t_begin, t_end);
+    record_timings(c, t);
     return BDX_OK;
 }
 

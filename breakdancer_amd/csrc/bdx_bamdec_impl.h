@@ -253,7 +253,7 @@ int bam_feed_classifier(bdx_bamdec* d, bool final) {
             d->presized = true;
             const double est = (double)counted / (double)bytes_counted * (double)total * 1.10 + (double)d->records_at_arm;
             if (est >= (double)(1u << 20) && !c->ran) {
-                const uint64_t prior = (uint64_t)est / 32 + 4096;
+                const uint64_t prior = prior_anomalous((uint64_t)est);
                 if (prior <= kMaxAnomalous) {
                     const int device = d->device;
                     d->presize_thread = std::thread([d, c, prior, device] {

@@ -705,18 +705,16 @@ bool dist_tracing() {
 }
 
 // A ready word, else synchronise and look again, else the kernels that set it were never launched.  Two flavours: a word of this
-// rank's report area (a one-thread kernel sets it), and a context's own ready word (where polling is off, `ev` stands for it).
+// rank's report area (a one-thread kernel sets it), and a context's own ready word (await_ready; the context's error is the run's).
 int await_word(bdx_dist* d, volatile uint32_t* w, uint32_t value, hipStream_t s, const char* what) {
     if (wait_word(w, value)) return BDX_OK;
     DHIP(d, hipStreamSynchronize(s));
     if (*w != value) return dfail(d, BDX_EINTERNAL, std::string(what) + " did not arrive: its kernels were not launched");
     return BDX_OK;
 }
-int await_flag(bdx_dist* d, bdx_ctx* c, int idx, hipStream_t s, hipEvent_t ev, const char* what) {
-    if (wait_flag(c, idx, c->seq)) return BDX_OK;
-    if (c->poll || !ev) DHIP(d, hipStreamSynchronize(s)); else DHIP(d, hipEventSynchronize(ev));
-    if (!flag_arrived(c, idx)) return dfail(d, BDX_EINTERNAL, std::string(what) + " did not arrive: their kernels were not launched");
-    return BDX_OK;
+int await_flag(bdx_dist* d, bdx_ctx* c, ReadyWord w, hipEvent_t ev, const char* missing) {
+    const int rc = await_ready(c, w, ev, missing);
+    return rc == BDX_OK ? rc : dfail(d, rc, c->err);
 }
 
 // the first all-reduce's vector (collective A): one place that knows the order of its parts
@@ -977,7 +975,7 @@ int DistRun::pass1_and_counts(std::vector<uint64_t>& v1) {
         const int orc = check_order(d);
         if (orc != BDX_OK) return orc;
     }
-    DCTX(d, C, do_pass1(C, 0, false, false));   // (its record is waited for together with the chromosome table)
+    DCTX(d, C, do_pass1(C, {}));   // (its record is waited for together with the chromosome table)
     TidTableParams tp{};
     tp.tid = C->d.tid; tp.lib = C->d.lib; tp.cls = C->b_cls.as<uint8_t>(); tp.n = C->n; tp.ntiles = C->ntiles; tp.tstride = C->tstride;
     tp.ntids = ntids; tp.nkeys = nkeys; tp.nlibs = nlibs; tp.ncols = ncols; tp.libs = C->b_libs.as<DevLib>();
@@ -1358,7 +1356,7 @@ int DistRun::join_walk_table(const Stats& A, const Regions& B, const ExchangePla
         DHIP(d, hipStreamSynchronize(C->copy_stream));
         decode_regions(C, regs, pk, (uint32_t)NR, 0, true);
     }
-    if (const int rc = await_flag(d, C, 1, s, C->ev_groups, "the pair groups")) return rc;
+    if (const int rc = await_flag(d, C, kGroupsReady, C->ev_groups, "the pair groups did not arrive: their kernels were not launched")) return rc;
     C->counts = *C->h_counts.as<StageCounts>();
     if (C->counts.irregular) *irregular = 1;   // a read name seen more than twice: the run is replayed read by read on rank 0 (replay_route)
     if (C->counts.overflow) return dfail(d, BDX_EINTERNAL, "group list overflow");
@@ -1705,7 +1703,7 @@ int DistRun::walk_gathered(const Stats& A, const Regions& B, const Summary& S, c
         // converged fails the closure check and is the host's)
         DCTX(d, U, k6_prepare(U, force_host(), kK6LabelRoundsGather));
         DCTX(d, U, k6_then_walk(U, launch_k6_groups));
-        if (const int rc = await_flag(d, U, 1, su, nullptr, "the pair groups of the gathered components")) return rc;
+        if (const int rc = await_flag(d, U, kGroupsReady, nullptr, "the pair groups of the gathered components did not arrive: their kernels were not launched")) return rc;
         U->counts = *U->h_counts.as<StageCounts>();
         if (U->counts.overflow) return dfail(d, BDX_EINTERNAL, "group list overflow (gathered components)");
     }

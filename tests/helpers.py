@@ -329,3 +329,41 @@ def load_chr21(opts, config_name="inv_del_bam_config"):
     run.targets = decoded[0][0]
     run.decoded = decoded
     return run
+
+
+# ---- results of a single-context run, element for element (the tests that compare one route through bdx_run with another) ----
+
+def _bits(a):
+    return a.view(np.dtype("u%d" % a.dtype.itemsize)) if a.dtype.kind == "f" else a
+
+
+def snapshot(bd):
+    svs, (li, lp), (ck, cv) = bd.svs()
+    return dict(summary=bd.summary(), svs=svs, sv_lists=(li, lp, ck, cv), regions=bd.regions(), counters=bd.counters(),
+                cls=bd.read_class())
+
+
+def assert_same(a, b):
+    assert a["summary"] == b["summary"], (a["summary"], b["summary"])
+    for tab in ("svs", "regions"):
+        assert a[tab].shape == b[tab].shape, tab
+        for name in a[tab].dtype.names:
+            np.testing.assert_array_equal(_bits(a[tab][name]), _bits(b[tab][name]), err_msg=tab + "." + name)
+    for x, y in zip(a["sv_lists"], b["sv_lists"]):
+        np.testing.assert_array_equal(_bits(x), _bits(y))
+    assert a["counters"].keys() == b["counters"].keys()
+    for k in a["counters"]:
+        np.testing.assert_array_equal(_bits(a["counters"][k]), _bits(b["counters"][k]), err_msg=k)
+    np.testing.assert_array_equal(a["cls"], b["cls"])
+
+
+def context(mode=0, **debug):
+    """a context over synth's one-library configuration: enqueue-ahead mode `mode`, debug switches by name"""
+    import breakdancer_amd as bda
+    from breakdancer_amd.api import LibraryConfig, Options
+    from breakdancer_amd.synth import LIB_C2
+    bd = bda.BreakDancer(Options(), [LibraryConfig(**LIB_C2)], 1, max_read_window_size=200)
+    bd.set_enqueue_ahead(mode)
+    for name, value in debug.items():
+        bd.set_debug(name, value)
+    return bd

@@ -6,12 +6,10 @@ the debug switch "no_poll" is the route that waits for the record first, as ever
 import numpy as np
 import pytest
 
-from helpers import OracleRun, make_opts
+from helpers import OracleRun, assert_same, context, make_opts, snapshot
 from runner import compare, oracle_case, product_from_oracle
 
-import breakdancer_amd as bda
-from breakdancer_amd.api import LibraryConfig, Options
-from breakdancer_amd.synth import LIB_C2, make_chromosome
+from breakdancer_amd.synth import make_chromosome
 
 pytestmark = pytest.mark.gpu
 
@@ -59,40 +57,6 @@ def test_small_inputs_match_the_oracle(kind, monkeypatch):
     else:
         assert s["n_reads"] == 2600 and s["n_anomalous"] > 0
     bd.close()
-
-
-# ---- results of a run, element for element --------------------------------------------------------------------------------------------
-
-def _bits(a):
-    return a.view(np.dtype("u%d" % a.dtype.itemsize)) if a.dtype.kind == "f" else a
-
-
-def snapshot(bd):
-    svs, (li, lp), (ck, cv) = bd.svs()
-    return dict(summary=bd.summary(), svs=svs, sv_lists=(li, lp, ck, cv), regions=bd.regions(), counters=bd.counters(),
-                cls=bd.read_class())
-
-
-def assert_same(a, b):
-    assert a["summary"] == b["summary"], (a["summary"], b["summary"])
-    for tab in ("svs", "regions"):
-        assert a[tab].shape == b[tab].shape, tab
-        for name in a[tab].dtype.names:
-            np.testing.assert_array_equal(_bits(a[tab][name]), _bits(b[tab][name]), err_msg=tab + "." + name)
-    for x, y in zip(a["sv_lists"], b["sv_lists"]):
-        np.testing.assert_array_equal(_bits(x), _bits(y))
-    assert a["counters"].keys() == b["counters"].keys()
-    for k in a["counters"]:
-        np.testing.assert_array_equal(_bits(a["counters"][k]), _bits(b["counters"][k]), err_msg=k)
-    np.testing.assert_array_equal(a["cls"], b["cls"])
-
-
-def context(mode=0, **debug):
-    bd = bda.BreakDancer(Options(), [LibraryConfig(**LIB_C2)], 1, max_read_window_size=200)
-    bd.set_enqueue_ahead(mode)
-    for name, value in debug.items():
-        bd.set_debug(name, value)
-    return bd
 
 
 def fresh(arrs, mode=0, **debug):
