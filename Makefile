@@ -8,7 +8,7 @@ KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
 HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp $(HOST)/table.cpp $(HOST)/store_counts.cpp $(HOST)/inputs.cpp
 
-all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-table-check bin/bdx-feed-probe tests/prims/libbdx_prims.so oracle
+all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-table-check bin/bdx-feed-probe tests/prims/libbdx_prims.so oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -47,6 +47,11 @@ bin/bdx-depth-check: $(HOST)/depth_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/depth_check_main.cpp $(HOST)/vcf.cpp
 
+# test tooling: --mapq's INFO formatting (vcf.cpp) on its own (tests/test_mapq.py)
+bin/bdx-mapq-check: $(HOST)/mapq_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h
+	@mkdir -p bin
+	g++ $(HOSTFLAGS) -o $@ $(HOST)/mapq_check_main.cpp $(HOST)/vcf.cpp
+
 # test tooling: the table formatter (table.cpp) on its own, without libbdx (tests/test_table.py builds it again under the sanitizers)
 bin/bdx-table-check: $(HOST)/table_check_main.cpp $(HOST)/table.cpp $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/table.h $(HOST)/options.h $(HOST)/config.h include/bdx.h
 	@mkdir -p bin
@@ -74,7 +79,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-table-check tests/prims/libbdx_prims.so
+	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-table-check tests/prims/libbdx_prims.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -57,7 +57,7 @@ EXPORTS = ["bdx_opts_default", "bdx_create", "bdx_destroy", "bdx_strerror", "bdx
            "bdx_dist_world", "bdx_dist_chromosome", "bdx_dist_run", "bdx_dist_result", "bdx_dist_set_collect_support", "bdx_dist_get_phase_ms", "bdx_dist_phase_name", "bdx_dist_prepare", "bdx_dist_reset_reads", "bdx_dist_get_exchange", "bdx_dist_get_collectives", "bdx_dist_set_debug", "bdx_dist_owner", "bdx_dist_plan",
            "bdx_bamdec_create", "bdx_bamdec_destroy", "bdx_bamdec_last_error", "bdx_bamdec_acquire", "bdx_bamdec_submit", "bdx_bamdec_progress",
            "bdx_bamdec_finish", "bdx_bamdec_rearm", "bdx_bamdec_fetch", "bdx_bamdec_stats", "bdx_bamdec_host_ms", "bdx_merge_decoded", "bdx_append_decoded", "bdx_inflate_blocks", "bdx_insert_size_stats",
-           "bdx_count_junction_pairs", "bdx_bamdec_set_exclude", "bdx_bamdec_excluded", "bdx_exclude_mask", "bdx_count_site_pairs", "bdx_site_breakpoint_bounds", "bdx_count_interval_reads",
+           "bdx_count_junction_pairs", "bdx_bamdec_set_exclude", "bdx_bamdec_excluded", "bdx_exclude_mask", "bdx_count_site_pairs", "bdx_site_breakpoint_bounds", "bdx_count_interval_reads", "bdx_site_end_quality",
            "bdx_set_mark_duplicates", "bdx_get_duplicates", "bdx_dist_set_mark_duplicates", "bdx_dist_get_duplicates", "bdx_mark_duplicates"]
 
 # kDupT (csrc/bdx_dev.h): KD compares the records of a run directly when the run has at most this many, longer runs go through its table
@@ -67,6 +67,9 @@ DUP_T = 64
 SITE_DTYPE = np.dtype([("tid1", "<i4"), ("pos1", "<i4"), ("tid2", "<i4"), ("pos2", "<i4"), ("flag_mask", "<u4")])
 # bdx_site_bounds: the records that count for the site; per end the largest lower and the smallest upper bound (1-based; all 0 with n == 0)
 SITE_BOUNDS_DTYPE = np.dtype([("n", "<u4"), ("lo1", "<i4"), ("hi1", "<i4"), ("lo2", "<i4"), ("hi2", "<i4")])
+# bdx_site_quality: supporters of one end of a site, the records around it and the low ones among them; over the supporters' mapping
+# qualities the extremes, the lower quartile and the lower median (all 0 with n == 0)
+SITE_QUALITY_DTYPE = np.dtype([("n", "<u4"), ("n_all", "<u4"), ("n_low", "<u4"), ("qmin", "u1"), ("q1", "u1"), ("median", "u1"), ("qmax", "u1")])
 # bdx_interval: 0-based, half-open (--exclude's mask, bdx_count_interval_reads)
 INTERVAL_DTYPE = np.dtype([("tid", "<i4"), ("beg", "<i4"), ("end", "<i4")])
 # BDX_DEPTH_CHUNK (include/bdx.h): the records per chunk of bdx_count_interval_reads' table; the tests place intervals around its multiples
@@ -131,6 +134,7 @@ def load():
     L.bdx_count_site_pairs.argtypes = [vp, vp, C.c_size_t, C.c_int32, C.c_int, vp]
     L.bdx_site_breakpoint_bounds.argtypes = [vp, vp, C.c_size_t, C.c_int32, vp]
     L.bdx_count_interval_reads.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]
+    L.bdx_site_end_quality.argtypes = [vp, vp, vp, C.c_size_t, C.c_int32, vp]
     L.bdx_set_mark_duplicates.argtypes = [vp, C.c_int]
     L.bdx_get_duplicates.argtypes = [vp, vp, vp]
     L.bdx_dist_set_mark_duplicates.argtypes = [vp, C.c_int]

@@ -329,6 +329,26 @@ class BreakDancer:
         self._chk(self.lib.bdx_site_breakpoint_bounds(self.h, p(s), len(s), int(window), p(out)), "bdx_site_breakpoint_bounds")
         return out
 
+    def site_end_quality(self, sites, ends, window):
+        """Mapping quality at one end of given SV sites (bdx_site_end_quality; the rule is in include/bdx.h): `sites` and `window` as for
+        count_site_pairs, `ends` one 1 or 2 per site -- the end that is asked.  A passing record whose flag is in the mask supports the end
+        when it starts within `window` of it and its mate within `window` of the other end (no lower-mate condition: each mate counts at
+        its own end); a mapped record that starts within `window` of the end is around it, and low when its quality does not exceed its
+        library's minimum.  Returns an array of _lib.SITE_QUALITY_DTYPE: n, n_all, n_low, and over the supporters' qualities qmin, q1
+        (lower quartile), median (lower median) and qmax (all 0 with n == 0)."""
+        if isinstance(sites, np.ndarray) and sites.dtype == L.SITE_DTYPE:
+            s = np.ascontiguousarray(sites)
+        else:
+            rows = [tuple(int(v) for v in r) for r in sites]
+            s = np.array(rows, dtype=L.SITE_DTYPE) if rows else np.zeros(0, dtype=L.SITE_DTYPE)
+        e = np.ascontiguousarray(np.asarray(ends).reshape(-1), dtype=np.uint8)
+        if len(e) != len(s):
+            raise ValueError("sites and ends differ in length")
+        out = np.zeros(len(s), dtype=L.SITE_QUALITY_DTYPE)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.bdx_site_end_quality(self.h, p(s), p(e), len(s), int(window), p(out)), "bdx_site_end_quality")
+        return out
+
     def count_interval_reads(self, intervals, by_library=False):
         """Passing read starts of the last run inside given intervals (bdx_count_interval_reads; the rule is in include/bdx.h):
         `intervals` is an array of _lib.INTERVAL_DTYPE, or a sequence of (tid, beg, end), 0-based and half-open.  A record counts when it

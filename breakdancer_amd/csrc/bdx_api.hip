@@ -197,10 +197,10 @@ struct bdx_ctx {
     std::vector<KeySeg> key_segs;
     DevBuf b_seg;
 
-    // ---- bdx_count_junction_pairs, bdx_count_site_pairs, bdx_site_breakpoint_bounds (run_query) ----
+    // ---- bdx_count_junction_pairs, bdx_count_site_pairs, bdx_site_breakpoint_bounds, bdx_site_end_quality (run_query) ----
     size_t cls_n = (size_t)-1;        // reads the class bytes in b_cls describe (set by a completed pass 1; -1: none)
     DevBuf b_qtab;                    // bdx_count_interval_reads' table of one call (scratch: rebuilt by every call)
-    DevBuf b_qin, b_qout;             // a call's uploads (queries or sites, and behind them KI's table of the libraries' U) and its results.
+    DevBuf b_qin, b_qout;             // a call's uploads (queries or sites, and behind them KI's table of the libraries' U, or KM's of their minima and its ends) and its results.
                                       // One pair serves the three: every call ends with hipStreamSynchronize, so none can see another's data
     // ---- bdx_set_mark_duplicates ----
     bool mark_dup = false;            // KD marks duplicates in the flag column at the head of pass 1; pass 1 then does not start behind arriving batches
@@ -237,6 +237,9 @@ int hipfail(bdx_ctx* c, hipError_t e, const char* what) {
     } while (0)
 
 size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
+
+// a library's minimum mapping quality as K1 compares against it (quality > minimum passes) and as bdx_site_end_quality calls a record low
+int32_t resolved_min_mapq(const bdx_opts& o, const bdx_lib& l) { return l.min_mapping_quality < 0 ? o.min_map_qual : l.min_mapping_quality; }
 
 // The stamp of the next look-back launch on this context.  A state array may see a given stamp only once (a word of an
 // earlier launch with the same stamp would read as already published), so the stamp counts LAUNCHES, not runs -- the cut and
@@ -484,7 +487,7 @@ int bdx_create(bdx_ctx** out, const bdx_opts* opts, const bdx_lib* libs, int nli
     for (int i = 0; i < nlibs; ++i) {
         dl[i].upper = libs[i].uppercutoff;
         dl[i].lower = libs[i].lowercutoff;
-        dl[i].min_mapq = libs[i].min_mapping_quality < 0 ? opts->min_map_qual : libs[i].min_mapping_quality;
+        dl[i].min_mapq = resolved_min_mapq(*opts, libs[i]);
         dl[i].key = opts->cn_lib ? i : libs[i].bam_index;
     }
     std::vector<float> means(nlibs);
@@ -2240,7 +2243,7 @@ int bdx_classify(const bdx_opts* opts, const bdx_lib* libs, int nlibs, const bdx
     return bdx_get_read_class(c, cls_out, b->n);
 }
 
-// ---- queries over the resident store: K8, KS, KI (kq_queries.hip) and KR (kr_depth.hip) ----
+// ---- queries over the resident store: K8, KS, KI, KM (kq_queries.hip) and KR (kr_depth.hip) ----
 
 // What the calls check first, in this order: a context, no sizing pass in flight, a run that classified the store.  *none: n == 0, nothing to do.
 static int check_query_state(bdx_ctx* c, size_t n, bool* none) {
@@ -2307,11 +2310,12 @@ int bdx_count_junction_pairs(bdx_ctx* c, const int32_t* tid, const int32_t* pos_
     });
 }
 
-// What bdx_count_site_pairs and bdx_site_breakpoint_bounds check before they touch the device, in this order.  *none: n == 0, nothing to do.
-static int check_site_call(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, const void* out, bool* none) {
+// What bdx_count_site_pairs, bdx_site_breakpoint_bounds and bdx_site_end_quality check before they touch the device, in this order.
+// *none: n == 0, nothing to do.  others: the call's other arrays (its results; bdx_site_end_quality's ends) are all there.
+static int check_site_call(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, bool others, bool* none) {
     BDX_TRY(check_query_state(c, n, none));
     if (*none) return BDX_OK;
-    if (!sites || !out) return fail(c, BDX_EINVAL, "null array");
+    if (!sites || !others) return fail(c, BDX_EINVAL, "null array");
     if (window < 0 || window > (1 << 30)) return fail(c, BDX_EINVAL, "window < 0 or window > 2^30");
     if (n > ((size_t)1 << 31)) return fail(c, BDX_ELIMIT, "more than 2^31 sites in one call");
     for (size_t i = 0; i < n; ++i) {
@@ -2328,7 +2332,7 @@ static int check_site_call(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t 
 
 int bdx_count_site_pairs(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, int by_library, uint32_t* counts) {
     bool none;
-    BDX_TRY(check_site_call(c, sites, n, window, counts, &none));
+    BDX_TRY(check_site_call(c, sites, n, window, counts != nullptr, &none));
     if (none) return BDX_OK;
     const int nkeys = by_library ? c->nlibs : c->nbams;
     return run_query(c, {{sites, n * sizeof(bdx_site)}}, counts, n * (size_t)nkeys * 4, [&](const char* in, void* results, hipStream_t s) {
@@ -2338,7 +2342,7 @@ int bdx_count_site_pairs(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t wi
 
 int bdx_site_breakpoint_bounds(bdx_ctx* c, const bdx_site* sites, size_t n, int32_t window, bdx_site_bounds* out) {
     bool none;
-    BDX_TRY(check_site_call(c, sites, n, window, out, &none));
+    BDX_TRY(check_site_call(c, sites, n, window, out != nullptr, &none));
     if (none) return BDX_OK;
     // U per library: ceil(uppercutoff); 0 when that is negative; 2^30 when the cutoff is NaN, infinite or above 2^30
     std::vector<uint32_t> u(c->libs.size());
@@ -2352,6 +2356,23 @@ int bdx_site_breakpoint_bounds(bdx_ctx* c, const bdx_site* sites, size_t n, int3
     return run_query(c, {{sites, sbytes}, {u.data(), many ? u.size() * 4 : 0}}, out, n * sizeof(bdx_site_bounds), [&](const char* in, void* results, hipStream_t s) {
         launch_ki(KiParams{store_view(c), many ? c->d.lib : nullptr, (const KsSite*)in, (uint32_t)n, nlibs, window, c->opts.illumina_long_insert ? 1 : 0,
                            u.empty() ? 0u : u[0], many ? (const uint32_t*)(in + sbytes) : nullptr, (KiBounds*)results}, s);
+    });
+}
+
+int bdx_site_end_quality(bdx_ctx* c, const bdx_site* sites, const uint8_t* end, size_t n, int32_t window, bdx_site_quality* out) {
+    bool none;
+    BDX_TRY(check_site_call(c, sites, n, window, end && out, &none));
+    if (none) return BDX_OK;
+    for (size_t i = 0; i < n; ++i)
+        if (end[i] != 1 && end[i] != 2) return fail(c, BDX_EINVAL, "query " + std::to_string(i) + ": end is neither 1 nor 2");
+    std::vector<int32_t> least(c->libs.size());
+    for (size_t i = 0; i < least.size(); ++i) least[i] = resolved_min_mapq(c->opts, c->libs[i]);
+    const int nlibs = c->nlibs;
+    const bool many = nlibs > 1;   // (as in bdx_site_breakpoint_bounds: one library's minimum travels with the launch, and its lib column is never read)
+    const size_t sbytes = n * sizeof(bdx_site), tbytes = many ? least.size() * 4 : 0;   // (the table in front of the ends: it wants 4-byte alignment)
+    return run_query(c, {{sites, sbytes}, {least.data(), tbytes}, {end, n}}, out, n * sizeof(bdx_site_quality), [&](const char* in, void* results, hipStream_t s) {
+        launch_km(KmParams{store_view(c), c->d.mapq, many ? c->d.lib : nullptr, nlibs, least.empty() ? 0 : least[0], many ? (const int32_t*)(in + sbytes) : nullptr,
+                           (const KsSite*)in, (const uint8_t*)(in + sbytes + tbytes), (uint32_t)n, window, (KmQuality*)results}, s);
     });
 }
 

@@ -191,7 +191,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
-// The resident store as the kernels that answer queries over it see it (K8, KS, KI: kq_queries.hip; their shared pieces: bdx_window.h)
+// The resident store as the kernels that answer queries over it see it (K8, KS, KI, KM: kq_queries.hip; their shared pieces: bdx_window.h)
 struct StoreView {
     const int32_t *tid, *pos, *mtid, *mpos, *isize;   // sorted by (tid, pos)
     const uint16_t* flag;               // SAM flags
@@ -243,6 +243,25 @@ struct KiParams {
     KiBounds* out;                      // [nq]
 };
 
+// KM: mapping quality of the supporters of one end of given SV sites and of the records around it (bdx_site_end_quality)
+struct KmQuality {                      // = bdx_site_quality (include/bdx.h)
+    uint32_t n, n_all, n_low;           // supporters; records around the end; the low ones among them
+    uint8_t qmin, q1, median, qmax;     // over the supporters' qualities; all 0 with n == 0
+};
+struct KmParams {
+    StoreView st;
+    const uint8_t* mapq;                // quality column (AM tag if present, else MAPQ)
+    const uint8_t* lib;                 // library column; read only when nlibs > 1
+    int nlibs;                          // 1..255
+    int32_t q0;                         // library 0's minimum mapping quality, resolved as for K1 ...
+    const int32_t* qtab;                // ... and every library's [nlibs]; read only when nlibs > 1
+    const KsSite* sites;
+    const uint8_t* end;                 // [nq] 1 or 2: the end of sites[q] that is asked
+    uint32_t nq;
+    int32_t window;                     // 0..2^30
+    KmQuality* out;                     // [nq]
+};
+
 // KR (kr_depth.hip): passing read starts inside given intervals, per interval and key (bdx_count_interval_reads)
 struct KrInterval {                     // = bdx_interval (include/bdx.h)
     int32_t tid, beg, end;              // 0-based, half-open
@@ -292,6 +311,7 @@ void launch_kd_apply(const KdParams& p, uint16_t* flag, uint8_t* mask, hipStream
 void launch_k8(const K8Params& p, hipStream_t s);
 void launch_ks(const KsParams& p, hipStream_t s);
 void launch_ki(const KiParams& p, hipStream_t s);
+void launch_km(const KmParams& p, hipStream_t s);
 void launch_kr_table(const KrParams& p, hipStream_t s);   // chunk counts and their prefix per key: before launch_kr_query when p.table
 void launch_kr_query(const KrParams& p, hipStream_t s);
 void launch_k1(const K1Params& p, int grid, size_t lds, hipStream_t s, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);

@@ -126,6 +126,7 @@ Inputs::Inputs(int argc, char** argv, const Env& env)
         if (sites_window < 0) sites_window = cutoff_window(cfg, "--sites");
     }
     ci_window = !opts.ci ? 0 : opts.ci_window >= 0 ? opts.ci_window : cutoff_window(cfg, "--ci");
+    mapq_window = !opts.mapq ? 0 : opts.mapq_window >= 0 ? opts.mapq_window : cutoff_window(cfg, "--mapq");
     // Decode threads: the work is CPU-bound on zlib (~375 MB/s of inflated bytes per core), so what counts is the number of
     // cores this process may really use -- the cgroup's CPU quota when there is one (a container with "16 CPUs" on a
     // 256-thread host: 16 threads 0.64 s, 32 0.55 s, 64 0.70 s for 15 M records), else the hardware threads.  Twice that

@@ -1,5 +1,5 @@
 // What a run is given, settled before the GPU is touched: the BDX_* environment knobs, the options (or the -R cache's), the
-// configuration, and the opened or parsed option inputs (--vcf, --exclude, --sites, --ci).  bdx-dump-reads shares the two helpers.
+// configuration, and the opened or parsed option inputs (--vcf, --exclude, --sites, --ci, --mapq).  bdx-dump-reads shares the two helpers.
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -55,7 +55,7 @@ Env read_env();
 
 struct Inputs {
     // Fails in this order, each before the GPU is touched: option parsing, -R / config, (no BAM files: see no_bams), --vcf open, --exclude
-    // parse, --sites-vcf open and --sites parse, --ci window.
+    // parse, --sites-vcf open and --sites parse, --ci window, --mapq window.
     Inputs(int argc, char** argv, const Env& env);
     Inputs(const Inputs&) = delete;
     Inputs& operator=(const Inputs&) = delete;
@@ -74,6 +74,7 @@ struct Inputs {
     SiteTable site_table;
     int32_t sites_window = 0;
     int32_t ci_window = 0;       // --ci: without a finite cutoff the run ends here
+    int32_t mapq_window = 0;     // --mapq: likewise
     unsigned io_threads = 0;     // decode threads of the host producer
     std::vector<bdx_lib> libs;
     std::vector<int> devices;    // BDX_GPUS

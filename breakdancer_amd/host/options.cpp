@@ -67,6 +67,8 @@ void print_usage(const bdx_opts& o) {
     fprintf(stderr, "       --sites-window INT how far from a breakpoint a supporting read may start [the largest library uppercutoff]\n");
     fprintf(stderr, "       --ci           add CIPOS / CIEND (and CIN) to every --vcf / --sites-vcf record: the breakpoint intervals its supporting pairs allow\n");
     fprintf(stderr, "       --ci-window INT    how far from a breakpoint a supporting read of --ci may start [the largest library uppercutoff]\n");
+    fprintf(stderr, "       --mapq         add SQN / SQMIN / SQQ1 / SQMED / SQMAX and LQA / LQN / LQF to every --vcf / --sites-vcf record: the mapping quality of the reads that support either end, and the share of low-quality reads around it\n");
+    fprintf(stderr, "       --mapq-window INT  how far from a breakpoint a read of --mapq may start [the largest library uppercutoff]\n");
     fprintf(stderr, "       --depth        add RCI / RCF / RDR to every sample of a --vcf / --sites-vcf record: passing read starts inside the record, in its flanks, and their ratio\n");
     fprintf(stderr, "       --depth-flank INT  the width of either flank of --depth [%d]\n", Options::kDepthFlankDefault);
     fprintf(stderr, "       --mark-dup     flag duplicate read pairs (same library, positions and strands of both mates) on the GPU; they are ignored like reads with SAM flag 0x400\n");
@@ -79,12 +81,13 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
     // (the reference's letters parse exactly as with getopt; the long options are this tool's own)
-    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank };
+    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank, kMapq, kMapqWindow };
     static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude},
                                          {"sites", required_argument, nullptr, kSites}, {"sites-vcf", required_argument, nullptr, kSitesVcf},
                                          {"sites-window", required_argument, nullptr, kSitesWindow}, {"mark-dup", no_argument, nullptr, kMarkDup},
                                          {"ci", no_argument, nullptr, kCi}, {"ci-window", required_argument, nullptr, kCiWindow},
                                          {"depth", no_argument, nullptr, kDepth}, {"depth-flank", required_argument, nullptr, kDepthFlank},
+                                         {"mapq", no_argument, nullptr, kMapq}, {"mapq-window", required_argument, nullptr, kMapqWindow},
                                          {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
@@ -116,6 +119,10 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
             depth = true;
             continue;
         }
+        if (c == kMapq) {
+            mapq = true;
+            continue;
+        }
         if (c == kDepthFlank) {
             char* end = nullptr;
             const long v = strtol(optarg, &end, 10);
@@ -126,14 +133,14 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
             depth_flank = (int)v;
             continue;
         }
-        if (c == kSitesWindow || c == kCiWindow) {
+        if (c == kSitesWindow || c == kCiWindow || c == kMapqWindow) {
             char* end = nullptr;
             const long v = strtol(optarg, &end, 10);
             if (end == optarg || *end || v < 0 || v > (1L << 30)) {
-                fprintf(stderr, "--%s-window takes an integer from 0 to 2^30, not '%s'.\n", c == kCiWindow ? "ci" : "sites", optarg);
+                fprintf(stderr, "--%s-window takes an integer from 0 to 2^30, not '%s'.\n", c == kCiWindow ? "ci" : c == kMapqWindow ? "mapq" : "sites", optarg);
                 exit(1);
             }
-            (c == kCiWindow ? ci_window : sites_window) = (int)v;
+            (c == kCiWindow ? ci_window : c == kMapqWindow ? mapq_window : sites_window) = (int)v;
             continue;
         }
         const Row* row = nullptr;
@@ -163,6 +170,10 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     }
     if ((depth && vcf.empty() && sites_vcf.empty()) || (!depth && depth_flank >= 0)) {
         fprintf(stderr, "--depth needs --vcf FILE or --sites-vcf FILE to write to (and --depth-flank goes with --depth).\n");
+        exit(1);
+    }
+    if ((mapq && vcf.empty() && sites_vcf.empty()) || (!mapq && mapq_window >= 0)) {
+        fprintf(stderr, "--mapq needs --vcf FILE or --sites-vcf FILE to write to (and --mapq-window goes with --mapq).\n");
         exit(1);
     }
     o.chr_restricted = chr.empty() ? 0 : 1;

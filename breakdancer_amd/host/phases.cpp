@@ -299,6 +299,17 @@ Genotypes count_on_store(const Inputs& in, const Env& env, const Session& s, con
             fprintf(stderr, "[bdx timing] --ci: breakpoint bounds of %zu records (window %d, %zu with supporting pairs) %.4f s\n",
                     gt.vcf_rows.size() + gt.site_rows.size(), in.ci_window, with, secs(tv, now()));
     }
+    if (opts.mapq) {
+        const auto tv = now();
+        fill_quality(opts, rc, in.mapq_window, gt.vcf_rows);
+        fill_quality(opts, rc, in.mapq_window, gt.site_rows);
+        size_t ends = 0;
+        for (auto const* rows : {&gt.vcf_rows, &gt.site_rows})
+            for (auto const& r : *rows) ends += r.has_mapq ? (size_t)r.mq[0].held + (size_t)r.mq[1].held : 0;
+        if (env.timing)
+            fprintf(stderr, "[bdx timing] --mapq: mapping quality at %zu ends of %zu records (window %d) %.4f s\n", ends,
+                    gt.vcf_rows.size() + gt.site_rows.size(), in.mapq_window, secs(tv, now()));
+    }
     if (opts.depth) {
         const auto tv = now();
         const size_t ns = sample_names(opts, in.cfg).size();
@@ -373,10 +384,12 @@ void write_vcfs(const Inputs& in, Genotypes& gt) {
     const VcfCi* ci = opts.ci ? &ci_info : nullptr;
     const VcfDepth depth_info{opts.flank()};
     const VcfDepth* depth = opts.depth ? &depth_info : nullptr;
-    if (in.vcf) in.vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.vcf_rows), opts.exclude, nullptr, opts.mark_dup, ci, depth);
+    const VcfMapq mapq_header{in.mapq_window};
+    const VcfMapq* mapq = opts.mapq ? &mapq_header : nullptr;
+    if (in.vcf) in.vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.vcf_rows), opts.exclude, nullptr, opts.mark_dup, ci, depth, mapq);
     if (in.sites_vcf) {
         const VcfSites info{opts.sites, in.sites_window};
-        in.sites_vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.site_rows), opts.exclude, &info, opts.mark_dup, ci, depth);
+        in.sites_vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.site_rows), opts.exclude, &info, opts.mark_dup, ci, depth, mapq);
     }
 }
 

@@ -65,7 +65,7 @@ struct Calls {
 };
 Calls fetch_calls(const Session& s, size_t n_svs);
 
-// --vcf / --sites / --ci / --depth: the counts over the records the run holds
+// --vcf / --sites / --ci / --depth / --mapq: the counts over the records the run holds
 struct Genotypes {
     std::vector<VcfRecord> vcf_rows, site_rows;
 };

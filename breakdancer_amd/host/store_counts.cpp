@@ -190,6 +190,53 @@ void fill_ci(const Options& opts, const RunContexts& rc, int32_t window, std::ve
     }
 }
 
+// Each record becomes a site exactly as in fill_ci -- its ends put into order, its mask Options::sv_flag_mask -- and every end of it that
+// lies on a chromosome the run read is one query (KM, bdx_site_end_quality): up to two per record, all of an output's in one call, a
+// sharded run's on the rank that holds the ASKED end's chromosome -- every record that can count for an end lives there, so a CTX record's
+// two ends go to two ranks.  The ends stay in the site's order and the record notes that its own is the reverse (the writer swaps them
+// back).  A record takes part when both positions are >= 1, a read class maps to its type and at least one end is held.
+void fill_quality(const Options& opts, const RunContexts& rc, int32_t window, std::vector<VcfRecord>& out) {
+    constexpr size_t kWords = sizeof(bdx_site_quality) / 4;   // (count_on_ranks moves rows of 32-bit words: an end's summary is four)
+    static_assert(sizeof(bdx_site_quality) == 16 && alignof(bdx_site_quality) == 4, "bdx_site_quality is four 32-bit words");
+    std::vector<bdx_site> q;
+    std::vector<uint8_t> q_end;
+    std::vector<int32_t> q_tid;
+    std::vector<size_t> q_row;
+    for (size_t k = 0; k < out.size(); ++k) {
+        VcfRecord& r = out[k];
+        const uint32_t mask = opts.sv_flag_mask(r.type);
+        if ((!rc.held(r.chr1) && !rc.held(r.chr2)) || r.pos1 < 1 || r.pos2 < 1 || mask == 0) continue;
+        const bool swapped = r.chr1 > r.chr2 || (r.chr1 == r.chr2 && r.pos1 > r.pos2);
+        const bdx_site s = swapped ? bdx_site{r.chr2, r.pos2, r.chr1, r.pos1, mask} : bdx_site{r.chr1, r.pos1, r.chr2, r.pos2, mask};
+        r.has_mapq = true;
+        r.mq_swapped = swapped;
+        for (int e = 0; e < 2; ++e) {
+            const int32_t t = e ? s.tid2 : s.tid1;
+            r.mq[e] = EndQuality{};
+            if (!rc.held(t)) continue;
+            r.mq[e].held = true;
+            q.push_back(s); q_end.push_back((uint8_t)(e + 1)); q_tid.push_back(t); q_row.push_back(k);
+        }
+    }
+    std::vector<uint32_t> words;
+    count_on_ranks(rc, q_tid, kWords, "bdx_site_end_quality", words, [&](bdx_ctx* c, const std::vector<size_t>& m, uint32_t* w) {
+        std::vector<bdx_site> mine(m.size());
+        std::vector<uint8_t> ends(m.size());
+        for (size_t j = 0; j < m.size(); ++j) { mine[j] = q[m[j]]; ends[j] = q_end[m[j]]; }
+        std::vector<bdx_site_quality> b(m.size());
+        const int st = bdx_site_end_quality(c, mine.data(), ends.data(), m.size(), window, b.data());
+        if (st == BDX_OK) memcpy(w, b.data(), b.size() * sizeof(bdx_site_quality));
+        return st;
+    });
+    for (size_t i = 0; i < q.size(); ++i) {
+        bdx_site_quality b;
+        memcpy(&b, words.data() + i * kWords, sizeof b);
+        EndQuality& e = out[q_row[i]].mq[q_end[i] - 1];
+        e.n = b.n; e.n_all = b.n_all; e.n_low = b.n_low;
+        e.qmin = b.qmin; e.q1 = b.q1; e.median = b.median; e.qmax = b.qmax;
+    }
+}
+
 // Every record with both ends on one sequence the run read and pos1 != pos2 gives three intervals of read starts -- its inside and its two
 // flanks (vcf.h depth_spans), clamped to the sequence -- and all of them go to the GPU in one call (KR, bdx_count_interval_reads; a sharded
 // run's on the rank that holds the sequence).  RCI is the inside's count per sample, RCF the two flanks' together.

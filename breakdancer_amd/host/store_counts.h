@@ -1,4 +1,4 @@
-// --vcf / --sites / --ci / --depth: the counts over the records a finished run holds on the GPU (K8, KS, KI, KR of include/bdx.h), turned into the
+// --vcf / --sites / --ci / --depth / --mapq: the counts over the records a finished run holds on the GPU (K8, KS, KI, KR, KM of include/bdx.h), turned into the
 // records VcfWriter prints (vcf.h).
 #pragma once
 #include <cstdint>
@@ -36,12 +36,15 @@ std::vector<VcfRecord> site_records(const Options& opts, const BamConfig& cfg, c
 // --ci: CIPOS / CIEND of --vcf and --sites-vcf records from the breakpoint bounds their supporting pairs give.
 void fill_ci(const Options& opts, const RunContexts& rc, int32_t window, std::vector<VcfRecord>& out);
 
+// --mapq: SQ* / LQ* of --vcf and --sites-vcf records from the mapping qualities of the reads that support either end and of those around it.
+void fill_quality(const Options& opts, const RunContexts& rc, int32_t window, std::vector<VcfRecord>& out);
+
 // --depth: RCI / RCF of --vcf and --sites-vcf records from the passing read starts inside and beside them; lengths: the sequences' (the
 // flanks are clamped to them), ns: the samples.
 void fill_depth(const Options& opts, const RunContexts& rc, int32_t flank, const std::vector<uint32_t>& lengths, size_t ns, std::vector<VcfRecord>& out);
 
 // How far a supporting mate can start from a breakpoint it brackets: the ceiling of the largest finite library uppercutoff, the window
-// of --sites and --ci when theirs is not given.
+// of --sites, --ci and --mapq when theirs is not given.
 int32_t cutoff_window(const BamConfig& cfg, const char* option);
 
 }  // namespace bdhost

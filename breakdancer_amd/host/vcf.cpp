@@ -50,6 +50,25 @@ std::string depth_ratio(int64_t rci, int64_t rcf, int64_t len_in, int64_t len_fl
     return buf;
 }
 
+std::string mapq_info(const EndQuality& e1, const EndQuality& e2, bool swapped) {
+    const EndQuality* e[2] = {swapped ? &e2 : &e1, swapped ? &e1 : &e2};
+    auto key = [&](const char* name, auto entry) {
+        std::string s = std::string(";") + name + "=";
+        for (int k = 0; k < 2; ++k) s += (k ? "," : "") + (e[k]->held ? entry(*e[k]) : std::string("."));
+        return s;
+    };
+    auto quality = [](unsigned EndQuality::*q) { return [q](const EndQuality& x) { return x.n ? std::to_string(x.*q) : std::string("."); }; };
+    auto count = [](uint32_t EndQuality::*c) { return [c](const EndQuality& x) { return std::to_string(x.*c); }; };
+    return key("SQN", count(&EndQuality::n)) + key("SQMIN", quality(&EndQuality::qmin)) + key("SQQ1", quality(&EndQuality::q1)) +
+           key("SQMED", quality(&EndQuality::median)) + key("SQMAX", quality(&EndQuality::qmax)) + key("LQA", count(&EndQuality::n_all)) +
+           key("LQN", count(&EndQuality::n_low)) + key("LQF", [](const EndQuality& x) {
+               if (!x.n_all) return std::string(".");
+               char buf[32];
+               snprintf(buf, sizeof buf, "%.3f", (double)x.n_low / (double)x.n_all);
+               return std::string(buf);
+           });
+}
+
 VcfWriter::VcfWriter(const std::string& path) : path_(path) {
     f_ = fopen(path.c_str(), "w");
     if (!f_) throw std::runtime_error("unable to open VCF output file '" + path + "'");
@@ -61,7 +80,7 @@ VcfWriter::~VcfWriter() {
 
 void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                       const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude,
-                      const VcfSites* sites, bool mark_dup, const VcfCi* ci, const VcfDepth* depth) {
+                      const VcfSites* sites, bool mark_dup, const VcfCi* ci, const VcfDepth* depth, const VcfMapq* mapq) {
     if (!f_) throw std::runtime_error("VCF output file '" + path_ + "' is already closed");
     FILE* f = f_;
     fprintf(f, "##fileformat=VCFv4.2\n##source=breakdancer-max-mi355x\n##command=");
@@ -72,6 +91,7 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
     if (mark_dup) fprintf(f, "##mark_dup=1\n");
     if (ci) fprintf(f, "##ci_window=%d\n", ci->window);
     if (depth) fprintf(f, "##depth_flank=%d\n", depth->flank);
+    if (mapq) fprintf(f, "##mapq_window=%d\n", mapq->window);
     for (size_t t = 0; t < contigs.size(); ++t)
         fprintf(f, "##contig=<ID=%s,length=%u>\n", contigs[t].c_str(), t < lengths.size() ? lengths[t] : 0u);
     fputs("##FILTER=<ID=PASS,Description=\"All filters passed\">\n"
@@ -98,6 +118,16 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
               "##INFO=<ID=CIEND,Number=2,Type=Integer,Description=\"Confidence interval around END, likewise\">\n"
               "##INFO=<ID=CIPOS2,Number=2,Type=Integer,Description=\"Confidence interval around POS2, likewise (records without END)\">\n"
               "##INFO=<ID=CIN,Number=1,Type=Integer,Description=\"Read pairs the confidence intervals come from: those with one mate starting within ci_window of each breakpoint\">\n",
+              f);
+    if (mapq)
+        fputs("##INFO=<ID=SQN,Number=2,Type=Integer,Description=\"Reads supporting the first and the second printed breakpoint: passing reads of the record's type that start within mapq_window of it with their mate within mapq_window of the other (all samples pooled)\">\n"
+              "##INFO=<ID=SQMIN,Number=2,Type=Integer,Description=\"Smallest mapping quality among those reads (the AM tag if present, else MAPQ)\">\n"
+              "##INFO=<ID=SQQ1,Number=2,Type=Integer,Description=\"Lower quartile of their mapping qualities: the smallest q that ceil(SQN / 4) of them do not exceed\">\n"
+              "##INFO=<ID=SQMED,Number=2,Type=Integer,Description=\"Lower median of their mapping qualities: the smallest q that ceil(SQN / 2) of them do not exceed\">\n"
+              "##INFO=<ID=SQMAX,Number=2,Type=Integer,Description=\"Largest mapping quality among them\">\n"
+              "##INFO=<ID=LQA,Number=2,Type=Integer,Description=\"Mapped reads that start within mapq_window of the breakpoint, whatever their class\">\n"
+              "##INFO=<ID=LQN,Number=2,Type=Integer,Description=\"Those among LQA whose mapping quality does not exceed their library's minimum (-q, or the configuration's mapqual)\">\n"
+              "##INFO=<ID=LQF,Number=2,Type=Float,Description=\"LQN / LQA\">\n",
               f);
     fputs("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
           "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: second-smallest PL, capped at 99\">\n"
@@ -135,6 +165,7 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
             fprintf(f, ";CIPOS=%lld,%lld;%s=%lld,%lld;CIN=%u", (long long)c1.a, (long long)c1.b, r.chr2 == r.chr1 && r.pos2 >= r.pos1 ? "CIEND" : "CIPOS2",
                     (long long)c2.a, (long long)c2.b, r.ci_n);
         }
+        if (mapq && r.has_mapq) fputs(mapq_info(r.mq[0], r.mq[1], r.mq_swapped).c_str(), f);
         fputs(depth ? "\tGT:GQ:PL:DR:DV:RCI:RCF:RDR" : "\tGT:GQ:PL:DR:DV", f);
         for (size_t k = 0; k < samples.size(); ++k) {
             const int64_t dr = k < r.dr.size() ? r.dr[k] : -1, dv = k < r.dv.size() ? r.dv[k] : 0;

@@ -7,6 +7,9 @@
 // supporting pairs give (bdx_site_breakpoint_bounds).
 // --depth: either output's samples gain RCI / RCF / RDR behind DV: the passing read starts inside the record and in its two flanks,
 // counted on the GPU (bdx_count_interval_reads), and the ratio of the two densities.
+// --mapq: either output's records gain eight Number=2 INFO keys, one entry per printed end: SQN / SQMIN / SQQ1 / SQMED / SQMAX, the number
+// and the mapping qualities of the reads that support the end, and LQA / LQN / LQF, the reads around it, the low-quality ones among them and
+// their share (bdx_site_end_quality).  All samples pooled; FORMAT and the samples do not change.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -48,6 +51,19 @@ DepthSpans depth_spans(int64_t pos1, int64_t pos2, int64_t flank, int64_t contig
 // "." when rcf == 0 or either length is 0 (or below), or a count is unknown (< 0)
 std::string depth_ratio(int64_t rci, int64_t rcf, int64_t len_in, int64_t len_flank);
 
+// --mapq: what bdx_site_end_quality says about one end of a record; held: the end lies on a chromosome the run read (otherwise every
+// entry of the end is '.')
+struct EndQuality {
+    bool held = false;
+    uint32_t n = 0, n_all = 0, n_low = 0;
+    unsigned qmin = 0, q1 = 0, median = 0, qmax = 0;
+};
+// The INFO fragment of --mapq, ";SQN=a,b;SQMIN=a,b;SQQ1=a,b;SQMED=a,b;SQMAX=a,b;LQA=a,b;LQN=a,b;LQF=a,b": e1 / e2 are the ends of the site
+// the record was counted as ((tid1, pos1) <= (tid2, pos2)), swapped: the record prints them the other way round, so e2's entry comes first.
+// An entry is '.' for an end that is not held (every key), with n == 0 (SQMIN, SQQ1, SQMED, SQMAX; SQN prints 0) and with n_all == 0 (LQF);
+// LQF is n_low / n_all with three decimals (printf's rounding of the double quotient).
+std::string mapq_info(const EndQuality& e1, const EndQuality& e2, bool swapped);
+
 // one printed row of the table
 struct VcfRecord {
     size_t row = 0;                  // 1-based row number among the printed rows (ID = BDX<row>)
@@ -63,6 +79,9 @@ struct VcfRecord {
     bool has_depth = false;          // --depth: both ends on one sequence the run read, pos1 != pos2 (otherwise '.' in all three fields) ...
     DepthSpans spans;                // ... what was counted over ...
     std::vector<int64_t> rci, rcf;   // ... and the counts per sample: inside, and in the two flanks together
+    bool has_mapq = false;           // --mapq: the record took part (both positions >= 1, a read class maps to its type, an end the run read) ...
+    EndQuality mq[2];                // ... the two ends of the site it was counted as, in the site's order ...
+    bool mq_swapped = false;         // ... which is the reverse of the record's own
 };
 
 // what makes an output a --sites-vcf one: the records are given sites (ID SITE<row>, QUAL '.', INFO without ORI1 / ORI2 / NREADS / BDAF)
@@ -81,6 +100,11 @@ struct VcfDepth {
     int32_t flank = 0;               // the width of either flank
 };
 
+// what makes an output a --mapq one: the ##mapq_window= line and the eight SQ* / LQ* header lines
+struct VcfMapq {
+    int32_t window = 0;              // the window the reads were looked for with
+};
+
 class VcfWriter {
 public:
     // opens (truncates) the file at once: an unwritable path fails before any work is done
@@ -91,11 +115,11 @@ public:
     // header + records, sorted by (chr1, pos1) with ties in row order; `contigs` are the reference sequences (names are also the
     // records' CHROM / CHR2 values); exclude: the --exclude file of the run ("": none) for the ##exclude= line; sites: non-null for a
     // --sites-vcf output; mark_dup: the run marked duplicates (--mark-dup), for the ##mark_dup=1 line; ci: non-null for a run
-    // with --ci, depth: for a run with --depth; the file is closed afterwards
+    // with --ci, depth: for a run with --depth, mapq: for a run with --mapq; the file is closed afterwards
     void write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude = "",
                const VcfSites* sites = nullptr, bool mark_dup = false, const VcfCi* ci = nullptr,
-               const VcfDepth* depth = nullptr);
+               const VcfDepth* depth = nullptr, const VcfMapq* mapq = nullptr);
 
 private:
     std::string path_;

@@ -549,6 +549,31 @@ int bdx_count_site_pairs(bdx_ctx* ctx, const bdx_site* sites, size_t n, int32_t 
 typedef struct bdx_site_bounds { uint32_t n; int32_t lo1, hi1, lo2, hi2; } bdx_site_bounds;   /* 20 bytes */
 int bdx_site_breakpoint_bounds(bdx_ctx* ctx, const bdx_site* sites, size_t n, int32_t window, bdx_site_bounds* out);
 
+/* Mapping quality at ONE END of given SV sites: no counterpart in the reference (the SQ* / LQ* keys of the CLI's --mapq).  How good are the
+ * reads that support the end, and how large a share of the reads around it did -q turn away -- the classic sign of a repeat.  The rule,
+ * written down here once:
+ *   A QUERY    is (site, end): site a bdx_site exactly as bdx_count_site_pairs takes it (1-based, normalised, flag_mask), end 1 or 2.
+ *              (T, P) is the asked end -- (tid1, pos1) for end 1, (tid2, pos2) for end 2 --, (T', P') the other one.  NEAR is that of
+ *              bdx_count_site_pairs: 64-bit arithmetic, window 0 to 2^30.
+ *   SUPPORT    record i supports the end when cls[i] & BDX_CLS_PASS, bit BDX_CLS_FLAG(cls[i]) of flag_mask is set, it is near P on T and
+ *              its mate (mtid, mpos) is near P' on T'.  There is NO lower-mate condition: both mates of a pair are records and each
+ *              counts at its own end, which is what brings the upper mate's quality in.  When the two windows overlap one record may
+ *              support both ends; that is the rule, not an accident.  Only what the record itself carries is looked at.
+ *   AROUND     record i is around the end when tid == T, |pos + 1 - P| <= window and SAM flag 0x4 is clear.  It is LOW when its quality
+ *              (the mapq column: the AM tag if present, else MAPQ) is <= its library's minimum mapping quality, resolved as K1 resolves
+ *              it: bdx_lib.min_mapping_quality, or opts.min_map_qual when that is negative; a library index out of range is library 0.
+ *              The comparison is made in int, so a minimum below 0 or above 255 behaves as in K1 (which lets quality > minimum pass).
+ *   RESULT     n: the supporters; n_all: the records around, supporters or not; n_low: the low ones among them.  Over the supporters'
+ *              qualities: qmin and qmax the extremes, median the smallest q with #(quality <= q) >= ceil(n / 2) (the lower median),
+ *              q1 the smallest q with #(quality <= q) >= ceil(n / 4); the ranks in 64-bit.  With n == 0 the four bytes are 0.
+ * State, errors and their order are those of bdx_count_site_pairs; besides BDX_EINVAL for a null `end` with n > 0 and, behind the sites'
+ * own checks, for an end[i] outside {1, 2}; BDX_ELIMIT above 2^31 queries.  After bdx_run, or on a rank's context (bdx_dist_chromosome)
+ * after bdx_dist_run: a query is answered by the rank that holds T, since every record that can count for it has tid == T (the routing of
+ * bdx_count_interval_reads, not that of bdx_count_site_pairs).  A chromosome the context holds no reads of, or beyond the header, gives
+ * all zeros.  Not beside another call on the same context (bdx_trim_results included). */
+typedef struct bdx_site_quality { uint32_t n, n_all, n_low; uint8_t qmin, q1, median, qmax; } bdx_site_quality;   /* 16 bytes */
+int bdx_site_end_quality(bdx_ctx* ctx, const bdx_site* sites, const uint8_t* end, size_t n, int32_t window, bdx_site_quality* out);
+
 /* Passing read starts inside given intervals: no counterpart in the reference, which says nothing about read depth (the input of --depth's
  * RCI / RCF / RDR).  The rule, written down here once:
  *   Record i of the resident store counts for interval (tid, [beg, end)) -- 0-based, half-open, as in --exclude's mask -- when
