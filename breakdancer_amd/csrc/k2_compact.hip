@@ -268,25 +268,35 @@ template <bool kBases> __device__ __forceinline__ void k2_body(const K2Params& p
     }
 }
 
-__device__ __forceinline__ void k2_fills(const K2Params& p) {  // (every workgroup of the launch takes part)
+// 16 bytes per store (the buffers are allocation bases), the last words of a buffer one at a time: a quarter of the store instructions of a
+// fill word by word, 24.4 against 25.0 us at configs[1].  The fills stay IN FRONT of the body.  vmcnt counts stores as well as loads and
+// retires in order, so the body's first wait covers their acknowledgements too; behind the body they were tried and measured slower (25.1
+// against 24.3 us: a wave's fills are then the tail it ends on, and K4 behind it finds its table less settled --
+// profiles/r23_store_order_gaps_*.txt).  nblk: the workgroups that take part (those that compact).
+__device__ __forceinline__ void k2_fills(const K2Params& p, uint32_t nblk) {
 #pragma nounroll  // (indexed at run time, the argument block is read from kernarg memory where it is used; unrolled, all of it is loaded on entry and a third spilled to lanes: one VGPR more)
-    for (int f = 0; f < 4; ++f)
-        for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < p.fill_words[f]; i += gridDim.x * kBlock) p.fill_ptr[f][i] = p.fill_value[f];
+    for (int f = 0; f < 4; ++f) {
+        const uint32_t words = p.fill_words[f], quads = words >> 2, v = p.fill_value[f];
+        uint4* const q = (uint4*)p.fill_ptr[f];
+        for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < quads; i += nblk * kBlock) q[i] = make_uint4(v, v, v, v);
+        if (blockIdx.x == 0 && threadIdx.x < (words & 3u)) p.fill_ptr[f][4 * quads + threadIdx.x] = v;
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void k2_compact_kernel(const K2Params p) {
-    k2_fills(p);
+    k2_fills(p, gridDim.x);
     k2_body<true>(p, gridDim.x);
 }
 
 // the same with one more workgroup, the last, that runs the second level of the pass-1 finalisation: when K2 is enqueued
-// without waiting for the pass-1 record (enqueue-ahead) that one-workgroup kernel would only sit between two launches
+// without waiting for the pass-1 record (enqueue-ahead) that one-workgroup kernel would only sit between two launches.
+// That workgroup is left out of the fills' striding: the compacting workgroups cover every word.
 __global__ __launch_bounds__(kBlock) void k2_compact_side_kernel(const K2Params p, const FinalizeParams fp) {
-    k2_fills(p);
     if (blockIdx.x == gridDim.x - 1) {
         finalize2_body(fp);
         return;
     }
+    k2_fills(p, gridDim.x - 1);
     k2_body<false>(p, gridDim.x - 1);
 }
 

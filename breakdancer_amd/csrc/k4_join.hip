@@ -163,6 +163,26 @@ __global__ __launch_bounds__(256) void k4_join_kernel(K4Arrays k4, const int32_t
 // table (8 B per slot, load <= 0.25) lives in L2 / Infinity Cache, and the partitioning launches of the bucketed
 // path are not worth their latency.  partner[] must be -1 and the table all ones on entry.
 constexpr uint32_t kJoinForwardBlocks = 32;
+constexpr uint32_t kJoinForwardAhead = 4;   // 16-byte words a forwarding lane requests per turn (a turn of all of them: kJoinForwardBlocks * 256 * this many words)
+
+// dst[0 .. quads) = src[0 .. quads), thread t of gsz: a turn's loads are all issued before its stores, and the NEXT turn's loads before them too.
+// The stores go over the link; vmcnt counts them with the loads and retires in order, so a load issued behind a store waits for that store's
+// acknowledgement -- copied word by word, a wave had one store in flight.  (Past the end a lane reads the last word again and stores nothing.)
+__device__ __forceinline__ void forward_quads(uint4* dst, const uint4* src, uint32_t quads, uint32_t t, uint32_t gsz) {
+    if (quads == 0) return;
+    static_assert(kJoinForwardAhead == 4, "four named words (an array of them is kept in scratch memory)");
+    const uint32_t last = quads - 1u;
+    uint4 c0 = src[min(t, last)], c1 = src[min(t + gsz, last)], c2 = src[min(t + 2 * gsz, last)], c3 = src[min(t + 3 * gsz, last)];
+    uint32_t i = t;
+    for (; i + 3 * gsz < quads; i += 4 * gsz) {   // whole turns: no branch around a store, so the waits at the loop's end can be counted ones
+        const uint4 n0 = src[min(i + 4 * gsz, last)], n1 = src[min(i + 5 * gsz, last)], n2 = src[min(i + 6 * gsz, last)], n3 = src[min(i + 7 * gsz, last)];
+        dst[i] = c0; dst[i + gsz] = c1; dst[i + 2 * gsz] = c2; dst[i + 3 * gsz] = c3;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    }
+    if (i < quads) dst[i] = c0;   // the last, partial turn
+    if (i + gsz < quads) dst[i + gsz] = c1;
+    if (i + 2 * gsz < quads) dst[i + 2 * gsz] = c2;
+}
 __global__ __launch_bounds__(256) void k4_direct_join_kernel(K4Arrays k4, Entries en, const uint32_t* n_ptr, StageCounts* counts) {
     const uint32_t na = *n_ptr;
     // The region table's way to the host (single-context runs: the host's share of the walk reads it): kJoinForwardBlocks workgroups IN FRONT
@@ -177,16 +197,12 @@ __global__ __launch_bounds__(256) void k4_direct_join_kernel(K4Arrays k4, Entrie
         constexpr uint32_t kw = sizeof(RegionRec) / 4;
         {
             const uint32_t words = nr * kw, quads = words / 4;   // (the tables start on 256-byte boundaries)
-            const uint4* src = (const uint4*)en.r_rec_dev;
-            uint4* dst = (uint4*)en.r_rec_host;
-            for (uint32_t i = t; i < quads; i += gsz) dst[i] = src[i];
+            forward_quads((uint4*)en.r_rec_host, (const uint4*)en.r_rec_dev, quads, t, gsz);
             if (t < words - quads * 4) ((uint32_t*)en.r_rec_host)[quads * 4 + t] = ((const uint32_t*)en.r_rec_dev)[quads * 4 + t];
         }
         {
             const uint32_t words = nr * (uint32_t)en.nkeys2, quads = words / 4;
-            const uint4* src = (const uint4*)en.r_pk_dev;
-            uint4* dst = (uint4*)en.r_pk_host;
-            for (uint32_t i = t; i < quads; i += gsz) dst[i] = src[i];
+            forward_quads((uint4*)en.r_pk_host, (const uint4*)en.r_pk_dev, quads, t, gsz);
             if (t < words - quads * 4) en.r_pk_host[quads * 4 + t] = en.r_pk_dev[quads * 4 + t];
         }
     }

@@ -145,6 +145,8 @@ __global__ __launch_bounds__(256) void k6_pairs_kernel(K6Arrays a) {
             is = 0;
             if (i >= n) return false;
             const uint32_t j = first + i;
+            // (meta and isize are requested with the mate's region and taken by select: behind the test of it they were a round trip more)
+            const uint32_t m = a.meta[j], isz = (uint32_t)a.isize[j];
             int32_t plo;
             if (a.pair_lo) {
                 plo = a.pair_lo[j];
@@ -152,11 +154,10 @@ __global__ __launch_bounds__(256) void k6_pairs_kernel(K6Arrays a) {
                 const int32_t p = a.partner[j];
                 plo = (p >= 0 && (uint32_t)p < j) ? a.region_of[p] : -1;
             }
-            if (plo < 0) return false;
-            const uint32_t m = a.meta[j];
-            key = ((uint64_t)(uint32_t)plo << 12) | ((uint64_t)meta_lib(m) << 4) | (uint64_t)meta_flag(m);
-            is = (uint32_t)a.isize[j];
-            return true;
+            const bool ok = plo >= 0;
+            key = ok ? ((uint64_t)(uint32_t)plo << 12) | ((uint64_t)meta_lib(m) << 4) | (uint64_t)meta_flag(m) : ~0ull;
+            is = ok ? isz : 0u;
+            return ok;
         };
         uint64_t key = ~0ull;
         uint32_t is = 0;
@@ -293,7 +294,6 @@ __global__ __launch_bounds__(256) void k6_pairs_kernel(K6Arrays a) {
             const bool strong = m.gw >= mrp;
             const bool in_edge = m.gleader && lo < r && strong;
             const uint64_t gl_in = __ballot(in_edge);
-            if (in_edge) atomicAdd(&a.out_deg[lo], 1u);
             // sharded run: the earlier region of a gate-passing group is another rank's (its place in this rank's table is empty): the
             // component spans ranks -- both regions are tainted, every rank learns it, and rank 0 walks the component
             if (a.taint && in_edge && a.r_rec[lo].n == 0) { a.taint[lo] = 1; a.taint[r] = 1; }
@@ -325,6 +325,8 @@ __global__ __launch_bounds__(256) void k6_pairs_kernel(K6Arrays a) {
                     }
                 }
             }
+            // (behind the label loads above: in front of them the atomic's acknowledgement is part of what their wait covers)
+            if (in_edge) atomicAdd(&a.out_deg[lo], 1u);
             if (m.leader) a.parts[first + m.rank] = PartRec{(lo < r && !strong) ? (key | kWeakPart) : key, m.cnt, m.sum};
         }
         if (lane == 0) a.rs[r] = rs;
@@ -355,42 +357,47 @@ __global__ __launch_bounds__(256) void k6_label_kernel(K6Arrays a) {
 __global__ __launch_bounds__(256) void k6_classify_kernel(K6Arrays a) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.counts->n_regions) return;
-    const RegSum* s = &a.rs[r];
-    const uint32_t n_in = s->n_in;
-    const bool hub = s->big || n_in > (uint32_t)kK6MaxIn;
-    if (!hub && n_in == 0 && a.out_deg[r] == 0 && s->np_self == 0) return;  // no group that could ever be consumed
-    const uint32_t L = a.label[r];
-    if (hub || a.bad_v[r] || (a.taint && a.taint[r])) a.bad[L] = 1u;
-    if (!hub) {
+    // Loads first, stores behind them: vmcnt counts stores as well as loads and retires in order, so a bad[] store between two label[]
+    // loads puts its acknowledgement into the second load's wait.  Everything indexed by r -- the whole summary, degree, label, verdicts,
+    // the region's record -- is requested at once and without a branch (behind `&&` each was a round trip of its own); then every
+    // neighbour's label at once (a neighbour that is not there reads the region's own label, which decides nothing); then the stores.
+    const RegSum s = a.rs[r];
+    const uint32_t od = a.out_deg[r], L = a.label[r], bv = a.bad_v[r], tn = a.taint ? a.taint[r] : 0u;
+    const uint32_t* rw = (const uint32_t*)&a.r_rec[r];
+    const uint32_t r0 = rw[0], r1 = rw[1], r2 = rw[2], r3 = rw[3], r4 = rw[4], r5 = rw[5], r6 = rw[6], r7 = rw[7], r8 = a.first_of ? a.first_of[r] : rw[8];   // (word 8: `first`)
+    const uint32_t n_in = s.n_in;
+    const bool hub = s.big || n_in > (uint32_t)kK6MaxIn;
+    if (!hub & (n_in == 0) & (od == 0) & (s.np_self == 0)) return;  // no group that could ever be consumed
+    const bool own_bad = hub | (bv != 0) | (tn != 0);
+    uint32_t ll[kK6MaxIn];
 #pragma unroll
-        for (uint32_t e = 0; e < (uint32_t)kK6MaxIn; ++e) {  // (static trip count: no private array behind the loop)
-            if (e < n_in) {
-                const uint32_t ll = a.label[s->e_lo[e]];
-                if (ll != L) { a.bad[L] = 1u; a.bad[ll] = 1u; }
-            }
-        }
+    for (uint32_t e = 0; e < (uint32_t)kK6MaxIn; ++e) {  // (static trip count: no private array behind the loop)
+        const uint32_t lo = (!hub && e < n_in) ? s.e_lo[e] : r;
+        ll[e] = a.label[lo];
     }
+    if (own_bad) a.bad[L] = 1u;
+#pragma unroll
+    for (uint32_t e = 0; e < (uint32_t)kK6MaxIn; ++e)
+        if (ll[e] != L) { a.bad[L] = 1u; a.bad[ll[e]] = 1u; }
     const uint32_t slot = atomicAdd(&a.mcount[L], 1u);
     if (a.big_walk && slot < (uint32_t)kK6BigMembers) a.member_ids[(size_t)L * kK6BigMembers + slot] = r;
     if (slot < (uint32_t)kK6MaxMembers) {
         // The member record leaves as seven 16-byte stores (k6_walk_kernel fetches it as seven 16-byte words): written field by field it was
         // 28 scattered 4-byte stores per region, each a 32-byte write at the memory side -- 138 MB for the 130 k regions of a genome share
-        // (profiles/r05_pmc_genome.txt).  Every word is named (no struct on the stack: a private copy would go through scratch memory).
+        // (profiles/r05_pmc_genome.txt).  Every word is named (every index a constant: nothing goes through scratch memory).
         static_assert(sizeof(MemberInfo) == 7 * 16 && sizeof(RegionRec) == 36 && offsetof(MemberInfo, rec) == 4 && offsetof(MemberInfo, np_all) == 40 &&
                           offsetof(MemberInfo, e_lo) == 56 && offsetof(MemberInfo, stored) == 104, "a member's record is seven 16-byte words");
-        const uint32_t* rw = (const uint32_t*)&a.r_rec[r];
-        const uint32_t r0 = rw[0], r1 = rw[1], r2 = rw[2], r3 = rw[3], r4 = rw[4], r5 = rw[5], r6 = rw[6], r7 = rw[7], r8 = a.first_of ? a.first_of[r] : rw[8];   // (word 8: `first`)
         const uint32_t stored = (int)(a.chr_restricted ? r5 : r3) >= a.min_read_pair ? 1u : 0u;  // region_stored(): nonctx is word 5, n word 3
         uint4* dst = (uint4*)&a.members[(size_t)L * kK6MaxMembers + slot];
         dst[0] = make_uint4(r, r0, r1, r2);
         dst[1] = make_uint4(r3, r4, r5, r6);
-        dst[2] = make_uint4(r7, r8, s->np_all, s->np_self);
-        dst[3] = make_uint4(s->w_self, hub ? 0u : n_in, s->e_lo[0], s->e_lo[1]);
-        dst[4] = make_uint4(s->e_lo[2], s->e_w[0], s->e_w[1], s->e_w[2]);
-        dst[5] = make_uint4(s->e_off[0], s->e_off[1], s->e_off[2], s->e_cnt[0]);
-        dst[6] = make_uint4(s->e_cnt[1], s->e_cnt[2], stored, 0u);
+        dst[2] = make_uint4(r7, r8, s.np_all, s.np_self);
+        dst[3] = make_uint4(s.w_self, hub ? 0u : n_in, s.e_lo[0], s.e_lo[1]);
+        dst[4] = make_uint4(s.e_lo[2], s.e_w[0], s.e_w[1], s.e_w[2]);
+        dst[5] = make_uint4(s.e_off[0], s.e_off[1], s.e_off[2], s.e_cnt[0]);
+        dst[6] = make_uint4(s.e_cnt[1], s.e_cnt[2], stored, 0u);
     }
-    if (s->np_emit) atomicAdd(&a.pcount[L], s->np_emit);
+    if (s.np_emit) atomicAdd(&a.pcount[L], s.np_emit);
 }
 
 namespace {
@@ -601,8 +608,10 @@ __global__ __launch_bounds__(256) void k6_emit_kernel(K6Arrays a) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = r < NR;
     RegSum s{};
-    uint32_t od = 0, L = 0;
-    if (active) { s = a.rs[r]; od = a.out_deg[r]; L = a.label[r]; a.own_nsv[r] = 0; a.own_nacc[r] = 0; a.own_ncn[r] = 0; }
+    uint32_t od = 0, L = 0, own_members = 0;
+    // (own_nsv / own_nacc / own_ncn are cleared at the kernel's end: stores issued here stand in front of the loads of bad[], mcount[] and
+    // pcount[], whose wait then covers the stores' acknowledgements as well -- vmcnt counts both and retires in order)
+    if (active) { s = a.rs[r]; od = a.out_deg[r]; L = a.label[r]; }
     const bool hub = s.big || s.n_in > (uint32_t)kK6MaxIn;
     const bool registered = active && (hub || s.n_in > 0 || od > 0 || s.np_self > 0);
     const bool covered = registered && component_on_device(a, L);
@@ -611,27 +620,39 @@ __global__ __launch_bounds__(256) void k6_emit_kernel(K6Arrays a) {
         uint32_t o = wave_reserve(need, &a.counts->n_groups);
         if (need) {
             const uint32_t first = a.first_of ? a.first_of[r] : a.r_rec[r].first;
-            for (uint32_t i = 0; i < s.np_all; ++i) {
-                const PartRec q = a.parts[first + i];
-                const uint64_t key = q.key;
-                if (key & kWeakPart) continue;
-                if (o < a.g_cap) {
-                    GroupRec g;
-                    g.key = ((key >> 12) << 38) | ((uint64_t)r << 12) | (key & 0xFFFull);
-                    g.pairs = q.pairs;
-                    g.sum_isize = q.sum;
-                    a.g_rec[o] = g;
-                } else {
-                    a.counts->overflow = 1;
+            // four parts requested at once, their records stored behind the loads (as assemble_sv fetches its parts): a record goes to pinned
+            // host memory, and one stored per part stood in front of the next part's load -- a trip over the link in every turn
+            // (a part as one 16-byte word, b_parts being an allocation base, and past the last part the last once more: no branch around a
+            // load and no field left to be fetched beside its store)
+            static_assert(sizeof(PartRec) == 16 && offsetof(PartRec, pairs) == 8 && offsetof(PartRec, sum) == 12, "a part is one 16-byte word");
+            const uint4* const P4 = (const uint4*)a.parts;
+            for (uint32_t i = 0; i < s.np_all; i += 4) {
+                uint4 q[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) q[u] = P4[first + min(i + u, s.np_all - 1u)];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const uint64_t key = (uint64_t)q[u].x | ((uint64_t)q[u].y << 32);
+                    if (i + u >= s.np_all || (key & kWeakPart)) continue;
+                    if (o < a.g_cap) {
+                        GroupRec g;
+                        g.key = ((key >> 12) << 38) | ((uint64_t)r << 12) | (key & 0xFFFull);
+                        g.pairs = q[u].z;
+                        g.sum_isize = q[u].w;
+                        a.g_rec[o] = g;
+                    } else {
+                        a.counts->overflow = 1;
+                    }
+                    ++o;
                 }
-                ++o;
             }
         }
     }
     {   // the walk kernels' work: the smallest region of every device-walked component
         const bool owner = covered && L == r;
-        const bool small = owner && a.mcount[L] <= (uint32_t)kK6MaxMembers;
-        if (active) a.owners[r] = small ? a.mcount[L] : 0u;  // (the walk kernel takes one lane per region: no list, no indirection)
+        const uint32_t mc = owner ? a.mcount[L] : 0u;
+        const bool small = owner && mc <= (uint32_t)kK6MaxMembers;
+        own_members = small ? mc : 0u;
         const uint32_t no = (uint32_t)__popcll(__ballot(small));
         // (this kernel's four totals go to one of 64 slots, summed by whoever mirrors the counters: as atomics on the counter record itself they were
         // ~8,000 read-modify-writes of ONE cache line for a genome share's 130 k regions -- the kernel's 76 us)
@@ -651,6 +672,11 @@ __global__ __launch_bounds__(256) void k6_emit_kernel(K6Arrays a) {
             if (tg) atomicAdd(part ? &part[2] : &a.counts->n_groups_dev, tg);
             if (tb) atomicAdd(part ? &part[3] : &a.counts->n_groups_big, tb);
         }
+    }
+    // the stores no load of this kernel waits for, last
+    if (active) {
+        a.owners[r] = own_members;  // (the walk kernel takes one lane per region: no list, no indirection)
+        a.own_nsv[r] = 0; a.own_nacc[r] = 0; a.own_ncn[r] = 0;
     }
 }
 
@@ -1298,15 +1324,34 @@ __global__ __launch_bounds__(kScanBlock) void k6_score_kernel(K6Arrays a, double
         for (int off = 32; off > 0; off >>= 1) { max_nl = max(max_nl, __shfl_xor(max_nl, off)); max_ncn = max(max_ncn, __shfl_xor(max_ncn, off)); }
         // one candidate per lane: K5 for its terms (all 64 lanes take part: a term with a long series is summed by the whole
         // wave); the entries of the two flat lists go straight to the host's arrays
-        double logp = 0.0, err = 0.0;
-        for (int32_t q = 0; q < max_nl; ++q) {
-            const bool a2 = q < nl;
-            double lam = 1.0;
-            int32_t k = 0, li = 0;
-            if (a2) {
+        // The entries go to pinned host memory, and vmcnt counts stores with the loads and retires in order: a term's stage entry requested
+        // behind the stores of the term before it waits for their trip over the link.  So the next term's entry is requested before this
+        // term's stores, and the first copy-number entry before the first term's.  (The order of the sum per candidate is what it was.)
+        auto load_term = [&](int32_t q, double& lam, int32_t& k, int32_t& li) {
+            lam = 1.0; k = 0; li = 0;
+            if (q < nl) {
                 if (hosted) { lam = a.hs_lambda[l0 + q]; k = a.hs_lib_pairs[l0 + q]; li = a.hs_lib_index[l0 + q]; }
                 else { const LibStage t = a.lib_stage[(size_t)from * a.lib_stride + q]; lam = t.lambda; k = t.rc; li = t.lib; }
             }
+        };
+        auto load_cn = [&](int32_t t, int32_t& key, float& value) {
+            key = 0; value = 0.f;
+            if (t < ncn) {
+                if (hosted) { key = a.hs_cn_key[k0 + t]; value = a.hs_cn_value[k0 + t]; }
+                else { const CnStage cn = a.cn_stage[(size_t)from * a.nkeys + t]; key = cn.key; value = cn.value; }
+            }
+        };
+        double lam_n;
+        int32_t k_n, li_n, key_n;
+        float value_n;
+        load_term(0, lam_n, k_n, li_n);
+        load_cn(0, key_n, value_n);
+        double logp = 0.0, err = 0.0;
+        for (int32_t q = 0; q < max_nl; ++q) {
+            const bool a2 = q < nl;
+            const double lam = lam_n;
+            const int32_t k = k_n, li = li_n;
+            load_term(q + 1, lam_n, k_n, li_n);
             const double lt = poisson_term(lam, k, a2, lane);
             if (a2) {
                 a.lib_index[bg.x + q] = li;
@@ -1319,11 +1364,10 @@ __global__ __launch_bounds__(kScanBlock) void k6_score_kernel(K6Arrays a, double
             }
         }
         for (int32_t t = 0; t < max_ncn; ++t) {
+            const int32_t key = key_n;
+            const float value = value_n;
+            load_cn(t + 1, key_n, value_n);
             if (t < ncn) {
-                int32_t key;
-                float value;
-                if (hosted) { key = a.hs_cn_key[k0 + t]; value = a.hs_cn_value[k0 + t]; }
-                else { const CnStage cn = a.cn_stage[(size_t)from * a.nkeys + t]; key = cn.key; value = cn.value; }
                 a.cn_key[bg.y + t] = key;
                 a.cn_value[bg.y + t] = value;
             }
