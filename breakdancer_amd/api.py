@@ -94,6 +94,16 @@ def make_batch(arrs):
     return b, keep
 
 
+def lib_array(libs):
+    """list of LibraryConfig -> ctypes array of bdx_lib"""
+    arr = (L.bdx_lib * len(libs))()
+    for i, l in enumerate(libs):
+        arr[i].mean_insertsize, arr[i].std_insertsize = l.mean_insertsize, l.std_insertsize
+        arr[i].uppercutoff, arr[i].lowercutoff, arr[i].readlens = l.uppercutoff, l.lowercutoff, l.readlens
+        arr[i].min_mapping_quality, arr[i].bam_index = l.min_mapping_quality, l.bam_file_index
+    return arr
+
+
 def run_many(contexts, in_flight=3):
     """bdx_run_many: every context of the list runs, `in_flight` of them at a time (the native driver for one context per chromosome)"""
     lib = L.load()
@@ -116,11 +126,7 @@ class BreakDancer:
         self.libs = list(libs)
         self.nlibs, self.nbams = len(self.libs), nbams
         co = opts.to_c()
-        arr = (L.bdx_lib * self.nlibs)()
-        for i, l in enumerate(self.libs):
-            arr[i].mean_insertsize, arr[i].std_insertsize = l.mean_insertsize, l.std_insertsize
-            arr[i].uppercutoff, arr[i].lowercutoff, arr[i].readlens = l.uppercutoff, l.lowercutoff, l.readlens
-            arr[i].min_mapping_quality, arr[i].bam_index = l.min_mapping_quality, l.bam_file_index
+        arr = lib_array(self.libs)
         self.h = C.c_void_p()
         rc = self.lib.bdx_create(C.byref(self.h), C.byref(co), arr, self.nlibs, nbams, ntids, max_read_window_size, device)
         if rc != 0:
@@ -425,6 +431,22 @@ def mark_duplicates(tid, pos, mtid, mpos, flag, lib, name_key, device=0):
     if rc != 0:
         raise BdxError("bdx_mark_duplicates: %s" % lb.bdx_strerror(rc).decode())
     return out.astype(bool), groups.value
+
+
+def classify(opts, libs, arrs, device=0):
+    """bdx_classify on host arrays: the class byte of every record of the batch `arrs` (as for push_reads) under `opts` and `libs`, from a
+    context of its own; the number of source files is the larger of what the libraries and the batch's file indices say"""
+    lb = L.load()
+    co = opts.to_c()
+    libs = list(libs)
+    arr = lib_array(libs)
+    b, keep = make_batch(arrs)
+    out = np.zeros(b.n, np.uint8)
+    rc = lb.bdx_classify(C.byref(co), arr, len(libs), C.byref(b), out.ctypes.data_as(C.c_void_p), device)
+    del keep
+    if rc != 0:
+        raise BdxError("bdx_classify: %s" % lb.bdx_strerror(rc).decode())
+    return out
 
 
 def poisson_log_upper_tail(lam, k, device=0):

@@ -12,6 +12,7 @@ region-table invariants, and recovery of the planted variants."""
 import numpy as np
 import pytest
 
+from classify_cases import numpy_class_bytes
 from helpers import make_opts
 from runner import compare, product_from_oracle
 from test_gpu_configs import LIBS4, cfg_line, oracle_from_soa
@@ -26,37 +27,6 @@ TARGETS = ["chr%s" % c for c in list(range(1, 23)) + ["X", "Y"]]
 
 def share_lengths(fraction):
     return [int(m * 1e6 * fraction) for m in HG38_MBP]
-
-
-def numpy_class_bytes(d, upper, lower, min_mapq, opt_t=False, max_sd=1000000000):
-    """io/IlluminaPEReadClassifier.cpp:13-101 + the filter chain of BreakDancer.cpp:159-206 as array arithmetic:
-    (flag | pass << 4 | proper << 5) per record, the oracle's class byte"""
-    sam = d["flag"].astype(np.int32)
-    tid, mtid, pos, mpos = d["tid"], d["mtid"], d["pos"], d["mpos"]
-    ai = np.abs(d["isize"].astype(np.int64))
-    lib = d["lib"].astype(np.int64)
-    up = np.asarray(upper, np.float32)[lib]
-    lo = np.asarray(lower, np.float32)[lib]
-    rev, mrev = (sam & 0x10) != 0, (sam & 0x20) != 0
-    f = np.full(len(sam), 6, np.uint8)                                    # NORMAL_FR
-    f[ai.astype(np.float32) < lo] = 3                                       # ARP_SMALL_INSERT
-    f[ai.astype(np.float32) > up] = 2                                       # ARP_LARGE_INSERT
-    f[(pos < mpos) == rev] = 4                                              # ARP_RF (leftmost read on the reverse strand)
-    same = rev == mrev
-    f[same & rev] = 5                                                       # ARP_RR
-    f[same & ~rev] = 1                                                      # ARP_FF
-    f[tid != mtid] = 8                                                      # ARP_CTX
-    f[(sam & 0x8) != 0] = 9                                                 # MATE_UNMAPPED
-    f[(sam & 0x4) != 0] = 10                                                # UNMAPPED
-    f[((sam & 0x400) != 0) | ((sam & 0x1) == 0)] = 0                        # NA
-    unm = (sam & 0xC) != 0
-    ok = (f != 0) & ~unm & (d["mapq"].astype(np.int32) > np.asarray(min_mapq)[lib]) & ((f == 8) | (ai <= max_sd))
-    if opt_t:
-        ok &= tid != mtid
-    proper = ok & ((sam & (0x2 | 0x4 | 0x8 | 0x1 | 0x400)) == 0x3)
-    g = f.copy()
-    g[ok & (f == 5)] = 1                                                    # RR clusters with FF (BreakDancer.cpp:196-197)
-    return g | (ok.astype(np.uint8) << 4) | (proper.astype(np.uint8) << 5)
 
 
 def tables_equal(a, b):
