@@ -6,9 +6,9 @@ HOST := breakdancer_amd/host
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Iinclude
 KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/kq_queries.hip $(CSRC)/kr_depth.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/bdx_api.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
-HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp $(HOST)/table.cpp $(HOST)/store_counts.cpp $(HOST)/inputs.cpp
+HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/device_feed.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp $(HOST)/table.cpp $(HOST)/store_counts.cpp $(HOST)/inputs.cpp
 
-all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-table-check bin/bdx-feed-probe tests/prims/libbdx_prims.so oracle
+all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-table-check bin/bdx-feed-check bin/bdx-feed-probe tests/prims/libbdx_prims.so oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -57,6 +57,12 @@ bin/bdx-table-check: $(HOST)/table_check_main.cpp $(HOST)/table.cpp $(HOST)/opti
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/table_check_main.cpp $(HOST)/table.cpp $(HOST)/options.cpp $(HOST)/config.cpp
 
+# test tooling: the device feeder's sizing plan, piece cutter and tie rule (feed_plan.h) on their own, without libbdx (tests/test_feed.py
+# builds it again under the sanitizers)
+bin/bdx-feed-check: $(HOST)/feed_check_main.cpp $(HOST)/feed_plan.h $(HOST)/bgzf.h include/bdx.h
+	@mkdir -p bin
+	g++ $(HOSTFLAGS) -o $@ $(HOST)/feed_check_main.cpp
+
 # test tooling: the shared scan, wave-search, window-walk and insertion-merge headers on their own behind plain C entry points
 # (tests/test_gpu_prims.py, tests/test_gpu_insert.py)
 tests/prims/libbdx_prims.so: tests/prims/prims.hip $(CSRC)/bdx_scan.h $(CSRC)/bdx_wave_search.h $(CSRC)/bdx_window.h $(CSRC)/bdx_insert.h $(CSRC)/bdx_k3.h $(CSRC)/bdx_dev.h include/bdx.h
@@ -79,7 +85,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-table-check tests/prims/libbdx_prims.so
+	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-table-check bin/bdx-feed-check tests/prims/libbdx_prims.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -9,6 +9,7 @@
 // only checks that consecutive pieces agree on their record boundaries and takes the columns.
 #pragma once
 #include <atomic>
+#include <cctype>
 #include <condition_variable>
 #include <cstdint>
 #include <deque>
@@ -43,6 +44,50 @@ struct RecordFilter {  // -o <region>: one tid, records overlapping [beg, end) (
     int beg = 0, end = 1 << 29;
     bdx::ExcludeMask exclude{nullptr, nullptr, nullptr, 0};   // --exclude, tested after the region (the table outlives the reader); ntids == 0: none
 };
+
+// samtools region strings as the reference accepts them for -o (bam_aux.c:107-160 bam_parse_region): "name",
+// "name:beg" or "name:beg-end" (1-based, commas allowed); a name that itself contains ':' is tried as a whole
+template <class Reader>
+bool parse_region(const Reader& rd, const std::string& str, int& tid, int& beg, int& end) {
+    std::string s;
+    for (char c : str)
+        if (!isspace((unsigned char)c)) s += c;
+    size_t l = s.size(), name_end = l;
+    const size_t colon = s.rfind(':');
+    if (colon != std::string::npos) name_end = colon;
+    tid = -1;
+    if (name_end < l) {
+        int n_hyphen = 0;
+        size_t i = name_end + 1;
+        for (; i < l; ++i) {
+            if (s[i] == '-') ++n_hyphen;
+            else if (!isdigit((unsigned char)s[i]) && s[i] != ',') break;
+        }
+        if (i < l || n_hyphen > 1) name_end = l;
+        tid = rd.tid_of(s.substr(0, name_end));
+        if (tid < 0) {
+            tid = rd.tid_of(str);
+            if (tid < 0) return false;
+            name_end = l;
+        }
+    } else {
+        tid = rd.tid_of(str);
+        if (tid < 0) return false;
+    }
+    if (name_end < l) {
+        std::string t;
+        for (size_t i = name_end + 1; i < l; ++i)
+            if (s[i] != ',') t += s[i];
+        beg = atoi(t.c_str());
+        const size_t h = t.find('-');
+        end = h != std::string::npos ? atoi(t.c_str() + h + 1) : 1 << 29;
+        if (beg > 0) --beg;
+    } else {
+        beg = 0;
+        end = 1 << 29;
+    }
+    return beg <= end;
+}
 
 struct ColumnChunk {
     std::vector<int32_t> tid, pos, mtid, mpos, isize;
