@@ -58,7 +58,8 @@ EXPORTS = ["bdx_opts_default", "bdx_create", "bdx_destroy", "bdx_strerror", "bdx
            "bdx_bamdec_create", "bdx_bamdec_destroy", "bdx_bamdec_last_error", "bdx_bamdec_acquire", "bdx_bamdec_submit", "bdx_bamdec_progress",
            "bdx_bamdec_finish", "bdx_bamdec_rearm", "bdx_bamdec_fetch", "bdx_bamdec_stats", "bdx_bamdec_host_ms", "bdx_merge_decoded", "bdx_append_decoded", "bdx_inflate_blocks", "bdx_insert_size_stats",
            "bdx_count_junction_pairs", "bdx_bamdec_set_exclude", "bdx_bamdec_excluded", "bdx_exclude_mask", "bdx_count_site_pairs", "bdx_site_breakpoint_bounds", "bdx_count_interval_reads", "bdx_site_end_quality",
-           "bdx_set_mark_duplicates", "bdx_get_duplicates", "bdx_dist_set_mark_duplicates", "bdx_dist_get_duplicates", "bdx_mark_duplicates"]
+           "bdx_set_mark_duplicates", "bdx_get_duplicates", "bdx_dist_set_mark_duplicates", "bdx_dist_get_duplicates", "bdx_mark_duplicates",
+           "bdx_insert_size_histogram", "bdx_dist_insert_size_histogram", "bdx_estimate_insert_size", "bdx_set_libs", "bdx_dist_set_libs"]
 
 # kDupT (csrc/bdx_dev.h): KD compares the records of a run directly when the run has at most this many, longer runs go through its table
 DUP_T = 64
@@ -74,6 +75,15 @@ SITE_QUALITY_DTYPE = np.dtype([("n", "<u4"), ("n_all", "<u4"), ("n_low", "<u4"),
 INTERVAL_DTYPE = np.dtype([("tid", "<i4"), ("beg", "<i4"), ("end", "<i4")])
 # BDX_DEPTH_CHUNK (include/bdx.h): the records per chunk of bdx_count_interval_reads' table; the tests place intervals around its multiples
 DEPTH_CHUNK = 2048
+# BDX_ISIZE_BINS (include/bdx.h): the bins per library of bdx_insert_size_histogram; larger insert sizes only count in n_over
+ISIZE_BINS = 32768
+
+
+class bdx_insert_estimate(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("mean_all", "sd_all", "mean", "sd", "sd_minus", "sd_plus")] + \
+               [(k, C.c_uint64) for k in ("n", "n_kept", "n_minus", "n_plus")] + [("valid", C.c_int32)]
+
+
 SITE_FLAGS = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 5) | (1 << 8)   # BDX_SITE_FLAGS: the anomalous classes
 
 _lib = None
@@ -140,5 +150,10 @@ def load():
     L.bdx_dist_set_mark_duplicates.argtypes = [vp, C.c_int]
     L.bdx_dist_get_duplicates.argtypes = [vp, vp, vp]
     L.bdx_mark_duplicates.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    L.bdx_insert_size_histogram.argtypes = [vp, vp, vp]
+    L.bdx_dist_insert_size_histogram.argtypes = [vp, vp, vp]
+    L.bdx_estimate_insert_size.argtypes = [vp, C.POINTER(bdx_insert_estimate)]
+    L.bdx_set_libs.argtypes = [vp, C.POINTER(bdx_lib), C.c_int, C.c_int]
+    L.bdx_dist_set_libs.argtypes = [vp, C.POINTER(bdx_lib), C.c_int, C.c_int]
     _lib = L
     return L

@@ -182,6 +182,22 @@ class BreakDancer:
         self._chk(self.lib.bdx_get_duplicates(self.h, C.byref(m), C.byref(g)), "bdx_get_duplicates")
         return m.value, g.value
 
+    def insert_size_histogram(self):
+        """(hist[nlibs][ISIZE_BINS], n_over[nlibs]) as uint64: the insert sizes of the proper, well-mapped pairs the store holds, per library
+        (bdx_insert_size_histogram; the rule is in include/bdx.h); before or after a run"""
+        hist = np.empty((self.nlibs, L.ISIZE_BINS), dtype=np.uint64)
+        over = np.empty(self.nlibs, dtype=np.uint64)
+        self._chk(self.lib.bdx_insert_size_histogram(self.h, hist.ctypes.data_as(C.c_void_p), over.ctypes.data_as(C.c_void_p)), "bdx_insert_size_histogram")
+        return hist, over
+
+    def set_libs(self, libs, max_read_window_size):
+        """the libraries and the initial window of the runs that follow (bdx_set_libs): same number, same BAM indices; the next run classifies
+        the store again"""
+        libs = list(libs)
+        self._chk(self.lib.bdx_set_libs(self.h, lib_array(libs), len(libs), int(max_read_window_size)), "bdx_set_libs")
+        self.libs = libs
+        return self
+
     def push_reads(self, arrs):
         b, keep = make_batch(arrs)
         self._keep.append(keep)  # the H2D copies are asynchronous: the arrays must outlive them (released by run())
@@ -415,6 +431,19 @@ class BreakDancer:
         self.lib.bdx_get_timings(self.h, ms.ctypes.data_as(C.c_void_p), 12)
         return dict(zip(("classify", "compact", "regions", "join", "readback", "walk", "score", "total", "final_wait", "merge",
                          "combine_scores"), ms.tolist()))
+
+
+def estimate_insert_size(hist):
+    """bdx_estimate_insert_size: bam2cfg's figures of one library from its histogram hist[ISIZE_BINS] (host only, no GPU), as a dict"""
+    lib = L.load()
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    if h.shape != (L.ISIZE_BINS,):
+        raise ValueError("a histogram of %d bins is expected" % L.ISIZE_BINS)
+    out = L.bdx_insert_estimate()
+    rc = lib.bdx_estimate_insert_size(h.ctypes.data_as(C.c_void_p), C.byref(out))
+    if rc != 0:
+        raise BdxError("bdx_estimate_insert_size: %s" % lib.bdx_strerror(rc).decode())
+    return {k: getattr(out, k) for k, _ in L.bdx_insert_estimate._fields_}
 
 
 def mark_duplicates(tid, pos, mtid, mpos, flag, lib, name_key, device=0):

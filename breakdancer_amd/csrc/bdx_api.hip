@@ -29,6 +29,7 @@
 #include "bdx_scan.h"
 #include "bdx_walk.h"
 #include "bdx_bam_dev.h"
+#include "bdx_estimate.h"
 
 using namespace bdx;
 
@@ -200,6 +201,7 @@ struct bdx_ctx {
     // ---- bdx_count_junction_pairs, bdx_count_site_pairs, bdx_site_breakpoint_bounds, bdx_site_end_quality (run_query) ----
     size_t cls_n = (size_t)-1;        // reads the class bytes in b_cls describe (set by a completed pass 1; -1: none)
     DevBuf b_qtab;                    // bdx_count_interval_reads' table of one call (scratch: rebuilt by every call)
+    DevBuf b_hist;                    // bdx_insert_size_histogram's table of one call: [nlibs][BDX_ISIZE_BINS] counts and behind them n_over[nlibs]
     DevBuf b_qin, b_qout;             // a call's uploads (queries or sites, and behind them KI's table of the libraries' U, or KM's of their minima and its ends) and its results.
                                       // One pair serves the three: every call ends with hipStreamSynchronize, so none can see another's data
     // ---- bdx_set_mark_duplicates ----
@@ -2400,6 +2402,77 @@ int bdx_count_interval_reads(bdx_ctx* c, const bdx_interval* iv, size_t n, int b
         launch_kr_table(p, s);
         launch_kr_query(p, s);
     });
+}
+
+// ---- --estimate: the insert-size histogram of the store (KH, kh_insert_hist.hip), the estimate and the libraries of the runs that follow ----
+
+int bdx_insert_size_histogram(bdx_ctx* c, uint64_t* hist, uint64_t* n_over) {
+    if (!c) return BDX_EINVAL;
+    if (!hist || !n_over) return fail(c, BDX_EINVAL, "null array");
+    NOT_WHILE_SIZING(c);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the device table is copied out as it is");
+    const size_t nh = (size_t)c->nlibs * BDX_ISIZE_BINS, nw = nh + (size_t)c->nlibs;
+    if (c->n == 0) {
+        memset(hist, 0, nh * 8);
+        memset(n_over, 0, (size_t)c->nlibs * 8);
+        return BDX_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (c->copy_pending) {  // batches pushed since the last classifier launch
+        HIPCHK(c, hipStreamWaitEvent(s, c->ev_copy, 0));
+        c->copy_pending = false;
+    }
+    HIPCHK(c, c->b_hist.ensure(nw * 8));
+    HIPCHK(c, hipMemsetAsync(c->b_hist.p, 0, nw * 8, s));
+    KhParams p{};
+    p.tid = c->d.tid; p.mtid = c->d.mtid; p.isize = c->d.isize; p.flag = c->d.flag; p.mapq = c->d.mapq;
+    p.lib = c->nlibs > 1 ? c->d.lib : nullptr;   // (with one library the column is not copied)
+    p.n = c->n; p.nlibs = c->nlibs; p.libs = c->b_libs.as<DevLib>(); p.lib_mean = c->b_lib_mean.as<float>();
+    p.hist = c->b_hist.as<unsigned long long>(); p.n_over = p.hist + nh;
+    launch_kh(p, s);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hist, p.hist, nh * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(n_over, p.n_over, (size_t)c->nlibs * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return BDX_OK;
+}
+
+int bdx_estimate_insert_size(const uint64_t* hist, bdx_insert_estimate* out) {
+    if (!hist || !out) return BDX_EINVAL;
+    estimate_insert_size(hist, out);
+    return BDX_OK;
+}
+
+int bdx_set_libs(bdx_ctx* c, const bdx_lib* libs, int nlibs, int max_read_window_size0) {
+    if (!c) return BDX_EINVAL;
+    if (!libs) return fail(c, BDX_EINVAL, "null array");
+    if (nlibs != c->nlibs) return fail(c, BDX_EINVAL, "the number of libraries is not the context's");
+    for (int i = 0; i < nlibs; ++i)
+        if (libs[i].bam_index != c->libs[i].bam_index) return fail(c, BDX_EINVAL, "library " + std::to_string(i) + ": bam_index is not the one given at creation");
+    NOT_WHILE_SIZING(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<DevLib> dl(nlibs);
+    std::vector<float> means(nlibs);
+    for (int i = 0; i < nlibs; ++i) {
+        dl[i].upper = libs[i].uppercutoff;
+        dl[i].lower = libs[i].lowercutoff;
+        dl[i].min_mapq = resolved_min_mapq(c->opts, libs[i]);
+        dl[i].key = c->opts.cn_lib ? i : libs[i].bam_index;
+        means[i] = libs[i].mean_insertsize;
+    }
+    // in stream order: behind the classifier launches that followed the batches under the old libraries (their results are dropped below)
+    HIPCHK(c, hipMemcpyAsync(c->b_libs.p, dl.data(), (size_t)nlibs * sizeof(DevLib), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->b_lib_mean.p, means.data(), (size_t)nlibs * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the two vectors go with this call)
+    c->libs.assign(libs, libs + nlibs);
+    c->w0 = max_read_window_size0;
+    // a live or finished pass 1 belongs to the old cutoffs: the next run classifies from tile 0 through pass1_prepare
+    c->k1_live = false;
+    c->k1_done = 0;
+    c->ran = false;
+    c->cls_n = (size_t)-1;
+    return BDX_OK;
 }
 
 int bdx_set_process_option(const char* name, int value) {

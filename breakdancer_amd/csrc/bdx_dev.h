@@ -12,6 +12,9 @@ constexpr int kNumFlags = 11;
 constexpr int kK2TilesPerWave = 4; // K2 compacts four of K1's tiles per wave and needs the prefixes at those boundaries only
 constexpr int kCntCopies = 64;   // replication factor of the global pass-1 counters (power of two)
 constexpr int kMaxChunks = 64;   // chunks a tile-total column is scanned in (one workgroup of finalize_kernel each)
+constexpr int kKhMaxGrid = 1024; // KH's persistent workgroups: 256 CUs x 4, what its 35 KiB of LDS per workgroup lets a CU hold (K1's cap, kK1MaxGrid in
+                                 // bdx_api.hip, is a measured optimum of a kernel without such a limit; this one is the residency bound, so that the
+                                 // number of flushes stays the number of workgroups that can run at once)
 constexpr int kStashCap = 16;    // anomalous reads per tile that K1 leaves ready-made for K2 (a tile with more is compacted from the columns)
 constexpr int kStashKeys = 2;    // ... when there are at most this many normal-read counter keys (K2's fast path holds their totals in 16 lanes)
 
@@ -276,6 +279,21 @@ struct KrParams {
     uint32_t* table;                    // [nkeys][nchunks + 1]: passing records of the key in front of each chunk; null: every interval is walked
     uint32_t* counts;                   // [nq][nkeys]
 };
+
+// KH (kh_insert_hist.hip): insert-size histogram per library over the resident store (bdx_insert_size_histogram)
+struct KhParams {
+    const int32_t *tid, *mtid, *isize;
+    const uint16_t* flag;
+    const uint8_t* mapq;
+    const uint8_t* lib;                 // null: one library (the column is not resident)
+    uint64_t n;
+    int nlibs;                          // 1..255
+    const DevLib* libs;                 // [nlibs]: min_mapq, resolved as for K1
+    const float* lib_mean;              // [nlibs]: the libraries' mean insert sizes (where a library's LDS window sits; never the result)
+    unsigned long long* hist;           // [nlibs][BDX_ISIZE_BINS], zeroed by the caller
+    unsigned long long* n_over;         // [nlibs], likewise
+};
+void launch_kh(const KhParams& p, hipStream_t s);
 
 // KD (kd_markdup.hip): duplicate marking over the resident store (bdx_set_mark_duplicates, bdx_mark_duplicates)
 constexpr int kDupT = 64;               // neighbours a record looks at each way; runs of more records go through the table

@@ -607,6 +607,28 @@ int bdx_dist_set_mark_duplicates(bdx_dist* d, int on) {
     return rc == BDX_OK ? rc : dfail(d, rc, d->reads->err);
 }
 
+// bdx_insert_size_histogram over this rank's own store; the caller sums the ranks (threads of one process: no collective)
+int bdx_dist_insert_size_histogram(bdx_dist* d, uint64_t* hist, uint64_t* n_over) {
+    if (!d || !d->reads) return BDX_EINVAL;
+    const int rc = bdx_insert_size_histogram(d->reads, hist, n_over);
+    return rc == BDX_OK ? rc : dfail(d, rc, d->reads->err);
+}
+
+// bdx_set_libs for this rank's reads, for the result context on rank 0 and for the rank's own copy
+int bdx_dist_set_libs(bdx_dist* d, const bdx_lib* libs, int nlibs, int max_read_window_size0) {
+    if (!d || !d->reads) return BDX_EINVAL;
+    int rc = bdx_set_libs(d->reads, libs, nlibs, max_read_window_size0);
+    if (rc != BDX_OK) return dfail(d, rc, d->reads->err);
+    if (d->util) {
+        rc = bdx_set_libs(d->util, libs, nlibs, max_read_window_size0);
+        if (rc != BDX_OK) return dfail(d, rc, d->util->err);
+    }
+    d->libs.assign(libs, libs + nlibs);
+    d->w0 = max_read_window_size0;
+    d->ran = false;
+    return BDX_OK;
+}
+
 int bdx_dist_get_duplicates(const bdx_dist* d, uint64_t* n_marked, uint64_t* n_groups) {
     if (!d || !d->reads) return BDX_EINVAL;
     if (!d->ran) return BDX_ESTATE;

@@ -184,6 +184,23 @@ class DistRun:
         self._chk(self.lib.bdx_dist_get_duplicates(self.h, C.byref(m), C.byref(g)), "bdx_dist_get_duplicates")
         return m.value, g.value
 
+    def insert_size_histogram(self):
+        """(hist[nlibs][ISIZE_BINS], n_over[nlibs]) of this rank's own store (bdx_dist_insert_size_histogram); the caller sums the ranks"""
+        hist = np.empty((len(self.libs), L.ISIZE_BINS), dtype=np.uint64)
+        over = np.empty(len(self.libs), dtype=np.uint64)
+        self._chk(self.lib.bdx_dist_insert_size_histogram(self.h, hist.ctypes.data_as(C.c_void_p), over.ctypes.data_as(C.c_void_p)), "bdx_dist_insert_size_histogram")
+        return hist, over
+
+    def set_libs(self, libs, max_read_window_size):
+        """bdx_dist_set_libs: the libraries and the initial window of the run that follows, on every rank alike"""
+        libs = list(libs)
+        _, arr = _c_args(self.opts, libs)
+        self._chk(self.lib.bdx_dist_set_libs(self.h, arr, len(libs), int(max_read_window_size)), "bdx_dist_set_libs")
+        self.libs = libs
+        for c in self._chrom.values():
+            c.libs = libs
+        return self
+
     def set_debug(self, name, value=1):
         """a test / measurement switch for this rank's contexts, the result context included (bdx_dist_set_debug)"""
         self.lib.bdx_dist_set_debug.argtypes = [C.c_void_p, C.c_char_p, C.c_int]

@@ -130,6 +130,7 @@ BamConfig::BamConfig(std::istream& in, int cutoff_sd) {
         }
         LibraryConfig lc;
         lc.name = lib; lc.bam_file = fmap; lc.min_mapping_quality = mqual;
+        lc.has_mean = have_mean; lc.has_std = have_std;
         lc.mean_insertsize = mean; lc.std_insertsize = stddev; lc.uppercutoff = upper; lc.lowercutoff = lower; lc.readlens = readlen;
         auto ins = tmp.insert(std::make_pair(lib, lc));
         if (!ins.second) {
@@ -166,6 +167,15 @@ BamConfig::BamConfig(std::istream& in, int cutoff_sd) {
 size_t BamConfig::library_of_readgroup(const std::string& rg) const {
     auto it = rg_lib_.find(rg);
     return it != rg_lib_.end() ? it->second : fallback_lib_;
+}
+
+void BamConfig::set_insert_sizes(const std::vector<bdx_lib>& libs, int max_read_window_size) {
+    if (libs.size() != libs_.size()) throw std::runtime_error("set_insert_sizes: another number of libraries than the configuration's");
+    for (size_t i = 0; i < libs_.size(); ++i) {
+        libs_[i].mean_insertsize = libs[i].mean_insertsize; libs_[i].std_insertsize = libs[i].std_insertsize;
+        libs_[i].uppercutoff = libs[i].uppercutoff; libs_[i].lowercutoff = libs[i].lowercutoff;
+    }
+    max_read_window_size_ = max_read_window_size;
 }
 
 std::vector<bdx_lib> BamConfig::abi_libs() const {

@@ -23,6 +23,7 @@ struct LibraryConfig {
     std::string bam_file;
     float mean_insertsize = 0, std_insertsize = 0, uppercutoff = 0, lowercutoff = 0, readlens = 0;
     int min_mapping_quality = -1;
+    bool has_mean = false, has_std = false;   // the library's line gave the field (--estimate: a library it cannot estimate needs one of them)
 };
 
 class BamConfig {
@@ -39,6 +40,9 @@ public:
     size_t fallback_library() const { return fallback_lib_; }
     const std::map<std::string, size_t>& readgroup_index() const { return rg_lib_; }
     std::vector<bdx_lib> abi_libs() const;
+    // --estimate: the four insert-size values of every library and the initial window as the run estimated them (estimate.h); everything
+    // else stays the configuration's
+    void set_insert_sizes(const std::vector<bdx_lib>& libs, int max_read_window_size);
 
 private:
     std::vector<std::string> bam_files_;

@@ -135,6 +135,23 @@ Inputs::Inputs(int argc, char** argv, const Env& env)
     libs = cfg.abi_libs();
     devices = env.gpus;
     sharded = devices.size() > 1 && opts.chr.empty();
+    if (!opts.estimate_config.empty()) {
+        estimate_config.open(opts.estimate_config.c_str());
+        if (!estimate_config.is_open()) throw std::runtime_error("unable to open --estimate-config file '" + opts.estimate_config + "' for writing");
+    }
+}
+
+void Inputs::apply_estimate(const EstimatePlan& plan) {
+    cfg.set_insert_sizes(plan.libs, plan.window);
+    libs = cfg.abi_libs();
+    if (!opts.sites.empty() && opts.sites_window < 0) sites_window = cutoff_window(cfg, "--sites");
+    if (opts.ci && opts.ci_window < 0) ci_window = cutoff_window(cfg, "--ci");
+    if (opts.mapq && opts.mapq_window < 0) mapq_window = cutoff_window(cfg, "--mapq");
+    if (estimate_config.is_open()) {
+        estimate_config << plan.config_text;
+        estimate_config.close();
+        if (estimate_config.fail()) throw std::runtime_error("unable to write --estimate-config file '" + opts.estimate_config + "'");
+    }
 }
 
 }  // namespace bdhost

@@ -1,7 +1,8 @@
 // What a run is given, settled before the GPU is touched: the BDX_* environment knobs, the options (or the -R cache's), the
-// configuration, and the opened or parsed option inputs (--vcf, --exclude, --sites, --ci, --mapq).  bdx-dump-reads shares the two helpers.
+// configuration, and the opened or parsed option inputs (--vcf, --exclude, --sites, --ci, --mapq, --estimate-config).  bdx-dump-reads shares the two helpers.
 #pragma once
 #include <cstdint>
+#include <fstream>
 #include <memory>
 #include <string>
 #include <vector>
@@ -9,6 +10,7 @@
 #include "bdx.h"
 #include "cache.h"
 #include "config.h"
+#include "estimate.h"
 #include "exclude.h"
 #include "options.h"
 #include "sites.h"
@@ -55,7 +57,7 @@ Env read_env();
 
 struct Inputs {
     // Fails in this order, each before the GPU is touched: option parsing, -R / config, (no BAM files: see no_bams), --vcf open, --exclude
-    // parse, --sites-vcf open and --sites parse, --ci window, --mapq window.
+    // parse, --sites-vcf open and --sites parse, --ci window, --mapq window, --estimate-config open.
     Inputs(int argc, char** argv, const Env& env);
     Inputs(const Inputs&) = delete;
     Inputs& operator=(const Inputs&) = delete;
@@ -79,6 +81,12 @@ struct Inputs {
     std::vector<bdx_lib> libs;
     std::vector<int> devices;    // BDX_GPUS
     bool sharded = false;        // ONE whole-genome run with the chromosomes spread over several GPUs
+    std::ofstream estimate_config;   // --estimate-config: opened at once -- an unwritable path fails here
+
+    // --estimate, the one change a run makes to its inputs (between "fed" and "run"): the estimated values replace the configuration's in
+    // cfg and libs, so that everything behind the feed prints and uses the run's libraries; the windows of --sites / --ci / --mapq that
+    // the command line did not give are computed again from them; --estimate-config is written and closed
+    void apply_estimate(const EstimatePlan& plan);
 };
 
 // CPUs this process can use: hardware threads, capped by the cgroup v2 / v1 CPU quota if one is set

@@ -62,7 +62,7 @@ void leave(const Inputs& in, const Env& env, const Session& s, Support& sup) {
 int run(int argc, char** argv, const Env& env) {
     Session s;   // (outside the try: whatever ends the run, the session goes behind it, in its destructor's one order)
     try {
-        const Inputs in(argc, argv, env);
+        Inputs in(argc, argv, env);   // (--estimate replaces its libraries between "fed" and "run": Inputs::apply_estimate)
         if (in.no_bams) {
             std::cout << "Error: no bams files in config file!\n";
             return 1;

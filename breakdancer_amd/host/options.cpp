@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
+#include <string>
 
 namespace bdhost {
 
@@ -72,7 +73,15 @@ void print_usage(const bdx_opts& o) {
     fprintf(stderr, "       --depth        add RCI / RCF / RDR to every sample of a --vcf / --sites-vcf record: passing read starts inside the record, in its flanks, and their ratio\n");
     fprintf(stderr, "       --depth-flank INT  the width of either flank of --depth [%d]\n", Options::kDepthFlankDefault);
     fprintf(stderr, "       --mark-dup     flag duplicate read pairs (same library, positions and strands of both mates) on the GPU; they are ignored like reads with SAM flag 0x400\n");
+    fprintf(stderr, "       --estimate     take mean, std and the cutoffs of every library from all read pairs the run holds (on the GPU), not from the configuration\n");
+    fprintf(stderr, "       --estimate-config FILE write the configuration with the estimated values to FILE (with --estimate)\n");
     fprintf(stderr, "\n");
+}
+
+// (a stated limit: the cache's pass-1 statistics belong to cutoffs the -R run would have to estimate again)
+[[noreturn]] void estimate_with_cache() {
+    fprintf(stderr, "--estimate does not go with -C or -R: the cache's pass-1 statistics belong to the cutoffs of the run that wrote it.\n");
+    exit(1);
 }
 
 }  // namespace
@@ -81,13 +90,14 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
     // (the reference's letters parse exactly as with getopt; the long options are this tool's own)
-    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank, kMapq, kMapqWindow };
+    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank, kMapq, kMapqWindow, kEstimate, kEstimateConfig };
     static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude},
                                          {"sites", required_argument, nullptr, kSites}, {"sites-vcf", required_argument, nullptr, kSitesVcf},
                                          {"sites-window", required_argument, nullptr, kSitesWindow}, {"mark-dup", no_argument, nullptr, kMarkDup},
                                          {"ci", no_argument, nullptr, kCi}, {"ci-window", required_argument, nullptr, kCiWindow},
                                          {"depth", no_argument, nullptr, kDepth}, {"depth-flank", required_argument, nullptr, kDepthFlank},
                                          {"mapq", no_argument, nullptr, kMapq}, {"mapq-window", required_argument, nullptr, kMapqWindow},
+                                         {"estimate", no_argument, nullptr, kEstimate}, {"estimate-config", required_argument, nullptr, kEstimateConfig},
                                          {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
@@ -123,6 +133,14 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
             mapq = true;
             continue;
         }
+        if (c == kEstimate) {
+            estimate = true;
+            continue;
+        }
+        if (c == kEstimateConfig) {
+            estimate_config = optarg;
+            continue;
+        }
         if (c == kDepthFlank) {
             char* end = nullptr;
             const long v = strtol(optarg, &end, 10);
@@ -156,8 +174,14 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
             case kString: this->*(row->str) = optarg; break;
         }
         if (c == 'R') {  // a run from a pass-1 cache takes its options from the cache (ConfigLoader.cpp:19-23)
-            if (argc != 3) throw std::runtime_error("When using -R, no other options are allowed");
-            return;
+            if (argc == 3) return;
+            // other options beside -R: an error either way.  The same parser goes on over the rest of the line, quietly, only to see
+            // whether --estimate is among them: it has a message of its own
+            opterr = 0;
+            while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0)
+                if (c == kEstimate || c == kEstimateConfig) estimate = true;
+            if (estimate) estimate_with_cache();
+            throw std::runtime_error("When using -R, no other options are allowed");
         }
     }
     if (sites.empty() != sites_vcf.empty() || (sites.empty() && sites_window >= 0)) {
@@ -176,6 +200,11 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
         fprintf(stderr, "--mapq needs --vcf FILE or --sites-vcf FILE to write to (and --mapq-window goes with --mapq).\n");
         exit(1);
     }
+    if (!estimate && !estimate_config.empty()) {
+        fprintf(stderr, "--estimate-config FILE goes with --estimate.\n");
+        exit(1);
+    }
+    if (estimate && !cache_file.empty()) estimate_with_cache();
     o.chr_restricted = chr.empty() ? 0 : 1;
     if (optind == argc) {
         print_usage(o);

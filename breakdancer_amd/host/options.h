@@ -1,6 +1,6 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
 // (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf, --exclude, --sites / --sites-vcf /
-// --sites-window, --mark-dup, --ci / --ci-window, --depth / --depth-flank and --mapq / --mapq-window.
+// --sites-window, --mark-dup, --ci / --ci-window, --depth / --depth-flank, --mapq / --mapq-window and --estimate / --estimate-config.
 #pragma once
 #include <string>
 #include <vector>
@@ -28,6 +28,8 @@ struct Options {
     int depth_flank = -1;        // --depth-flank: the width of either flank (-1: kDepthFlankDefault)
     bool mapq = false;           // --mapq: SQ* / LQ* of every --vcf / --sites-vcf record: mapping quality at either end (bdx_site_end_quality)
     int mapq_window = -1;        // --mapq-window: how far from a breakpoint a read of --mapq may start (-1: from the libraries' cutoffs)
+    bool estimate = false;       // --estimate: mean, std and cutoffs of every library from all pairs the run holds (bdx_insert_size_histogram, estimate.h)
+    std::string estimate_config; // --estimate-config: the configuration with the estimated values, written for later runs (needs --estimate)
     static constexpr int kDepthFlankDefault = 1000;
     int flank() const { return depth_flank > 0 ? depth_flank : kDepthFlankDefault; }
     bdx_opts o;                  // numeric options in the C-ABI layout

@@ -87,6 +87,16 @@ struct GpuSink : BatchSink {
     void submit(size_t n) override { check(s.ctx, bdx_submit_batch(s.ctx, n), "bdx_submit_batch"); }
 };
 
+// --estimate: from the summed histograms to the run's libraries in `in`; returns them for bdx_set_libs / bdx_dist_set_libs
+EstimatePlan estimate_from(Inputs& in, const Env& env, const std::vector<uint64_t>& hist, const std::vector<uint64_t>& n_over, Clock::time_point t0) {
+    EstimatePlan plan = plan_estimate(in.cfg, in.config_text, in.opts.o.cut_sd, hist.data(), n_over.data());
+    for (const std::string& w : plan.warnings) fprintf(stderr, "WARNING: %s\n", w.c_str());
+    if (!plan.fatal.empty()) throw std::runtime_error(plan.fatal);
+    in.apply_estimate(plan);
+    if (env.timing) fprintf(stderr, "[bdx timing] --estimate: %s; window %d; %.4f s\n", estimate_summary(in.cfg, plan).c_str(), plan.window, secs(t0, now()));
+    return plan;
+}
+
 }  // namespace
 
 Session::~Session() {
@@ -103,7 +113,7 @@ void Session::start_trimmer() {
     trimmer = std::thread([tc] { (void)bdx_trim_results(tc); });
 }
 
-Fed feed_and_run_single(const Inputs& in, const Env& env, Session& s, Clock::time_point t_start) {
+Fed feed_and_run_single(Inputs& in, const Env& env, Session& s, Clock::time_point t_start) {
     const Options& opts = in.opts;
     Fed fed;
     // the GPU context (HIP runtime start-up, ~0.1 s) comes up on a helper thread while the BAMs are decoded
@@ -144,6 +154,14 @@ Fed feed_and_run_single(const Inputs& in, const Env& env, Session& s, Clock::tim
     fed.t_decoded = now();
     if (in.want_dumps) check(s.ctx, bdx_set_collect_support(s.ctx, 1), "bdx_set_collect_support");
     if (in.restored) check(s.ctx, bdx_set_pass1_statistics(s.ctx, in.cache.counters.data(), in.cache.covered_ref_len), "bdx_set_pass1_statistics");
+    if (opts.estimate) {
+        const auto te = now();
+        const size_t nlibs = in.libs.size();
+        std::vector<uint64_t> hist(nlibs * (size_t)BDX_ISIZE_BINS), n_over(nlibs);
+        check(s.ctx, bdx_insert_size_histogram(s.ctx, hist.data(), n_over.data()), "bdx_insert_size_histogram");
+        const EstimatePlan plan = estimate_from(in, env, hist, n_over, te);
+        check(s.ctx, bdx_set_libs(s.ctx, plan.libs.data(), (int)plan.libs.size(), plan.window), "bdx_set_libs");
+    }
     check(s.ctx, bdx_run(s.ctx), "bdx_run");
     fed.t_ran = now();
     return fed;
@@ -151,7 +169,7 @@ Fed feed_and_run_single(const Inputs& in, const Env& env, Session& s, Clock::tim
 
 // BDX_GPUS=N (devices 0..N-1) or a list "0,1,2,3": ONE whole-genome run with the chromosomes spread over several
 // GPUs (bdx_dist_*: one rank per device, here as threads of this process) -- same output as on one GPU
-Fed feed_and_run_sharded(const Inputs& in, const Env& env, Session& s, Clock::time_point t_start) {
+Fed feed_and_run_sharded(Inputs& in, const Env& env, Session& s, Clock::time_point t_start) {
     const Options& opts = in.opts;
     Fed fed;
     if (in.restored) throw std::runtime_error("-R is not supported with BDX_GPUS");
@@ -203,6 +221,20 @@ Fed feed_and_run_sharded(const Inputs& in, const Env& env, Session& s, Clock::ti
     if (env.timing)
         fprintf(stderr, "[bdx timing] sharded run: ranks created %.3f s after start, in %.3f s; reads on the ranks %.3f s later; prepared in %.3f s\n",
                 secs(t_start, t_create), secs(t_create, t_created), secs(t_created, t_fed), secs(t_fed, fed.t_decoded));
+    if (opts.estimate) {   // (the ranks are threads of this process: their histograms are summed here, no collective)
+        const auto te = now();
+        std::vector<uint64_t> hist((size_t)nlibs * BDX_ISIZE_BINS, 0), n_over(nlibs, 0), h(hist.size()), o(nlibs);
+        for (bdx_dist* r : s.ranks) {
+            if (bdx_dist_insert_size_histogram(r, h.data(), o.data()) != BDX_OK)
+                throw std::runtime_error(std::string("bdx_dist_insert_size_histogram: ") + bdx_dist_last_error(r));
+            for (size_t i = 0; i < hist.size(); ++i) hist[i] += h[i];
+            for (int i = 0; i < nlibs; ++i) n_over[i] += o[i];
+        }
+        const EstimatePlan plan = estimate_from(in, env, hist, n_over, te);
+        for (bdx_dist* r : s.ranks)
+            if (bdx_dist_set_libs(r, plan.libs.data(), nlibs, plan.window) != BDX_OK)
+                throw std::runtime_error(std::string("bdx_dist_set_libs: ") + bdx_dist_last_error(r));
+    }
     std::vector<int> rcs(world, BDX_OK);
     std::vector<std::thread> th;
     for (int r = 0; r < world; ++r) th.emplace_back([&, r] { rcs[r] = bdx_dist_run(s.ranks[r]); });
@@ -386,10 +418,10 @@ void write_vcfs(const Inputs& in, Genotypes& gt) {
     const VcfDepth* depth = opts.depth ? &depth_info : nullptr;
     const VcfMapq mapq_header{in.mapq_window};
     const VcfMapq* mapq = opts.mapq ? &mapq_header : nullptr;
-    if (in.vcf) in.vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.vcf_rows), opts.exclude, nullptr, opts.mark_dup, ci, depth, mapq);
+    if (in.vcf) in.vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.vcf_rows), opts.exclude, nullptr, opts.mark_dup, ci, depth, mapq, opts.estimate);
     if (in.sites_vcf) {
         const VcfSites info{opts.sites, in.sites_window};
-        in.sites_vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.site_rows), opts.exclude, &info, opts.mark_dup, ci, depth, mapq);
+        in.sites_vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.site_rows), opts.exclude, &info, opts.mark_dup, ci, depth, mapq, opts.estimate);
     }
 }
 

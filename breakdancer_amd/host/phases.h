@@ -1,5 +1,5 @@
 // The phases of one breakdancer-max run behind its inputs (inputs.h), in the order main.cpp's run() calls them, and the one owner of
-// what the run holds on the GPU.  Each phase sees its inputs by const reference and returns what it produced by value.
+// what the run holds on the GPU.  Each phase sees its inputs by const reference (but see --estimate below) and returns what it produced by value.
 #pragma once
 #include <chrono>
 #include <future>
@@ -46,8 +46,10 @@ struct Fed {
     bool device_decoded = false;       // BGZF inflate and record decode ran on the GPU
     Clock::time_point t_decoded, t_ran;
 };
-Fed feed_and_run_single(const Inputs& in, const Env& env, Session& s, Clock::time_point t_start);
-Fed feed_and_run_sharded(const Inputs& in, const Env& env, Session& s, Clock::time_point t_start);
+// (--estimate: between "fed" and "run" the histograms of the store are taken -- every rank's summed on the host --, the libraries estimated,
+// in.apply_estimate called and the contexts given the run's libraries: bdx_set_libs / bdx_dist_set_libs.  The only phases that change `in`)
+Fed feed_and_run_single(Inputs& in, const Env& env, Session& s, Clock::time_point t_start);
+Fed feed_and_run_sharded(Inputs& in, const Env& env, Session& s, Clock::time_point t_start);
 
 struct Statistics {
     bdx_summary sum{};

@@ -80,7 +80,7 @@ VcfWriter::~VcfWriter() {
 
 void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                       const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude,
-                      const VcfSites* sites, bool mark_dup, const VcfCi* ci, const VcfDepth* depth, const VcfMapq* mapq) {
+                      const VcfSites* sites, bool mark_dup, const VcfCi* ci, const VcfDepth* depth, const VcfMapq* mapq, bool estimate) {
     if (!f_) throw std::runtime_error("VCF output file '" + path_ + "' is already closed");
     FILE* f = f_;
     fprintf(f, "##fileformat=VCFv4.2\n##source=breakdancer-max-mi355x\n##command=");
@@ -89,6 +89,7 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
     if (!exclude.empty()) fprintf(f, "##exclude=%s\n", exclude.c_str());
     if (sites) fprintf(f, "##sites=%s\n##sites_window=%d\n", sites->file.c_str(), sites->window);
     if (mark_dup) fprintf(f, "##mark_dup=1\n");
+    if (estimate) fprintf(f, "##estimate=1\n");
     if (ci) fprintf(f, "##ci_window=%d\n", ci->window);
     if (depth) fprintf(f, "##depth_flank=%d\n", depth->flank);
     if (mapq) fprintf(f, "##mapq_window=%d\n", mapq->window);

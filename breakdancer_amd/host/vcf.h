@@ -115,11 +115,12 @@ public:
     // header + records, sorted by (chr1, pos1) with ties in row order; `contigs` are the reference sequences (names are also the
     // records' CHROM / CHR2 values); exclude: the --exclude file of the run ("": none) for the ##exclude= line; sites: non-null for a
     // --sites-vcf output; mark_dup: the run marked duplicates (--mark-dup), for the ##mark_dup=1 line; ci: non-null for a run
-    // with --ci, depth: for a run with --depth, mapq: for a run with --mapq; the file is closed afterwards
+    // with --ci, depth: for a run with --depth, mapq: for a run with --mapq; estimate: the run took its
+    // libraries from its own pairs (--estimate), for the ##estimate=1 line; the file is closed afterwards
     void write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude = "",
                const VcfSites* sites = nullptr, bool mark_dup = false, const VcfCi* ci = nullptr,
-               const VcfDepth* depth = nullptr, const VcfMapq* mapq = nullptr);
+               const VcfDepth* depth = nullptr, const VcfMapq* mapq = nullptr, bool estimate = false);
 
 private:
     std::string path_;

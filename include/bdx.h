@@ -629,6 +629,46 @@ int bdx_dist_get_duplicates(const bdx_dist* d, uint64_t* n_marked, uint64_t* n_g
 int bdx_mark_duplicates(int device, const int32_t* tid, const int32_t* pos, const int32_t* mtid, const int32_t* mpos, const uint16_t* flag,
                         const uint8_t* lib, const uint64_t* name_key, size_t n, uint8_t* mask, uint64_t* n_groups);
 
+/* Insert-size cutoffs from ALL pairs the store holds: no counterpart in the reference, whose bam2cfg takes them from the first ~10,000
+ * pairs of a file (perl/bam2cfg.pl:153-197) and whose breakdancer-max only ever reads them from the configuration (the CLI's --estimate).
+ * The rule, written down here once:
+ *   OBSERVATION  record i of the resident store is an observation x = isize[i] of its library (lib; an index out of range is library 0; a
+ *                context with one library never reads the column) when flag & 0x1 (paired) is set, flag & 0x400, 0x4 and 0x8 are clear (not
+ *                a duplicate, both ends mapped), mtid == tid, flag & 0x2 (proper pair) is set, isize >= 0 -- zero counts; the upper mate's
+ *                negative isize does not, so each pair is counted once -- and its quality (the mapq column) is GREATER than the library's
+ *                minimum, resolved as K1 resolves it (bdx_lib.min_mapping_quality, or opts.min_map_qual when that is negative) and compared
+ *                in int.  This is bam2cfg's "flag 18 or 20 and isize >= 0", restated on what the record itself carries.
+ *   ROUTING      x < BDX_ISIZE_BINS is counted in hist[lib][x]; x >= BDX_ISIZE_BINS only in n_over[lib].
+ *   ESTIMATE     of one library from its histogram, bam2cfg's arithmetic: n, mean_all, sd_all over all observations (n - 1); every x with
+ *                !(x > mean_all + 5 sd_all) is kept; n_kept, mean, sd over the kept ones; sd_minus the deviation around mean over the kept
+ *                x <= mean (n_minus of them, divided by n_minus - 1), sd_plus over the kept x > mean (n_plus).  All sums in double, bin by
+ *                bin in ascending x, as count * x and count * (x - mean)^2; a deviation over fewer than two observations is 0.
+ *                valid = n_kept >= 100 && n_minus >= 2 && n_plus >= 2 (100 is bam2cfg's own figure).
+ *   bdx_insert_size_histogram  KH (csrc/kh_insert_hist.hip) over the records the store holds by whatever way they came in (pushed, staged,
+ *                adopted, decoded, merged), on the context's stream and behind pending batch copies; before or after a run (it needs no
+ *                class bytes; after a run with bdx_set_mark_duplicates the marks are in the flag column and count).  All counts are integers:
+ *                the result is exact.  hist[nlibs][BDX_ISIZE_BINS] and n_over[nlibs] are overwritten.  BDX_EINVAL for a null pointer,
+ *                BDX_ESTATE while a sizing pass is in flight
+ *   bdx_dist_insert_size_histogram  the same over the rank's own store; the caller sums the ranks
+ *   bdx_estimate_insert_size   host only, no GPU: the ESTIMATE of one library's hist[BDX_ISIZE_BINS].  BDX_EINVAL for a null pointer
+ *   bdx_set_libs   replaces the context's libraries and max_read_window_size0 (what bdx_create was given) for the runs that follow: the
+ *                host copy and the device tables in stream order; a live or finished pass 1 is invalidated, so the next bdx_run classifies
+ *                from the first tile (the route a grown store takes), and the query calls refuse until then.  The store, and the marks
+ *                bdx_set_mark_duplicates made on it, stay.  nlibs must be the context's and every bam_index the one given at creation (the
+ *                counter keys cannot move): BDX_EINVAL otherwise; BDX_ESTATE while a sizing pass is in flight
+ *   bdx_dist_set_libs   the same for the rank's contexts; on every rank alike, before bdx_dist_run */
+#define BDX_ISIZE_BINS 32768   /* published for the tests (they aim at its edges) */
+typedef struct bdx_insert_estimate {
+    double mean_all, sd_all, mean, sd, sd_minus, sd_plus;
+    uint64_t n, n_kept, n_minus, n_plus;
+    int32_t valid;
+} bdx_insert_estimate;
+int bdx_insert_size_histogram(bdx_ctx* ctx, uint64_t* hist /*[nlibs][BDX_ISIZE_BINS]*/, uint64_t* n_over /*[nlibs]*/);
+int bdx_dist_insert_size_histogram(bdx_dist* d, uint64_t* hist, uint64_t* n_over);
+int bdx_estimate_insert_size(const uint64_t* hist /*[BDX_ISIZE_BINS]*/, bdx_insert_estimate* out);
+int bdx_set_libs(bdx_ctx* ctx, const bdx_lib* libs, int nlibs, int max_read_window_size0);
+int bdx_dist_set_libs(bdx_dist* d, const bdx_lib* libs, int nlibs, int max_read_window_size0);
+
 /* device the context is bound to and the HIP stream it launches on (as void*), for callers that time it */
 int bdx_device(const bdx_ctx* ctx);
 void* bdx_stream(const bdx_ctx* ctx);
