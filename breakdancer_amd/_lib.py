@@ -59,7 +59,8 @@ EXPORTS = ["bdx_opts_default", "bdx_create", "bdx_destroy", "bdx_strerror", "bdx
            "bdx_bamdec_finish", "bdx_bamdec_rearm", "bdx_bamdec_fetch", "bdx_bamdec_stats", "bdx_bamdec_host_ms", "bdx_merge_decoded", "bdx_append_decoded", "bdx_inflate_blocks", "bdx_insert_size_stats",
            "bdx_count_junction_pairs", "bdx_bamdec_set_exclude", "bdx_bamdec_excluded", "bdx_exclude_mask", "bdx_count_site_pairs", "bdx_site_breakpoint_bounds", "bdx_count_interval_reads", "bdx_site_end_quality",
            "bdx_set_mark_duplicates", "bdx_get_duplicates", "bdx_dist_set_mark_duplicates", "bdx_dist_get_duplicates", "bdx_mark_duplicates",
-           "bdx_insert_size_histogram", "bdx_dist_insert_size_histogram", "bdx_estimate_insert_size", "bdx_set_libs", "bdx_dist_set_libs"]
+           "bdx_insert_size_histogram", "bdx_dist_insert_size_histogram", "bdx_estimate_insert_size", "bdx_set_libs", "bdx_dist_set_libs",
+           "bdx_set_insert_null", "bdx_window_insert_shift", "bdx_insert_shift_score"]
 
 # kDupT (csrc/bdx_dev.h): KD compares the records of a run directly when the run has at most this many, longer runs go through its table
 DUP_T = 64
@@ -77,6 +78,11 @@ INTERVAL_DTYPE = np.dtype([("tid", "<i4"), ("beg", "<i4"), ("end", "<i4")])
 DEPTH_CHUNK = 2048
 # BDX_ISIZE_BINS (include/bdx.h): the bins per library of bdx_insert_size_histogram; larger insert sizes only count in n_over
 ISIZE_BINS = 32768
+# BDX_MINI_CAP (include/bdx.h): the observations of one window, all libraries together, that bdx_window_insert_shift ranks; more saturate it
+MINI_CAP = 4096
+# bdx_insert_shift: one library's row of one window: observations, those beyond the bins, saturated, pad, the sum of the observations, and
+# n N times the one-sided Kolmogorov-Smirnov distances against the null
+INSERT_SHIFT_DTYPE = np.dtype([("n", "<u4"), ("n_over", "<u4"), ("saturated", "<u4"), ("pad", "<u4"), ("sum", "<u8"), ("t_plus", "<i8"), ("t_minus", "<i8")])
 
 
 class bdx_insert_estimate(C.Structure):
@@ -155,5 +161,8 @@ def load():
     L.bdx_estimate_insert_size.argtypes = [vp, C.POINTER(bdx_insert_estimate)]
     L.bdx_set_libs.argtypes = [vp, C.POINTER(bdx_lib), C.c_int, C.c_int]
     L.bdx_dist_set_libs.argtypes = [vp, C.POINTER(bdx_lib), C.c_int, C.c_int]
+    L.bdx_set_insert_null.argtypes = [vp, vp]
+    L.bdx_window_insert_shift.argtypes = [vp, vp, C.c_size_t, vp]
+    L.bdx_insert_shift_score.argtypes = [vp, C.c_uint64, vp, vp]
     _lib = L
     return L

@@ -387,6 +387,34 @@ class BreakDancer:
         self._chk(self.lib.bdx_count_interval_reads(self.h, p(iv), len(iv), int(bool(by_library)), p(out)), "bdx_count_interval_reads")
         return out
 
+    def set_insert_null(self, hist):
+        """the null distribution of window_insert_shift (bdx_set_insert_null): hist[nlibs][ISIZE_BINS] as insert_size_histogram gives it
+        (ranks summed by the caller), kept on the device as cumulative counts until the next call; None frees it"""
+        if hist is None:
+            self._chk(self.lib.bdx_set_insert_null(self.h, None), "bdx_set_insert_null")
+            return self
+        h = np.ascontiguousarray(hist, dtype=np.uint64)
+        if h.shape != (self.nlibs, L.ISIZE_BINS):
+            raise ValueError("hist is not [nlibs][ISIZE_BINS]")
+        self._chk(self.lib.bdx_set_insert_null(self.h, h.ctypes.data_as(C.c_void_p)), "bdx_set_insert_null")
+        return self
+
+    def window_insert_shift(self, intervals):
+        """Insert-size shift of the pairs of the last run that start inside given windows (bdx_window_insert_shift; the rule is in
+        include/bdx.h): `intervals` as for count_interval_reads.  A passing record of a same-chromosome class whose only anomaly can be its
+        insert size, the lower mate of its pair, is an observation |isize| of its library.  Returns an (n, nlibs) array of
+        _lib.INSERT_SHIFT_DTYPE: n, n_over, saturated, sum, and t_plus / t_minus = n N times the one-sided Kolmogorov-Smirnov distances
+        against the null set with set_insert_null; a window of more than _lib.MINI_CAP observations is saturated and has no t."""
+        if isinstance(intervals, np.ndarray) and intervals.dtype == L.INTERVAL_DTYPE:
+            iv = np.ascontiguousarray(intervals)
+        else:
+            rows = [tuple(int(v) for v in r) for r in intervals]
+            iv = np.array(rows, dtype=L.INTERVAL_DTYPE) if rows else np.zeros(0, dtype=L.INTERVAL_DTYPE)
+        out = np.zeros((len(iv), self.nlibs), dtype=L.INSERT_SHIFT_DTYPE)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.bdx_window_insert_shift(self.h, p(iv), len(iv), p(out)), "bdx_window_insert_shift")
+        return out
+
     def set_stage_timing(self, on=True):
         """HIP events between the stages (compact / regions / join timings); costs a few microseconds per event."""
         self._chk(self.lib.bdx_set_stage_timing(self.h, int(on)), "bdx_set_stage_timing")
@@ -444,6 +472,18 @@ def estimate_insert_size(hist):
     if rc != 0:
         raise BdxError("bdx_estimate_insert_size: %s" % lib.bdx_strerror(rc).decode())
     return {k: getattr(out, k) for k, _ in L.bdx_insert_estimate._fields_}
+
+
+def insert_shift_score(row, N):
+    """bdx_insert_shift_score: (score, D) of one row of window_insert_shift against a null of N observations (host only, no GPU)"""
+    lib = L.load()
+    r = np.zeros(1, dtype=L.INSERT_SHIFT_DTYPE)
+    r[0] = row
+    score, d = C.c_double(), C.c_double()
+    rc = lib.bdx_insert_shift_score(r.ctypes.data_as(C.c_void_p), int(N), C.byref(score), C.byref(d))
+    if rc != 0:
+        raise BdxError("bdx_insert_shift_score: %s" % lib.bdx_strerror(rc).decode())
+    return score.value, d.value
 
 
 def mark_duplicates(tid, pos, mtid, mpos, flag, lib, name_key, device=0):

@@ -30,6 +30,7 @@
 #include "bdx_walk.h"
 #include "bdx_bam_dev.h"
 #include "bdx_estimate.h"
+#include "bdx_mini.h"
 
 using namespace bdx;
 
@@ -97,7 +98,7 @@ struct bdx_ctx {
                                       // in its high half (FinalizeParams::count_host; read by wait_count)
     uint32_t seq = 0;
     // test / measurement switches (bdx_set_debug): all off by default
-    int dbg_no_stash = 0, dbg_max_chunks = 0, dbg_ins_plain = 0, dbg_gather_walk = 0, dbg_regions_copy = 0, dbg_asm_plain = 0, dbg_depth_plain = 0;
+    int dbg_no_stash = 0, dbg_max_chunks = 0, dbg_ins_plain = 0, dbg_gather_walk = 0, dbg_regions_copy = 0, dbg_asm_plain = 0, dbg_depth_plain = 0, dbg_mini_staged = 0;
     uint32_t lb_seq = 0;              // launches of look-back scans so far: every launch stamps its words with its own number (bdx_scan.h)
     float k1_ms_last = 0;
     bool k1_timed = false;
@@ -202,6 +203,8 @@ struct bdx_ctx {
     size_t cls_n = (size_t)-1;        // reads the class bytes in b_cls describe (set by a completed pass 1; -1: none)
     DevBuf b_qtab;                    // bdx_count_interval_reads' table of one call (scratch: rebuilt by every call)
     DevBuf b_hist;                    // bdx_insert_size_histogram's table of one call: [nlibs][BDX_ISIZE_BINS] counts and behind them n_over[nlibs]
+    DevBuf b_null;                    // bdx_set_insert_null's cumulative table [nlibs][BDX_ISIZE_BINS], kept until it is replaced or freed
+    bool null_set = false;
     DevBuf b_qin, b_qout;             // a call's uploads (queries or sites, and behind them KI's table of the libraries' U, or KM's of their minima and its ends) and its results.
                                       // One pair serves the three: every call ends with hipStreamSynchronize, so none can see another's data
     // ---- bdx_set_mark_duplicates ----
@@ -2184,7 +2187,7 @@ int bdx_set_debug(bdx_ctx* c, const char* name, int value) {
     if (!c || !name) return BDX_EINVAL;
     struct { const char* n; int* p; } ints[] = {{"no_stash", &c->dbg_no_stash}, {"max_chunks", &c->dbg_max_chunks}, {"spec_test", &c->spec_test},
                                                  {"big_walk", &c->big_walk_mode}, {"ins_plain", &c->dbg_ins_plain}, {"regions_copy", &c->dbg_regions_copy},
-                                                 {"asm_plain", &c->dbg_asm_plain}, {"gather_walk", &c->dbg_gather_walk}, {"depth_plain", &c->dbg_depth_plain}};
+                                                 {"asm_plain", &c->dbg_asm_plain}, {"gather_walk", &c->dbg_gather_walk}, {"depth_plain", &c->dbg_depth_plain}, {"mini_staged", &c->dbg_mini_staged}};
     for (auto& e : ints)
         if (!strcmp(name, e.n)) { *e.p = value; return BDX_OK; }
     if (!strcmp(name, "bucketed_join")) { c->bucketed_join = value != 0; return BDX_OK; }
@@ -2472,6 +2475,59 @@ int bdx_set_libs(bdx_ctx* c, const bdx_lib* libs, int nlibs, int max_read_window
     c->k1_done = 0;
     c->ran = false;
     c->cls_n = (size_t)-1;
+    return BDX_OK;
+}
+
+// ---- --mini: the null's cumulative table and the windows' insert-size shift (KW, km_mini.hip); the score is bdx_mini.h's ----
+
+int bdx_set_insert_null(bdx_ctx* c, const uint64_t* hist) {
+    if (!c) return BDX_EINVAL;
+    NOT_WHILE_SIZING(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!hist) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->b_null.release();
+        c->null_set = false;
+        return BDX_OK;
+    }
+    const size_t nh = (size_t)c->nlibs * BDX_ISIZE_BINS;
+    std::vector<uint64_t> cum(nh);
+    for (int l = 0; l < c->nlibs; ++l) {
+        uint64_t run = 0;
+        for (size_t x = 0; x < BDX_ISIZE_BINS; ++x) {
+            const uint64_t h = hist[(size_t)l * BDX_ISIZE_BINS + x];
+            if (h >= ((uint64_t)1 << 51) || (run += h) >= ((uint64_t)1 << 51))
+                return fail(c, BDX_ELIMIT, "library " + std::to_string(l) + ": the null holds 2^51 observations or more");
+            cum[(size_t)l * BDX_ISIZE_BINS + x] = run;
+        }
+    }
+    HIPCHK(c, c->b_null.ensure(nh * 8));
+    HIPCHK(c, hipMemcpyAsync(c->b_null.p, cum.data(), nh * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the vector goes with this call)
+    c->null_set = true;
+    return BDX_OK;
+}
+
+int bdx_window_insert_shift(bdx_ctx* c, const bdx_interval* iv, size_t n, bdx_insert_shift* out) {
+    bool none;
+    BDX_TRY(check_query_state(c, n, &none));
+    if (!c->null_set) return fail(c, BDX_ESTATE, "no null distribution is set (bdx_set_insert_null)");
+    if (none) return BDX_OK;
+    if (!iv || !out) return fail(c, BDX_EINVAL, "null array");
+    if (n > ((size_t)1 << 31)) return fail(c, BDX_ELIMIT, "more than 2^31 intervals in one call");
+    for (size_t i = 0; i < n; ++i)
+        if (iv[i].tid < 0 || iv[i].beg < 0 || iv[i].end < iv[i].beg)
+            return fail(c, BDX_EINVAL, "interval " + std::to_string(i) + ": tid < 0, beg < 0 or end < beg");
+    const int nlibs = c->nlibs;
+    return run_query(c, {{iv, n * sizeof(bdx_interval)}}, out, n * (size_t)nlibs * sizeof(bdx_insert_shift), [&](const char* in, void* results, hipStream_t s) {
+        launch_kw(KwParams{store_view(c), nlibs > 1 ? c->d.lib : nullptr, (const KrInterval*)in, (uint32_t)n, nlibs, c->b_null.as<uint64_t>(),
+                           c->dbg_mini_staged ? 1 : 0, (KwShift*)results}, s);
+    });
+}
+
+int bdx_insert_shift_score(const bdx_insert_shift* row, uint64_t N, double* score, double* D) {
+    if (!row) return BDX_EINVAL;
+    insert_shift_score(*row, N, score, D);
     return BDX_OK;
 }
 

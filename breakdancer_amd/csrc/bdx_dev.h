@@ -295,6 +295,24 @@ struct KhParams {
 };
 void launch_kh(const KhParams& p, hipStream_t s);
 
+// KW (km_mini.hip): insert-size shift of the pairs that start inside given windows, per window and library (bdx_window_insert_shift)
+struct KwShift {                        // = bdx_insert_shift (include/bdx.h)
+    uint32_t n, n_over, saturated, pad;
+    uint64_t sum;
+    int64_t t_plus, t_minus;
+};
+struct KwParams {
+    StoreView st;
+    const uint8_t* lib;                 // library column; read only when nlibs > 1
+    const KrInterval* iv;
+    uint32_t nq;
+    int nlibs;                          // 1..255
+    const uint64_t* ctab;               // [nlibs][BDX_ISIZE_BINS]: the null's cumulative counts C_L(x); N_L is the row's last entry (< 2^51)
+    int staged;                         // "mini_staged": the all-pairs route at every size
+    KwShift* out;                       // [nq][nlibs]
+};
+void launch_kw(const KwParams& p, hipStream_t s);
+
 // KD (kd_markdup.hip): duplicate marking over the resident store (bdx_set_mark_duplicates, bdx_mark_duplicates)
 constexpr int kDupT = 64;               // neighbours a record looks at each way; runs of more records go through the table
 struct KdCounts {

@@ -88,10 +88,10 @@ def _c_args(opts, libs):
 class DistRun:
     """one rank of a chromosome-sharded run"""
 
-    def __init__(self, handle, opts, libs, nbams):
+    def __init__(self, handle, opts, libs, nbams, ntids=None):
         self.lib = _lib()
         self.h = C.c_void_p(handle)
-        self.opts, self.libs, self.nbams = opts, list(libs), nbams
+        self.opts, self.libs, self.nbams, self.ntids = opts, list(libs), nbams, ntids
         self.rank = self.lib.bdx_dist_rank(self.h)
         self.world = self.lib.bdx_dist_world(self.h)
         self._chrom = {}
@@ -106,7 +106,7 @@ class DistRun:
         rc = lib.bdx_dist_create(C.byref(h), C.byref(co), arr, len(libs), nbams, ntids, max_read_window_size, device, rank, world, buf)
         if rc != 0:
             raise BdxError("bdx_dist_create: %s" % lib.bdx_strerror(rc).decode())
-        return cls(h.value, opts, libs, nbams)
+        return cls(h.value, opts, libs, nbams, ntids)
 
     @classmethod
     def from_process_group(cls, opts, libs, nbams, ntids, max_read_window_size, device):
@@ -128,7 +128,7 @@ class DistRun:
         rc = lib.bdx_dist_create_threads(hs, C.byref(co), arr, len(libs), nbams, ntids, max_read_window_size, dv, world)
         if rc != 0:
             raise BdxError("bdx_dist_create_threads: %s" % lib.bdx_strerror(rc).decode())
-        return [cls(hs[r], opts, libs, nbams) for r in range(world)]
+        return [cls(hs[r], opts, libs, nbams, ntids) for r in range(world)]
 
     def _chk(self, rc, what):
         if rc != 0:
@@ -190,6 +190,24 @@ class DistRun:
         over = np.empty(len(self.libs), dtype=np.uint64)
         self._chk(self.lib.bdx_dist_insert_size_histogram(self.h, hist.ctypes.data_as(C.c_void_p), over.ctypes.data_as(C.c_void_p)), "bdx_dist_insert_size_histogram")
         return hist, over
+
+    def context(self):
+        """this rank's one context, for the calls over its own store after run (bdx_dist_chromosome; every rank has one, whichever way
+        its records came in -- asking for the last sequence passes the feeding-order check whatever was fed)"""
+        if self.ntids is None:
+            raise BdxError("this rank was not created with a number of sequences: its context cannot be asked for")
+        return self.chromosome(self.ntids - 1)
+
+    def set_insert_null(self, hist):
+        """bdx_set_insert_null on this rank's context: hist[nlibs][ISIZE_BINS], the ranks' histograms summed by the caller -- on every
+        rank alike"""
+        self.context().set_insert_null(hist)
+        return self
+
+    def window_insert_shift(self, intervals):
+        """bdx_window_insert_shift over this rank's own store, after run: the caller sends a window to the rank that holds its sequence
+        (a sequence this rank holds nothing of gives zero rows)"""
+        return self.context().window_insert_shift(intervals)
 
     def set_libs(self, libs, max_read_window_size):
         """bdx_dist_set_libs: the libraries and the initial window of the run that follows, on every rank alike"""

@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "mini.h"
 #include "producer.h"
 #include "store_counts.h"
 
@@ -138,6 +139,11 @@ Inputs::Inputs(int argc, char** argv, const Env& env)
     if (!opts.estimate_config.empty()) {
         estimate_config.open(opts.estimate_config.c_str());
         if (!estimate_config.is_open()) throw std::runtime_error("unable to open --estimate-config file '" + opts.estimate_config + "' for writing");
+    }
+    if (!opts.mini.empty()) {
+        mini_out.open(opts.mini.c_str());
+        if (!mini_out.is_open()) throw std::runtime_error("unable to open --mini file '" + opts.mini + "' for writing");
+        if (opts.mini_window < 0 && !opts.estimate) (void)mini_mean_window(libs);
     }
 }
 

@@ -1,5 +1,5 @@
 // What a run is given, settled before the GPU is touched: the BDX_* environment knobs, the options (or the -R cache's), the
-// configuration, and the opened or parsed option inputs (--vcf, --exclude, --sites, --ci, --mapq, --estimate-config).  bdx-dump-reads shares the two helpers.
+// configuration, and the opened or parsed option inputs (--vcf, --exclude, --sites, --ci, --mapq, --estimate-config, --mini).  bdx-dump-reads shares the two helpers.
 #pragma once
 #include <cstdint>
 #include <fstream>
@@ -57,7 +57,7 @@ Env read_env();
 
 struct Inputs {
     // Fails in this order, each before the GPU is touched: option parsing, -R / config, (no BAM files: see no_bams), --vcf open, --exclude
-    // parse, --sites-vcf open and --sites parse, --ci window, --mapq window, --estimate-config open.
+    // parse, --sites-vcf open and --sites parse, --ci window, --mapq window, --estimate-config open, --mini open and window.
     Inputs(int argc, char** argv, const Env& env);
     Inputs(const Inputs&) = delete;
     Inputs& operator=(const Inputs&) = delete;
@@ -82,6 +82,9 @@ struct Inputs {
     std::vector<int> devices;    // BDX_GPUS
     bool sharded = false;        // ONE whole-genome run with the chromosomes spread over several GPUs
     std::ofstream estimate_config;   // --estimate-config: opened at once -- an unwritable path fails here
+
+    std::ofstream mini_out;          // --mini: opened at once -- an unwritable path fails here; without --mini-window (and without --estimate,
+                                     // which brings means of its own) a configuration with no finite positive mean insert size fails here too
 
     // --estimate, the one change a run makes to its inputs (between "fed" and "run"): the estimated values replace the configuration's in
     // cfg and libs, so that everything behind the feed prints and uses the run's libraries; the windows of --sites / --ci / --mapq that

@@ -75,6 +75,11 @@ void print_usage(const bdx_opts& o) {
     fprintf(stderr, "       --mark-dup     flag duplicate read pairs (same library, positions and strands of both mates) on the GPU; they are ignored like reads with SAM flag 0x400\n");
     fprintf(stderr, "       --estimate     take mean, std and the cutoffs of every library from all read pairs the run holds (on the GPU), not from the configuration\n");
     fprintf(stderr, "       --estimate-config FILE write the configuration with the estimated values to FILE (with --estimate)\n");
+    fprintf(stderr, "       --mini FILE    small insertions and deletions: windows whose pairs' insert sizes differ from their library's distribution (Kolmogorov-Smirnov), written to FILE\n");
+    fprintf(stderr, "       --mini-window INT  the window's width [the largest library mean insert size]\n");
+    fprintf(stderr, "       --mini-step INT    the distance between the starts of two windows [half the window]\n");
+    fprintf(stderr, "       --mini-min-pairs INT   the pairs of one library a window needs to be tested [%d]\n", Options::kMiniMinPairsDefault);
+    fprintf(stderr, "       --mini-score INT   the score a window must reach [20 + 10 log10 of the number of tested windows]\n");
     fprintf(stderr, "\n");
 }
 
@@ -90,7 +95,7 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
     // (the reference's letters parse exactly as with getopt; the long options are this tool's own)
-    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank, kMapq, kMapqWindow, kEstimate, kEstimateConfig };
+    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank, kMapq, kMapqWindow, kEstimate, kEstimateConfig, kMini, kMiniWindow, kMiniStep, kMiniMinPairs, kMiniScore };
     static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude},
                                          {"sites", required_argument, nullptr, kSites}, {"sites-vcf", required_argument, nullptr, kSitesVcf},
                                          {"sites-window", required_argument, nullptr, kSitesWindow}, {"mark-dup", no_argument, nullptr, kMarkDup},
@@ -98,6 +103,9 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
                                          {"depth", no_argument, nullptr, kDepth}, {"depth-flank", required_argument, nullptr, kDepthFlank},
                                          {"mapq", no_argument, nullptr, kMapq}, {"mapq-window", required_argument, nullptr, kMapqWindow},
                                          {"estimate", no_argument, nullptr, kEstimate}, {"estimate-config", required_argument, nullptr, kEstimateConfig},
+                                         {"mini", required_argument, nullptr, kMini}, {"mini-window", required_argument, nullptr, kMiniWindow},
+                                         {"mini-step", required_argument, nullptr, kMiniStep}, {"mini-min-pairs", required_argument, nullptr, kMiniMinPairs},
+                                         {"mini-score", required_argument, nullptr, kMiniScore},
                                          {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
@@ -139,6 +147,23 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
         }
         if (c == kEstimateConfig) {
             estimate_config = optarg;
+            continue;
+        }
+        if (c == kMini) {
+            mini = optarg;
+            continue;
+        }
+        if (c == kMiniWindow || c == kMiniStep || c == kMiniMinPairs || c == kMiniScore) {
+            const bool width = c == kMiniWindow || c == kMiniStep;
+            const long lo = width ? 1 : c == kMiniMinPairs ? 2 : 0, hi = width ? (1L << 30) : c == kMiniMinPairs ? BDX_MINI_CAP : 99999;
+            const char* name = c == kMiniWindow ? "window" : c == kMiniStep ? "step" : c == kMiniMinPairs ? "min-pairs" : "score";
+            char* end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < lo || v > hi) {
+                fprintf(stderr, "--mini-%s takes an integer from %ld to %ld, not '%s'.\n", name, lo, hi, optarg);
+                exit(1);
+            }
+            (c == kMiniWindow ? mini_window : c == kMiniStep ? mini_step : c == kMiniMinPairs ? mini_min_pairs : mini_score) = (int)v;
             continue;
         }
         if (c == kDepthFlank) {
@@ -198,6 +223,10 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     }
     if ((mapq && vcf.empty() && sites_vcf.empty()) || (!mapq && mapq_window >= 0)) {
         fprintf(stderr, "--mapq needs --vcf FILE or --sites-vcf FILE to write to (and --mapq-window goes with --mapq).\n");
+        exit(1);
+    }
+    if (mini.empty() && (mini_window >= 0 || mini_step >= 0 || mini_min_pairs >= 0 || mini_score >= 0)) {
+        fprintf(stderr, "--mini-window, --mini-step, --mini-min-pairs and --mini-score go with --mini FILE.\n");
         exit(1);
     }
     if (!estimate && !estimate_config.empty()) {

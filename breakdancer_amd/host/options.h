@@ -1,6 +1,6 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
 // (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf, --exclude, --sites / --sites-vcf /
-// --sites-window, --mark-dup, --ci / --ci-window, --depth / --depth-flank, --mapq / --mapq-window and --estimate / --estimate-config.
+// --sites-window, --mark-dup, --ci / --ci-window, --depth / --depth-flank, --mapq / --mapq-window, --estimate / --estimate-config and --mini / --mini-window / --mini-step / --mini-min-pairs / --mini-score.
 #pragma once
 #include <string>
 #include <vector>
@@ -30,6 +30,12 @@ struct Options {
     int mapq_window = -1;        // --mapq-window: how far from a breakpoint a read of --mapq may start (-1: from the libraries' cutoffs)
     bool estimate = false;       // --estimate: mean, std and cutoffs of every library from all pairs the run holds (bdx_insert_size_histogram, estimate.h)
     std::string estimate_config; // --estimate-config: the configuration with the estimated values, written for later runs (needs --estimate)
+    std::string mini;            // --mini: small insertions and deletions from windowed insert-size Kolmogorov-Smirnov tests, written to this file (mini.h)
+    int mini_window = -1;        // --mini-window: the window's width (-1: the ceiling of the largest library mean insert size)
+    int mini_step = -1;          // --mini-step: the distance between two windows' starts (-1: half the window)
+    int mini_min_pairs = -1;     // --mini-min-pairs: the pairs of one library a window needs for its row to score (-1: kMiniMinPairsDefault)
+    int mini_score = -1;         // --mini-score: the score a window must reach (-1: from the number of scoring windows)
+    static constexpr int kMiniMinPairsDefault = 20;
     static constexpr int kDepthFlankDefault = 1000;
     int flank() const { return depth_flank > 0 ? depth_flank : kDepthFlankDefault; }
     bdx_opts o;                  // numeric options in the C-ABI layout

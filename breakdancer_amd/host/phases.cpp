@@ -8,6 +8,7 @@
 #include <iostream>
 #include <stdexcept>
 
+#include "mini.h"
 #include "store_counts.h"
 
 namespace bdhost {
@@ -355,6 +356,82 @@ Genotypes count_on_store(const Inputs& in, const Env& env, const Session& s, con
                     gt.vcf_rows.size() + gt.site_rows.size(), opts.flank(), with, secs(tv, now()));
     }
     return gt;
+}
+
+// --mini: behind the run -- the store's histogram (after the run, so --mark-dup's marks are honoured) becomes the null of every context, the
+// grid windows of every sequence the run read go to the GPU in batches, and what reaches the threshold is merged and written (mini.h)
+void call_mini(Inputs& in, const Env& env, const Session& s, const Fed& fed) {
+    if (in.opts.mini.empty()) return;
+    const Options& opts = in.opts;
+    const auto t0 = now();
+    const int only_tid = opts.chr.empty() ? -1 : region_tid(in.header.names(), opts.chr);
+    const RunContexts rc{s.ctx, s.ranks, fed.rank_of, only_tid};
+    const size_t nlibs = in.libs.size();
+    MiniParams p;
+    p.window = opts.mini_window > 0 ? opts.mini_window : mini_mean_window(in.libs);
+    p.step = opts.mini_step > 0 ? opts.mini_step : std::max<int64_t>(p.window / 2, 1);
+    p.min_pairs = opts.mini_min_pairs > 0 ? opts.mini_min_pairs : Options::kMiniMinPairsDefault;
+    p.score = opts.mini_score;
+    std::vector<uint64_t> hist;
+    store_insert_histogram(rc, nlibs, hist);
+    const MiniNull null = mini_null(hist.data(), nlibs);
+    for (size_t l = 0; l < nlibs; ++l)
+        if (!null.usable[l])
+            fprintf(stderr, "WARNING: --mini: library %s has %llu usable pairs, fewer than %llu: skipped\n", in.cfg.library_config(l).name.c_str(),
+                    (unsigned long long)null.N[l], (unsigned long long)kMiniUsable);
+    set_insert_null(rc, hist.data());
+    const auto t1 = now();
+    double t_gpu = 0;
+    // (a sequence is taken to end at 2^31 - 2 at the latest, as --depth takes it: positions and window ends are int32 in the store and the ABI)
+    std::vector<uint32_t> lengths = in.header.lengths();
+    for (uint32_t& l : lengths) l = std::min<uint32_t>(l, 2147483646u);
+    const size_t batch = std::max<size_t>(((size_t)1 << 22) / nlibs, 1);   // (a call's rows stay at or below 160 MiB)
+    const double keep_from = p.score >= 0 ? (double)p.score : 20.0;       // (no threshold is below it)
+    std::vector<MiniKept> kept;
+    uint64_t windows = 0, scoring = 0, saturated = 0;
+    std::vector<bdx_interval> iv;
+    std::vector<std::pair<int32_t, int64_t>> which;
+    std::vector<bdx_insert_shift> rows;
+    auto flush = [&] {
+        if (iv.empty()) return;
+        const auto tg = now();
+        window_insert_shift(rc, iv, nlibs, rows);
+        t_gpu += secs(tg, now());
+        for (size_t i = 0; i < iv.size(); ++i) {
+            const MiniWindow w = mini_window(rows.data() + i * nlibs, null, p.min_pairs);
+            scoring += w.scoring;
+            saturated += w.saturated;
+            if (w.scoring && w.score >= keep_from) kept.push_back(MiniKept{which[i].first, which[i].second, w});
+        }
+        windows += iv.size();
+        iv.clear();
+        which.clear();
+    };
+    for (size_t t = 0; t < lengths.size(); ++t) {
+        if (!rc.held((int)t)) continue;
+        const int64_t len = lengths[t];
+        const uint64_t nw = mini_grid((uint64_t)len, p.step);
+        for (uint64_t j = 0; j < nw; ++j) {
+            const int64_t beg = (int64_t)j * p.step;
+            iv.push_back(bdx_interval{(int32_t)t, (int32_t)beg, (int32_t)std::min<int64_t>(beg + p.window, len)});
+            which.emplace_back((int32_t)t, (int64_t)j);
+            if (iv.size() == batch) flush();
+        }
+    }
+    flush();
+    const int threshold = p.score >= 0 ? p.score : mini_default_threshold(scoring);
+    const std::vector<MiniCall> calls = mini_merge(kept, threshold, p, lengths);
+    std::ofstream& out = in.mini_out;
+    out << "#Software: breakdancer-max --mini\n#Command: ";
+    for (auto const& a : opts.orig_argv) out << a << " ";
+    out << "\n#Window: " << p.window << "\n#Step: " << p.step << "\n#MinPairs: " << p.min_pairs << "\n#Threshold: " << threshold << "\n";
+    mini_write_table(out, calls, in.header.names());
+    out.close();
+    if (out.fail()) throw std::runtime_error("unable to write --mini file '" + opts.mini + "'");
+    if (env.timing)
+        fprintf(stderr, "[bdx timing] --mini: %llu windows (window %lld, step %lld), %llu scoring, %llu saturated, %zu calls, threshold %d; histogram %.4f s, kernel calls %.4f s, host %.4f s\n",
+                (unsigned long long)windows, (long long)p.window, (long long)p.step, (unsigned long long)scoring, (unsigned long long)saturated, calls.size(), threshold,
+                secs(t0, t1), t_gpu, secs(t1, now()) - t_gpu);
 }
 
 // supporting reads of the printed SVs: a second decode pass fetches just those records (the reference keeps

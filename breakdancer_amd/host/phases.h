@@ -73,6 +73,10 @@ struct Genotypes {
 };
 Genotypes count_on_store(const Inputs& in, const Env& env, const Session& s, const Fed& fed, const Calls& calls);
 
+// --mini: the windowed insert-size tests over the records the run holds, written to the file the inputs opened (mini.h).  Like
+// count_on_store it runs before the trimmer starts
+void call_mini(Inputs& in, const Env& env, const Session& s, const Fed& fed);
+
 // -g / -d: the supporting reads of the printed SVs and the opened dump files
 struct Support {
     std::vector<uint32_t> off;

@@ -19,13 +19,17 @@ void check(bdx_ctx* ctx, int rc, const char* what) {
 
 namespace {
 
+// the context of rank r of a sharded run (one per rank, the same for every chromosome: asking for the last sequence passes the
+// feeding-order check whatever was fed)
+bdx_ctx* rank_context(const RunContexts& rc, size_t r) { return bdx_dist_chromosome(rc.ranks[r], (int)rc.rank_of.size() - 1); }
+
 // Counts over the resident records, one item per query: on the single context all at once, or -- a sharded run -- item i on the rank that
 // holds chromosome item_tid[i], every rank on its own context and on a thread of its own.  count(context, the items' indices, their
 // counts [items][ns]) returns a bdx status.
-template <class F>
-void count_on_ranks(const RunContexts& rc, const std::vector<int32_t>& item_tid, size_t ns, const char* what, std::vector<uint32_t>& counts, F count) {
+template <class T, class F>
+void count_on_ranks(const RunContexts& rc, const std::vector<int32_t>& item_tid, size_t ns, const char* what, std::vector<T>& counts, F count) {
     const size_t nq = item_tid.size();
-    counts.assign(nq * ns, 0);
+    counts.assign(nq * ns, T{});
     if (!nq) return;
     if (rc.ranks.empty()) {
         std::vector<size_t> all(nq);
@@ -42,9 +46,8 @@ void count_on_ranks(const RunContexts& rc, const std::vector<int32_t>& item_tid,
         if (mine[r].empty()) continue;
         th.emplace_back([&, r] {
             const std::vector<size_t>& m = mine[r];
-            std::vector<uint32_t> c(m.size() * ns);
-            // (one context per rank, the same for every chromosome: asking for the last sequence passes the feeding-order check whatever was fed)
-            bdx_ctx* rctx = bdx_dist_chromosome(rc.ranks[r], (int)rc.rank_of.size() - 1);
+            std::vector<T> c(m.size() * ns);
+            bdx_ctx* rctx = rank_context(rc, r);
             const int st = rctx ? count(rctx, m, c.data()) : BDX_EINTERNAL;
             if (st != BDX_OK) {
                 errs[r] = std::string(what) + " on rank " + std::to_string(r) + ": " + bdx_strerror(st) + (rctx ? std::string(" (") + bdx_last_error(rctx) + ")" : "");
@@ -275,6 +278,45 @@ int32_t cutoff_window(const BamConfig& cfg, const char* option) {
     }
     if (ub < 0) throw std::runtime_error(std::string(option) + ": no library has a finite uppercutoff, give " + option + "-window");
     return (int32_t)std::min(ub, 1073741824.0);
+}
+
+// --mini: the store's insert-size histogram after the run (--mark-dup's marks are in the flag column), summed over the ranks
+void store_insert_histogram(const RunContexts& rc, size_t nlibs, std::vector<uint64_t>& hist) {
+    hist.assign(nlibs * (size_t)BDX_ISIZE_BINS, 0);
+    std::vector<uint64_t> over(nlibs);
+    if (rc.ranks.empty()) {
+        check(rc.ctx, bdx_insert_size_histogram(rc.ctx, hist.data(), over.data()), "bdx_insert_size_histogram");
+        return;
+    }
+    std::vector<uint64_t> h(hist.size());
+    for (bdx_dist* r : rc.ranks) {
+        if (bdx_dist_insert_size_histogram(r, h.data(), over.data()) != BDX_OK)
+            throw std::runtime_error(std::string("bdx_dist_insert_size_histogram: ") + bdx_dist_last_error(r));
+        for (size_t i = 0; i < hist.size(); ++i) hist[i] += h[i];
+    }
+}
+
+void set_insert_null(const RunContexts& rc, const uint64_t* hist) {
+    if (rc.ranks.empty()) {
+        check(rc.ctx, bdx_set_insert_null(rc.ctx, hist), "bdx_set_insert_null");
+        return;
+    }
+    for (size_t r = 0; r < rc.ranks.size(); ++r) {
+        bdx_ctx* c = rank_context(rc, r);
+        if (!c) throw std::runtime_error(std::string("bdx_dist_chromosome: ") + bdx_dist_last_error(rc.ranks[r]));
+        check(c, bdx_set_insert_null(c, hist), "bdx_set_insert_null");
+    }
+}
+
+void window_insert_shift(const RunContexts& rc, const std::vector<bdx_interval>& iv, size_t nlibs, std::vector<bdx_insert_shift>& rows) {
+    std::vector<int32_t> q_tid(iv.size());
+    for (size_t i = 0; i < iv.size(); ++i) q_tid[i] = iv[i].tid;
+    count_on_ranks(rc, q_tid, nlibs, "bdx_window_insert_shift", rows, [&](bdx_ctx* c, const std::vector<size_t>& m, bdx_insert_shift* out) {
+        if (m.size() == iv.size()) return bdx_window_insert_shift(c, iv.data(), iv.size(), out);   // (the single context: all of them, in order)
+        std::vector<bdx_interval> mine(m.size());
+        for (size_t j = 0; j < m.size(); ++j) mine[j] = iv[m[j]];
+        return bdx_window_insert_shift(c, mine.data(), m.size(), out);
+    });
 }
 
 }  // namespace bdhost

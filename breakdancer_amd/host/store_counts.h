@@ -1,4 +1,4 @@
-// --vcf / --sites / --ci / --depth / --mapq: the counts over the records a finished run holds on the GPU (K8, KS, KI, KR, KM of include/bdx.h), turned into the
+// --vcf / --sites / --ci / --depth / --mapq / --mini: the counts over the records a finished run holds on the GPU (K8, KS, KI, KR, KM of include/bdx.h), turned into the
 // records VcfWriter prints (vcf.h).
 #pragma once
 #include <cstdint>
@@ -42,6 +42,13 @@ void fill_quality(const Options& opts, const RunContexts& rc, int32_t window, st
 // --depth: RCI / RCF of --vcf and --sites-vcf records from the passing read starts inside and beside them; lengths: the sequences' (the
 // flanks are clamped to them), ns: the samples.
 void fill_depth(const Options& opts, const RunContexts& rc, int32_t flank, const std::vector<uint32_t>& lengths, size_t ns, std::vector<VcfRecord>& out);
+
+// --mini: the store's insert-size histogram after the run, summed over the ranks (hist[nlibs][BDX_ISIZE_BINS]); that histogram as the null of
+// every context of the run; and the rows [windows][nlibs] of bdx_window_insert_shift, each window answered by the rank that holds its sequence
+// (every iv[i].tid is a sequence the run holds).
+void store_insert_histogram(const RunContexts& rc, size_t nlibs, std::vector<uint64_t>& hist);
+void set_insert_null(const RunContexts& rc, const uint64_t* hist);
+void window_insert_shift(const RunContexts& rc, const std::vector<bdx_interval>& iv, size_t nlibs, std::vector<bdx_insert_shift>& rows);
 
 // How far a supporting mate can start from a breakpoint it brackets: the ceiling of the largest finite library uppercutoff, the window
 // of --sites, --ci and --mapq when theirs is not given.

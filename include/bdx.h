@@ -261,6 +261,7 @@ int bdx_set_host_walk(bdx_ctx* ctx, int on);
  *   "asm_plain"      the walk's candidate assembly merges its parts by the three-way merge (the route of one library, or of many)
  *   "gather_walk"    sharded runs: 1 = rank 0 walks the gathered components on its device, 2 = on its host (by their number otherwise)
  *   "depth_plain"    bdx_count_interval_reads walks every interval record by record, without the chunk table (the route of an interval that holds no whole chunk)
+ *   "mini_staged"    bdx_window_insert_shift ranks every window's observations by the all-pairs passes over its LDS slice (the route of a window with more than 64)
  * BDX_EINVAL for any other name. */
 int bdx_set_debug(bdx_ctx* ctx, const char* name, int value);
 int bdx_get_walk_split(const bdx_ctx* ctx, uint32_t* n_sv_device, uint32_t* n_sv_host, uint32_t* n_groups_host);
@@ -668,6 +669,51 @@ int bdx_dist_insert_size_histogram(bdx_dist* d, uint64_t* hist, uint64_t* n_over
 int bdx_estimate_insert_size(const uint64_t* hist /*[BDX_ISIZE_BINS]*/, bdx_insert_estimate* out);
 int bdx_set_libs(bdx_ctx* ctx, const bdx_lib* libs, int nlibs, int max_read_window_size0);
 int bdx_dist_set_libs(bdx_dist* d, const bdx_lib* libs, int nlibs, int max_read_window_size0);
+
+/* Insert-size shift of the pairs that start inside given windows: no counterpart in the C++ reference, whose calls need -r pairs beyond a
+ * hard cutoff; the original distribution's BreakDancerMini slid a window over the normally mapped pairs and tested their insert sizes
+ * against the library's distribution with Kolmogorov-Smirnov (the CLI's --mini).  The rule, written down here once:
+ *   NULL         bdx_set_insert_null takes hist[nlibs][BDX_ISIZE_BINS] exactly as bdx_insert_size_histogram writes it (the caller may sum
+ *                ranks first) and keeps, per library, the cumulative table C_L(x) = sum over y <= x of hist[L][y] on the device, with
+ *                N_L = C_L(BDX_ISIZE_BINS - 1).  The next call replaces the table; NULL, or bdx_destroy, frees it.  BDX_ELIMIT when some
+ *                N_L >= 2^51: with BDX_MINI_CAP that keeps every product below in int64.  BDX_ESTATE while a sizing pass is in flight.
+ *   OBSERVATION  record i of the resident store is an observation x = |isize[i]| of its library for interval (tid, [beg, end)) -- 0-based,
+ *                half-open, bdx_interval as everywhere -- when tid[i] == tid and beg <= pos[i] < end; cls[i] & BDX_CLS_PASS;
+ *                BDX_CLS_FLAG(cls[i]) is one of BDX_NORMAL_FR, BDX_NORMAL_RF, BDX_ARP_LARGE_INSERT, BDX_ARP_SMALL_INSERT (the same-chromosome
+ *                classes whose only possible anomaly is the insert size); mtid[i] == tid[i]; and it is its pair's lower mate exactly as
+ *                bdx_count_site_pairs decides it: pos < mpos, or the two are equal and the record is first in pair (flag & 0x40).  The
+ *                library index resolves as everywhere (out of range: library 0; a context with one library never reads the column).
+ *                x >= BDX_ISIZE_BINS counts only in n_over and is otherwise no observation.
+ *                A window is selected by the read's START, not by what its fragment spans: every pair has one lower mate with one start,
+ *                whatever its insert size, so the window's sample is drawn without regard to x and the null needs no length-bias correction.
+ *   ROW          out[q * nlibs + L], for the observations x_1 .. x_n of library L in interval q:
+ *                  n, n_over; sum = x_1 + .. + x_n;
+ *                  t_plus  = max(0, max over i of ( #{j: x_j <= x_i} N_L - C_L(x_i) n ));
+ *                  t_minus = max(0, max over i of ( C_L(x_i - 1) n - #{j: x_j < x_i} N_L )), with C_L(-1) = 0.
+ *                These are n N_L times the one-sided Kolmogorov-Smirnov distances D+ and D- between the window's empirical distribution
+ *                function and the null's: both are right-continuous steps on the integers, so the suprema are attained at x_i and x_i - 1.
+ *                Everything is an integer: the result is exact and does not depend on the order of evaluation.  N_L == 0 or n == 0: both
+ *                t's are 0.  A library absent from a window gets an all-zero row.
+ *   CAP          when the observations of a window, all libraries together, exceed BDX_MINI_CAP, every row of that window has
+ *                saturated = 1 and t_plus = t_minus = 0; n, n_over and sum stay exact.  This covers pile-ups; nothing is silent.
+ *   SCORE        bdx_insert_shift_score, host only, no GPU (csrc/bdx_mini.h): D = max(t_plus, t_minus) / ((double)n (double)N),
+ *                lambda = (sqrt(n) + 0.12 + 0.11 / sqrt(n)) D; score = 0 for lambda < 0.4; otherwise
+ *                ln p = ln 2 - 2 lambda^2 + ln( sum over j >= 1 of (-1)^(j-1) exp(-2 (j^2 - 1) lambda^2) ), terms added until one is below 1e-17,
+ *                and score = -10 ln p / ln 10: the asymptotic Kolmogorov tail, written so that it never underflows.  score and D are 0 for
+ *                n == 0, N == 0 or a saturated row.  Either result pointer may be NULL; BDX_EINVAL for a null row.
+ * bdx_window_insert_shift (KW, csrc/km_mini.hip): state, errors and their order are those of bdx_count_interval_reads -- BDX_ESTATE before a
+ * run has classified the reads the context holds, while a sizing pass is in flight, or with no null set; n == 0 is BDX_OK; BDX_EINVAL for a
+ * null array with n > 0, tid < 0, beg < 0 or end < beg; BDX_ELIMIT above 2^31 intervals.  After bdx_run, or on a rank's context
+ * (bdx_dist_chromosome) after bdx_dist_run; a tid the context holds nothing of gives zero rows.  Not beside another call on the same context. */
+#define BDX_MINI_CAP 4096   /* published for the tests */
+typedef struct bdx_insert_shift {     /* 40 bytes */
+    uint32_t n, n_over, saturated, pad;   /* pad = 0 */
+    uint64_t sum;
+    int64_t  t_plus, t_minus;
+} bdx_insert_shift;
+int bdx_set_insert_null(bdx_ctx* ctx, const uint64_t* hist /*[nlibs][BDX_ISIZE_BINS], NULL frees*/);
+int bdx_window_insert_shift(bdx_ctx* ctx, const bdx_interval* iv, size_t n, bdx_insert_shift* out /*[n][nlibs]*/);
+int bdx_insert_shift_score(const bdx_insert_shift* row, uint64_t N, double* score, double* D);
 
 /* device the context is bound to and the HIP stream it launches on (as void*), for callers that time it */
 int bdx_device(const bdx_ctx* ctx);
