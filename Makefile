@@ -8,7 +8,7 @@ KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
 HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/device_feed.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp $(HOST)/table.cpp $(HOST)/store_counts.cpp $(HOST)/inputs.cpp $(HOST)/estimate.cpp $(HOST)/mini.cpp
 
-all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check bin/bdx-feed-probe tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so oracle
+all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check bin/bdx-feed-probe tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -83,6 +83,11 @@ tests/prims/libbdx_prims.so: tests/prims/prims.hip $(CSRC)/bdx_scan.h $(CSRC)/bd
 tests/prims/libbdx_stages.so: tests/prims/stages.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/bdx_k3.h $(CSRC)/bdx_scan.h $(CSRC)/bdx_dev.h include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -shared -o $@ tests/prims/stages.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip
 
+# test tooling: K2 and the pass-1 finalisation on their own -- launch_k2, launch_finalize and launch_k1 with their translation units, unchanged,
+# behind plain C entry points (tests/test_gpu_compact.py); nothing of it goes into libbdx.so
+tests/prims/libbdx_compact.so: tests/prims/compact.hip $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/bdx_finalize.h $(CSRC)/bdx_dev.h include/bdx.h
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -shared -Wl,--no-undefined -o $@ tests/prims/compact.hip $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip
+
 # measurement tool (bench.py): the feeder's ceilings -- page cache -> pinned -> HBM
 bin/bdx-feed-probe: tools/feed_probe.hip
 	@mkdir -p bin
@@ -100,7 +105,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so
+	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -258,7 +258,7 @@ template <bool kBases> __device__ __forceinline__ void k2_body(const K2Params& p
             const uint32_t b1 = k0 + 1 < nkeys ? (k0 == 0 ? pre_k1 : col_prefix<kBases>(p, kColKey0 + k0 + 1, tile2, chunk, lane)) : 0u;
             uint32_t j = rank0 + local0;
             for (uint32_t mm = m_anom; mm; mm &= mm - 1, ++j) {
-                if (j >= p.c.cap) break;
+                if (j >= p.c.cap) continue;  // (slot by slot, as the gather above: a rank that wraps 2^32 comes back below the capacity)
                 const int r = __builtin_ctz(mm);
                 const uint32_t upto = (2u << r) - 1u;  // reads 0..r of this lane
                 p.c.pk[(size_t)k0 * p.c.cap + j] = b0 + (ex & 0xFFFFu) + (uint32_t)__popc(mk0 & upto);
