@@ -4,11 +4,11 @@ ARCH ?= gfx950
 CSRC := breakdancer_amd/csrc
 HOST := breakdancer_amd/host
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Iinclude
-KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/kq_queries.hip $(CSRC)/kr_depth.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/kh_insert_hist.hip $(CSRC)/km_mini.hip $(CSRC)/bdx_api.hip
+KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/kq_queries.hip $(CSRC)/kp_clip.hip $(CSRC)/kr_depth.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/kh_insert_hist.hip $(CSRC)/km_mini.hip $(CSRC)/bdx_api.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
 HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/device_feed.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp $(HOST)/table.cpp $(HOST)/store_counts.cpp $(HOST)/inputs.cpp $(HOST)/estimate.cpp $(HOST)/mini.cpp
 
-all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check bin/bdx-feed-probe tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so oracle
+all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check bin/bdx-feed-probe tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -24,7 +24,7 @@ breakdancer_amd/libbdx.so: $(OBJS)
 
 HOSTFLAGS := -O2 -std=c++17 -ffp-contract=off -Wall -Iinclude -pthread
 
-bin/breakdancer-max: $(HOSTCOMMON) $(HOST)/main.cpp $(HOST)/phases.cpp $(wildcard $(HOST)/*.h) $(CSRC)/bdx_exclude.h $(CSRC)/bdx_estimate.h $(CSRC)/bdx_mini.h breakdancer_amd/libbdx.so
+bin/breakdancer-max: $(HOSTCOMMON) $(HOST)/main.cpp $(HOST)/phases.cpp $(wildcard $(HOST)/*.h) $(CSRC)/bdx_exclude.h $(CSRC)/bdx_estimate.h $(CSRC)/bdx_mini.h $(CSRC)/bdx_clip.h breakdancer_amd/libbdx.so
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOSTCOMMON) $(HOST)/main.cpp $(HOST)/phases.cpp -Lbreakdancer_amd -lbdx -lz -Wl,-rpath,'$$ORIGIN/../breakdancer_amd' -Wl,-rpath,/opt/rocm/lib
 
@@ -51,6 +51,17 @@ bin/bdx-depth-check: $(HOST)/depth_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h
 bin/bdx-mapq-check: $(HOST)/mapq_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/mapq_check_main.cpp $(HOST)/vcf.cpp
+
+# test tooling: the host half of --clip -- the clip word (csrc/bdx_clip.h), the host reader's words of a BAM, the INFO keys (vcf.cpp) --
+# without libbdx (tests/test_clip.py)
+bin/bdx-clip-check: $(HOST)/clip_check_main.cpp $(HOST)/vcf.cpp $(HOST)/vcf.h $(HOST)/bam_reader.cpp $(HOST)/bam_reader.h $(HOST)/bgzf.h $(CSRC)/bdx_clip.h
+	@mkdir -p bin
+	g++ $(HOSTFLAGS) -o $@ $(HOST)/clip_check_main.cpp $(HOST)/vcf.cpp $(HOST)/bam_reader.cpp -lz
+
+# test tooling: the clip column as a run with --clip leaves it, through the CLI's own feeding phases (tests/test_gpu_clip.py; needs a GPU)
+bin/bdx-clip-store: $(HOSTCOMMON) $(HOST)/clip_store_main.cpp $(HOST)/phases.cpp $(wildcard $(HOST)/*.h) $(CSRC)/bdx_exclude.h $(CSRC)/bdx_estimate.h $(CSRC)/bdx_mini.h $(CSRC)/bdx_clip.h breakdancer_amd/libbdx.so
+	@mkdir -p bin
+	g++ $(HOSTFLAGS) -o $@ $(HOSTCOMMON) $(HOST)/clip_store_main.cpp $(HOST)/phases.cpp -Lbreakdancer_amd -lbdx -lz -Wl,-rpath,'$$ORIGIN/../breakdancer_amd' -Wl,-rpath,/opt/rocm/lib
 
 # test tooling: the host half of --estimate (estimate.cpp, csrc/bdx_estimate.h) on a histogram given as text, without libbdx (tests/test_estimate.py)
 bin/bdx-estimate-check: $(HOST)/estimate_check_main.cpp $(HOST)/estimate.cpp $(HOST)/config.cpp $(HOST)/estimate.h $(HOST)/config.h $(CSRC)/bdx_estimate.h include/bdx.h
@@ -93,11 +104,11 @@ bin/bdx-feed-probe: tools/feed_probe.hip
 	@mkdir -p bin
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -mavx2 -o $@ $< -lpthread
 
-bin/bam2cfg: $(HOST)/bam2cfg_main.cpp $(HOST)/bam_reader.cpp $(HOST)/bam_reader.h $(HOST)/bgzf.h breakdancer_amd/libbdx.so
+bin/bam2cfg: $(HOST)/bam2cfg_main.cpp $(HOST)/bam_reader.cpp $(HOST)/bam_reader.h $(HOST)/bgzf.h $(CSRC)/bdx_clip.h breakdancer_amd/libbdx.so
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/bam2cfg_main.cpp $(HOST)/bam_reader.cpp -Lbreakdancer_amd -lbdx -lz -lpthread -Wl,-rpath,'$$ORIGIN/../breakdancer_amd' -Wl,-rpath,/opt/rocm/lib
 
-bin/bdx-dump-reads: $(HOSTCOMMON) $(HOST)/dump_main.cpp $(wildcard $(HOST)/*.h) $(CSRC)/bdx_exclude.h $(CSRC)/bdx_estimate.h $(CSRC)/bdx_mini.h breakdancer_amd/libbdx.so
+bin/bdx-dump-reads: $(HOSTCOMMON) $(HOST)/dump_main.cpp $(wildcard $(HOST)/*.h) $(CSRC)/bdx_exclude.h $(CSRC)/bdx_estimate.h $(CSRC)/bdx_mini.h $(CSRC)/bdx_clip.h breakdancer_amd/libbdx.so
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOSTCOMMON) $(HOST)/dump_main.cpp -Lbreakdancer_amd -lbdx -lz -Wl,-rpath,'$$ORIGIN/../breakdancer_amd' -Wl,-rpath,/opt/rocm/lib
 
@@ -105,7 +116,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so
+	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

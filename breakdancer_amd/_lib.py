@@ -60,7 +60,8 @@ EXPORTS = ["bdx_opts_default", "bdx_create", "bdx_destroy", "bdx_strerror", "bdx
            "bdx_count_junction_pairs", "bdx_bamdec_set_exclude", "bdx_bamdec_excluded", "bdx_exclude_mask", "bdx_count_site_pairs", "bdx_site_breakpoint_bounds", "bdx_count_interval_reads", "bdx_site_end_quality",
            "bdx_set_mark_duplicates", "bdx_get_duplicates", "bdx_dist_set_mark_duplicates", "bdx_dist_get_duplicates", "bdx_mark_duplicates",
            "bdx_insert_size_histogram", "bdx_dist_insert_size_histogram", "bdx_estimate_insert_size", "bdx_set_libs", "bdx_dist_set_libs",
-           "bdx_set_insert_null", "bdx_window_insert_shift", "bdx_insert_shift_score"]
+           "bdx_set_insert_null", "bdx_window_insert_shift", "bdx_insert_shift_score",
+           "bdx_clip_word", "bdx_use_clips", "bdx_put_clips", "bdx_get_clips", "bdx_site_clip_peaks", "bdx_bamdec_fetch_clips"]
 
 # kDupT (csrc/bdx_dev.h): KD compares the records of a run directly when the run has at most this many, longer runs go through its table
 DUP_T = 64
@@ -72,6 +73,11 @@ SITE_BOUNDS_DTYPE = np.dtype([("n", "<u4"), ("lo1", "<i4"), ("hi1", "<i4"), ("lo
 # bdx_site_quality: supporters of one end of a site, the records around it and the low ones among them; over the supporters' mapping
 # qualities the extremes, the lower quartile and the lower median (all 0 with n == 0)
 SITE_QUALITY_DTYPE = np.dtype([("n", "<u4"), ("n_all", "<u4"), ("n_low", "<u4"), ("qmin", "u1"), ("q1", "u1"), ("median", "u1"), ("qmax", "u1")])
+# bdx_clip_peaks: per side of one end of a site the clipped observations, the X most of them share and how many do (all 0 with n == 0)
+CLIP_PEAKS_DTYPE = np.dtype([("n_left", "<u4"), ("n_right", "<u4"), ("pos_left", "<i4"), ("pos_right", "<i4"), ("peak_left", "<u4"), ("peak_right", "<u4")])
+# BDX_CLIP_SPAN_MAX, BDX_CLIP_WINDOW_MAX (include/bdx.h): how far behind its read's start a right clip is looked for; the largest window
+CLIP_SPAN_MAX = 4096
+CLIP_WINDOW_MAX = 1023
 # bdx_interval: 0-based, half-open (--exclude's mask, bdx_count_interval_reads)
 INTERVAL_DTYPE = np.dtype([("tid", "<i4"), ("beg", "<i4"), ("end", "<i4")])
 # BDX_DEPTH_CHUNK (include/bdx.h): the records per chunk of bdx_count_interval_reads' table; the tests place intervals around its multiples
@@ -164,5 +170,12 @@ def load():
     L.bdx_set_insert_null.argtypes = [vp, vp]
     L.bdx_window_insert_shift.argtypes = [vp, vp, C.c_size_t, vp]
     L.bdx_insert_shift_score.argtypes = [vp, C.c_uint64, vp, vp]
+    L.bdx_clip_word.argtypes = [vp, C.c_uint32, C.c_int32, C.c_uint32]
+    L.bdx_clip_word.restype = C.c_uint32
+    L.bdx_use_clips.argtypes = [vp, C.c_int]
+    L.bdx_put_clips.argtypes = [vp, C.c_size_t, vp, C.c_size_t]
+    L.bdx_get_clips.argtypes = [vp, vp, C.c_size_t]
+    L.bdx_site_clip_peaks.argtypes = [vp, vp, vp, C.c_size_t, C.c_int32, C.c_int32, vp]
+    L.bdx_bamdec_fetch_clips.argtypes = [vp, C.c_size_t, C.c_size_t, vp]
     _lib = L
     return L

@@ -133,6 +133,7 @@ class BreakDancer:
             self.h = C.c_void_p()
             raise BdxError("bdx_create: %s" % self.lib.bdx_strerror(rc).decode())
         self._keep = []
+        self._n_held = 0   # records pushed or streamed through this object since the last reset_reads (get_clips' default row count)
 
     @classmethod
     def borrow(cls, handle, opts, libs, nbams):
@@ -143,6 +144,7 @@ class BreakDancer:
         self.nlibs, self.nbams = len(self.libs), nbams
         self.h = C.c_void_p(handle)
         self._keep = []
+        self._n_held = 0
         self._borrowed = True
         return self
 
@@ -198,15 +200,46 @@ class BreakDancer:
         self.libs = libs
         return self
 
-    def push_reads(self, arrs):
+    def use_clips(self, on=True):
+        """the store gets a column of clip words (bdx_use_clips; the word is in include/bdx.h, bdx_clip_word): what site_clip_peaks reads;
+        while the context holds no reads"""
+        self._chk(self.lib.bdx_use_clips(self.h, 1 if on else 0), "bdx_use_clips")
+        return self
+
+    def put_clips(self, first, clip):
+        """clip words of the records [first, first + len(clip)) the context already holds (bdx_put_clips); rows never put stay 0"""
+        a = np.ascontiguousarray(clip, dtype=np.uint32)
+        self._chk(self.lib.bdx_put_clips(self.h, int(first), a.ctypes.data_as(C.c_void_p), len(a)), "bdx_put_clips")
+        return self
+
+    def get_clips(self, n=None):
+        """the clip column's first n rows as uint32 (bdx_get_clips).  The default n counts only what push_reads / stream_reads of THIS object
+        put into the store since the last reset_reads: it is wrong (too small) for a store that a decoder or merge_decoded filled -- give
+        that store's own record count"""
+        n = int(self._n_held if n is None else n)
+        out = np.zeros(n, np.uint32)
+        self._chk(self.lib.bdx_get_clips(self.h, out.ctypes.data_as(C.c_void_p), n), "bdx_get_clips")
+        return out
+
+    def push_reads(self, arrs, clip=None):
+        """clip: the batch's clip words (after use_clips), put behind the push"""
         b, keep = make_batch(arrs)
+        if clip is not None and len(clip) != b.n:
+            raise ValueError("ragged batch: clip has %d rows, expected %d" % (len(clip), b.n))
         self._keep.append(keep)  # the H2D copies are asynchronous: the arrays must outlive them (released by run())
         self._chk(self.lib.bdx_push(self.h, C.byref(b)), "bdx_push")
+        first = self._n_held
+        self._n_held = first + b.n
+        if clip is not None:
+            self.put_clips(first, clip)
 
-    def stream_reads(self, arrs, batch=1 << 20):
+    def stream_reads(self, arrs, batch=1 << 20, clip=None):
         """The streaming producer's path: fill the context's pinned staging buffers batch by batch (bdx_acquire_batch /
-        bdx_submit_batch); copies and the classifier overlap the filling of the next buffer."""
+        bdx_submit_batch); copies and the classifier overlap the filling of the next buffer.  clip: the records' clip words (after
+        use_clips), put behind each batch."""
         n = len(arrs["tid"])
+        if clip is not None and len(clip) != n:
+            raise ValueError("ragged batch: clip has %d rows, expected %d" % (len(clip), n))
         cols = {}
         for k, dt in BATCH_FIELDS:
             src = arrs.get(k)
@@ -226,10 +259,15 @@ class BreakDancer:
             for k, dt in fields:
                 C.memmove(getattr(buf, k), cols[k][lo:lo + m].ctypes.data, m * np.dtype(dt).itemsize)
             self._chk(self.lib.bdx_submit_batch(self.h, m), "bdx_submit_batch")
+            first = self._n_held
+            self._n_held = first + m
+            if clip is not None:
+                self.put_clips(first, clip[lo:lo + m])
 
     def reset_reads(self):
         self._chk(self.lib.bdx_reset_reads(self.h), "bdx_reset_reads")
         self._keep.clear()
+        self._n_held = 0
         return self
 
     def set_device_reads(self, ptrs, n):
@@ -371,6 +409,25 @@ class BreakDancer:
         self._chk(self.lib.bdx_site_end_quality(self.h, p(s), p(e), len(s), int(window), p(out)), "bdx_site_end_quality")
         return out
 
+    def site_clip_peaks(self, sites, ends, window, min_clip=10):
+        """Where the clipped reads pile up around one end of given SV sites (bdx_site_clip_peaks; the rule is in include/bdx.h), after
+        use_clips: `sites` and `ends` as for site_end_quality (the flag mask is not used), window 0 .. _lib.CLIP_WINDOW_MAX, min_clip
+        1 .. 255.  A passing record clipped by min_clip or more on its left gives an observation at its first aligned base, one clipped on
+        its right at its last.  Returns an array of _lib.CLIP_PEAKS_DTYPE: per side the observations within `window` of the end, the
+        position most of them share and how many do (ties: nearer to the end, then smaller; all 0 with n == 0)."""
+        if isinstance(sites, np.ndarray) and sites.dtype == L.SITE_DTYPE:
+            s = np.ascontiguousarray(sites)
+        else:
+            rows = [tuple(int(v) for v in r) for r in sites]
+            s = np.array(rows, dtype=L.SITE_DTYPE) if rows else np.zeros(0, dtype=L.SITE_DTYPE)
+        e = np.ascontiguousarray(np.asarray(ends).reshape(-1), dtype=np.uint8)
+        if len(e) != len(s):
+            raise ValueError("sites and ends differ in length")
+        out = np.zeros(len(s), dtype=L.CLIP_PEAKS_DTYPE)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.bdx_site_clip_peaks(self.h, p(s), p(e), len(s), int(window), int(min_clip), p(out)), "bdx_site_clip_peaks")
+        return out
+
     def count_interval_reads(self, intervals, by_library=False):
         """Passing read starts of the last run inside given intervals (bdx_count_interval_reads; the rule is in include/bdx.h):
         `intervals` is an array of _lib.INTERVAL_DTYPE, or a sequence of (tid, beg, end), 0-based and half-open.  A record counts when it
@@ -472,6 +529,15 @@ def estimate_insert_size(hist):
     if rc != 0:
         raise BdxError("bdx_estimate_insert_size: %s" % lib.bdx_strerror(rc).decode())
     return {k: getattr(out, k) for k, _ in L.bdx_insert_estimate._fields_}
+
+
+def clip_word(cigar, l_seq, flag=0):
+    """bdx_clip_word: the clip word of a CIGAR given as a sequence of (length, operation) with the operation a letter of MIDNSHP=X or its
+    BAM code (host only, no GPU)"""
+    lib = L.load()
+    code = lambda op: "MIDNSHP=X".index(op) if isinstance(op, str) else int(op)
+    w = np.array([(int(n) << 4) | code(op) for n, op in cigar], dtype=np.uint32)
+    return int(lib.bdx_clip_word(w.ctypes.data_as(C.c_void_p) if len(w) else None, len(w), int(l_seq), int(flag)))
 
 
 def insert_shift_score(row, N):

@@ -165,10 +165,12 @@ def bam_header(data, members):
 
 class BamDecoder:
     """One BAM file through bdx_bamdec_*.  sink: a breakdancer_amd.api.BreakDancer whose store receives the records, or None
-    (the columns stay in the decoder; fetch() copies them out).  exclude: rows of (tid, beg, end), the --exclude mask (bdx_bamdec_set_exclude)."""
+    (the columns stay in the decoder; fetch() copies them out).  exclude: rows of (tid, beg, end), the --exclude mask (bdx_bamdec_set_exclude).
+    clips: a decoder without a sink keeps the records' clip words too (record_mode bit 4; fetch_clips(), and what a merge into a context
+    with use_clips() needs); with a sink the sink's own use_clips() decides."""
 
     def __init__(self, n_targets, sink=None, device=0, bam_index=0, rg_ids=(), rg_lib=(), fallback_lib=0, region=None,
-                 first_record_offset=0, ring_bytes=0, batch_bytes=0, batch_blocks=0, exclude=None):
+                 first_record_offset=0, ring_bytes=0, batch_bytes=0, batch_blocks=0, exclude=None, clips=False):
         self.lib = _lib()
         p = bdx_bamdec_params()
         p.device = device
@@ -185,6 +187,7 @@ class BamDecoder:
         p.ring_bytes = ring_bytes
         p.batch_bytes = batch_bytes
         p.batch_blocks = batch_blocks
+        p.record_mode = 4 if clips else 0
         h = C.c_void_p()
         rc = self.lib.bdx_bamdec_create(C.byref(h), sink.h if sink is not None else None, C.byref(p))
         if rc != 0:
@@ -303,6 +306,12 @@ class BamDecoder:
         self._check(self.lib.bdx_bamdec_fetch(self.h, 0, n, C.byref(b)), "bdx_bamdec_fetch")
         return cols
 
+    def fetch_clips(self):
+        """the clip words of the decoder's own records (bdx_bamdec_fetch_clips): a decoder without a sink, made with clips=True"""
+        out = np.zeros(self.n, np.uint32)
+        self._check(self.lib.bdx_bamdec_fetch_clips(self.h, 0, self.n, out.ctypes.data), "bdx_bamdec_fetch_clips")
+        return out
+
     def close(self):
         if self.h:
             self.lib.bdx_bamdec_destroy(self.h)
@@ -328,17 +337,20 @@ def merge_decoded(sink, decoders, src_file, src_index):
 
 
 def decode_file(path, rg_ids=(), rg_lib=(), fallback_lib=0, bam_index=0, region=None, piece_blocks=512, ring_bytes=0, sink=None, device=0,
-                batch_blocks=0, ahead=1, exclude=None):
-    """whole file -> (columns or None with a sink, target names, decoder statistics; with exclude the statistics carry "excluded")"""
+                batch_blocks=0, ahead=1, exclude=None, clips=False):
+    """whole file -> (columns or None with a sink, target names, decoder statistics; with exclude the statistics carry "excluded");
+    clips=True without a sink: the columns carry "clip", the records' clip words"""
     data = np.fromfile(path, dtype=np.uint8)
     members = scan_bgzf(data)
     names, lens, k, off = bam_header(data, members)
     d = BamDecoder(len(names), sink=sink, device=device, bam_index=bam_index, rg_ids=rg_ids, rg_lib=rg_lib, fallback_lib=fallback_lib,
-                   region=region, first_record_offset=off, ring_bytes=ring_bytes, batch_blocks=batch_blocks, exclude=exclude)
+                   region=region, first_record_offset=off, ring_bytes=ring_bytes, batch_blocks=batch_blocks, exclude=exclude, clips=clips)
     try:
         d.feed(data, members[k:], piece_blocks, ahead=ahead)
         d.finish()
         cols = d.fetch() if sink is None else None
+        if cols is not None and clips:
+            cols["clip"] = d.fetch_clips()
         stats = d.stats()
         if exclude is not None:
             stats["excluded"] = d.excluded()

@@ -133,12 +133,45 @@ def _fixed_records(soa, lo, hi, L, rg, rng, names=None, ref=None):
     return rec
 
 
-def write_bam(path, soa, targets, rg="rg1", readlen=None, level=1, seed=0, names=None, threads=None, chunk=500_000, index=False, realistic=False):
+_CIGAR_OPS = "MIDNSHP=X"
+
+
+def cigar_words(cigar):
+    """a CIGAR -- a string like '5S85M', or a sequence of (length, operation letter) -- as BAM's little-endian words (len << 4 | op)"""
+    if isinstance(cigar, str):
+        ops, num = [], ""
+        for ch in cigar:
+            if ch.isdigit():
+                num += ch
+            else:
+                ops.append((int(num), ch))
+                num = ""
+        cigar = ops
+    return b"".join(struct.pack("<I", (int(n) << 4) | _CIGAR_OPS.index(op)) for n, op in cigar)
+
+
+def _with_cigars(rec, lname, cigars):
+    """the fixed-size records of _fixed_records with each one's single CIGAR word replaced by its own CIGAR: the bytes of the records, now
+    of different sizes (n_cigar_op and block_size follow; l_seq and the bases stay as they are)"""
+    at = 36 + lname
+    out = bytearray()
+    for row, cg in zip(rec, cigars):
+        w = cigar_words(cg)
+        body = bytearray(row[4:at].tobytes() + w + row[at + 4:].tobytes())
+        body[12:14] = struct.pack("<H", len(w) // 4)
+        out += struct.pack("<i", len(body)) + body
+    return bytes(out)
+
+
+def write_bam(path, soa, targets, rg="rg1", readlen=None, level=1, seed=0, names=None, threads=None, chunk=500_000, index=False, realistic=False,
+              cigars=None):
     """soa: dict with tid,pos,mtid,mpos,isize,flag,qlen,mapq (+name_key used to derive the read names).
     index=True also writes <path>.bai: per sequence ONE chunk (first record .. behind the last, in the root bin -- legal, if coarser
     than samtools') and the linear index of 16 kb windows, vectorised (the records have one size, so every virtual offset follows
     from the compressed sizes of the blocks).
     Every record gets `readlen` random bases / qualities (default: soa['qlen'][0]), a 100M-style CIGAR and RG:Z:<rg>.
+    cigars: a CIGAR per record instead (cigar_words: a string, or (length, letter) pairs; '' for none) -- the records then differ in
+    size, they are put together one by one (small inputs), and index=True is refused.  Without it the file is byte for byte what it was.
     realistic=True: bases drawn from a seeded random REFERENCE at the read's position (overlapping reads share sequence) and qualities in
     four bins (class Reference, _realistic_payload); with level=6 -- samtools' default, bgzf.c -- the file compresses like a real 30x BAM.
     Records are built and deflated `chunk` at a time on `threads` threads (numpy and zlib release the GIL), so a
@@ -146,6 +179,10 @@ def write_bam(path, soa, targets, rg="rg1", readlen=None, level=1, seed=0, names
     import os
     from concurrent.futures import ThreadPoolExecutor
     n = len(soa["tid"])
+    if cigars is not None and index:
+        raise ValueError("write_bam: no index for records of different sizes (cigars=)")
+    if cigars is not None and len(cigars) != n:
+        raise ValueError("write_bam: %d CIGARs for %d records" % (len(cigars), n))
     L = int(readlen if readlen is not None else (soa["qlen"][0] if n else 100))
     text = "@HD\tVN:1.0\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (t, 300000000) for t in targets) + \
            "".join("@RG\tID:%s\tLB:lib%d\tSM:s\n" % (r, i + 1) for i, r in enumerate([rg] if isinstance(rg, str) else rg))
@@ -157,7 +194,12 @@ def write_bam(path, soa, targets, rg="rg1", readlen=None, level=1, seed=0, names
 
     def piece(i):
         lo, hi = i * chunk, min(n, (i + 1) * chunk)
-        raw = _fixed_records(soa, lo, hi, L, rg, np.random.default_rng([seed, i]), names, ref).tobytes()
+        raw = _fixed_records(soa, lo, hi, L, rg, np.random.default_rng([seed, i]), names, ref)
+        if cigars is None:
+            raw = raw.tobytes()
+        else:
+            lname = 17 if names is None else max(len(x) for x in names) + 1
+            raw = _with_cigars(raw, lname, cigars[lo:hi])
         blocks = [_bgzf_block(raw[j:j + 65280], level) for j in range(0, len(raw), 65280)]
         return b"".join(blocks), [len(b) for b in blocks], len(raw)
 
@@ -178,7 +220,7 @@ def write_bam(path, soa, targets, rg="rg1", readlen=None, level=1, seed=0, names
                 data, sizes, raw_len = window.pop(0).result()
                 chunk_coff.append(f.tell())
                 chunk_blocks.append(sizes)
-                if raw_len:
+                if raw_len and cigars is None:
                     rec_bytes = raw_len // (min(n, (len(chunk_coff)) * chunk) - (len(chunk_coff) - 1) * chunk)
                 f.write(data)
         end_coff = f.tell()
@@ -267,7 +309,8 @@ def _write_bai(path, n_ref, entries):
 
 def write_bam_records(path, recs, targets, rgs=(), level=1, seed=0, index=False):
     """Generic (slow, per-record) writer for small test inputs.  recs: list of dicts with tid,pos,mtid,mpos,isize,flag,
-    qlen,mapq,name and optional rg (str or ''), am (int or None); random bases/qualities of length qlen.
+    qlen,mapq,name and optional rg (str or ''), am (int or None), cigar (cigar_words: instead of <qlen>M; the index then takes the
+    record's end from it); random bases/qualities of length qlen.
     index=True also writes <path>.bai (bins + linear index, BAM specification section 5.2)."""
     rng = np.random.default_rng(seed)
     text = "@HD\tVN:1.0\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % (t, 300000000) for t in targets) + \
@@ -290,14 +333,16 @@ def write_bam_records(path, recs, targets, rgs=(), level=1, seed=0, index=False)
         if r.get("rg"):
             aux += b"RGZ" + r["rg"].encode() + b"\0"
         aux += b"NMi" + struct.pack("<i", 1)
-        ncig = 1 if L else 0
+        cig = cigar_words(r["cigar"]) if r.get("cigar") is not None else (struct.pack("<I", (L << 4) | 0) if L else b"")
+        ncig = len(cig) // 4
         body = struct.pack("<iiBBHHHiiii", int(r["tid"]), int(r["pos"]), len(name), int(r["mapq"]), 0, ncig, int(r["flag"]), L,
-                           int(r["mtid"]), int(r["mpos"]), int(r["isize"])) + name + (struct.pack("<I", (L << 4) | 0) if ncig else b"") + \
+                           int(r["mtid"]), int(r["mpos"]), int(r["isize"])) + name + cig + \
             seq + qual + aux
         start = len(out)
         out += struct.pack("<i", len(body)) + body
         if int(r["tid"]) >= 0:
-            spans.append((int(r["tid"]), int(r["pos"]), int(r["pos"]) + max(L, 1), start, len(out)))
+            ref_len = L if r.get("cigar") is None else sum(w >> 4 for w, in struct.iter_unpack("<I", cig) if (w & 15) in (0, 2, 3, 7, 8))
+            spans.append((int(r["tid"]), int(r["pos"]), int(r["pos"]) + max(ref_len, 1), start, len(out)))
     raw = bytes(out)
     coffs = []
     with open(path, "wb") as f:

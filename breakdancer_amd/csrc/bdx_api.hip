@@ -29,6 +29,7 @@
 #include "bdx_scan.h"
 #include "bdx_walk.h"
 #include "bdx_bam_dev.h"
+#include "bdx_clip.h"
 #include "bdx_estimate.h"
 #include "bdx_mini.h"
 
@@ -86,6 +87,12 @@ struct bdx_ctx {
     DevBuf b_tid, b_pos, b_mtid, b_mpos, b_isize, b_flag, b_qlen, b_mapq, b_lib, b_bam, b_key, b_check;
     bool groups_in_hbm = false;       // (sharded runs) the join's pair groups stay in HBM instead of pinned host memory
     bool use_check = false;           // bdx_use_name_check: every batch carries a second hash of the read name, mates must agree in it too
+    bool use_clips = false;           // bdx_use_clips: the store has a column of clip words (b_clip: [cap], zero where nothing was put)
+    DevBuf b_clip;
+    // bdx_put_clips: the caller's words go through pinned buffers of the context's own, so that the call returns without waiting for the copy
+    struct ClipStage { PinBuf buf; Event done; bool busy = false; };
+    ClipStage clip_ring[4];
+    int clip_next = 0;
 
     // stage buffers
     DevBuf b_libs, b_cls, b_tile_tot, b_tile_pre, b_tile_mono, b_blk_cnt, b_cnt, b_p1, b_fold, b_stash, b_chunk_tot, b_counts;
@@ -282,6 +289,15 @@ int alloc_reads(bdx_ctx* c, size_t cap) {
         col.b->release();
         *col.b = std::move(nb);
         *col.slot = col.b->p;
+    }
+    if (c->use_clips) {   // the clip words: rows nobody has put stay 0
+        DevBuf nb;
+        HIPCHK(c, nb.ensure(cap * 4));
+        HIPCHK(c, hipMemsetAsync(nb.p, 0, cap * 4, c->stream));
+        if (c->n) HIPCHK(c, hipMemcpyAsync(nb.p, c->b_clip.p, c->n * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->b_clip.release();
+        c->b_clip = std::move(nb);
     }
     c->cap = cap;
     return BDX_OK;
@@ -587,6 +603,10 @@ int bdx_reset_reads(bdx_ctx* c) {
         c->cap = 0;
         c->adopted = false;
     }
+    if (c->use_clips && c->b_clip.p) {   // the next load's rows start from 0 again: all of them (a decoder that gave up may have written beyond n)
+        HIPCHK(c, hipMemsetAsync(c->b_clip.p, 0, c->cap * 4, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     c->n = 0;
     c->ran = false;
     c->dup_done = false;
@@ -603,6 +623,7 @@ int bdx_reset_reads(bdx_ctx* c) {
 int bdx_set_device_reads(bdx_ctx* c, const bdx_batch* b) {
     if (!c || !b) return BDX_EINVAL;
     if (c->n && !c->adopted) return fail(c, BDX_ESTATE, "context already holds pushed reads");
+    if (c->use_clips) return fail(c, BDX_ESTATE, "an adopted store cannot carry clip words (bdx_use_clips is on)");
     const void* ptrs[] = {b->tid, b->pos, b->mtid, b->mpos, b->isize, b->flag, b->qlen, b->mapq, b->lib, b->bam, b->name_key,
                           c->use_check ? (const void*)b->name_check : (const void*)b->name_key};
     for (const void* p : ptrs)
@@ -2137,6 +2158,65 @@ int bdx_use_name_check(bdx_ctx* c, int on) {
     return BDX_OK;
 }
 
+uint32_t bdx_clip_word(const uint32_t* cigar, uint32_t n_cigar, int32_t l_seq, uint32_t flag) {
+    return cigar || !n_cigar ? clip_word((const uint8_t*)cigar, n_cigar, l_seq, flag) : 0u;
+}
+
+int bdx_use_clips(bdx_ctx* c, int on) {
+    if (!c) return BDX_EINVAL;
+    if ((on != 0) == c->use_clips) return BDX_OK;
+    if (c->n) return fail(c, BDX_ESTATE, "the clip column is switched while the context holds no reads");
+    if (on && c->adopted) return fail(c, BDX_ESTATE, "an adopted store cannot carry clip words");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->use_clips = on != 0;
+    if (c->use_clips && c->cap) {
+        HIPCHK(c, c->b_clip.ensure(c->cap * 4));
+        HIPCHK(c, hipMemsetAsync(c->b_clip.p, 0, c->cap * 4, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (!c->use_clips) c->b_clip.release();
+    return BDX_OK;
+}
+
+int bdx_put_clips(bdx_ctx* c, size_t first, const uint32_t* clip, size_t n) {
+    if (!c) return BDX_EINVAL;
+    if (!c->use_clips) return fail(c, BDX_ESTATE, "the context has no clip column (bdx_use_clips)");
+    if (first > c->n || n > c->n - first) return fail(c, BDX_EINVAL, "clip words for records the context does not hold");
+    if (n == 0) return BDX_OK;
+    if (!clip) return fail(c, BDX_EINVAL, "null array");
+    HIPCHK(c, hipSetDevice(c->device));
+    // Through a pinned buffer of the context's (a ring of four, like the batches'): `clip` is free when the call returns and nobody waits
+    // for the copy, which goes on the copy stream behind the batches' own; the compute stream waits for it by an event, so every later
+    // run or query sees the rows.
+    bdx_ctx::ClipStage& st = c->clip_ring[c->clip_next];
+    c->clip_next = (c->clip_next + 1) % 4;
+    if (st.busy) {
+        HIPCHK(c, hipEventSynchronize(st.done));
+        st.busy = false;
+    }
+    if (!st.done) HIPCHK(c, st.done.create(hipEventDisableTiming));
+    HIPCHK(c, st.buf.ensure(n * 4));
+    memcpy(st.buf.p, clip, n * 4);
+    HIPCHK(c, hipMemcpyAsync(c->b_clip.as<uint32_t>() + first, st.buf.p, n * 4, hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(c, hipEventRecord(st.done, c->copy_stream));
+    st.busy = true;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, st.done, 0));
+    return BDX_OK;
+}
+
+int bdx_get_clips(bdx_ctx* c, uint32_t* out, size_t cap) {
+    if (!c) return BDX_EINVAL;
+    if (!c->use_clips) return fail(c, BDX_ESTATE, "the context has no clip column (bdx_use_clips)");
+    const size_t n = std::min(cap, c->n);
+    if (n == 0) return BDX_OK;
+    if (!out) return fail(c, BDX_EINVAL, "null array");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->copy_stream) HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out, c->b_clip.p, n * 4, hipMemcpyDeviceToHost));
+    return BDX_OK;
+}
+
 int bdx_set_mark_duplicates(bdx_ctx* c, int on) {
     if (!c) return BDX_EINVAL;
     if ((on != 0) == c->mark_dup) return BDX_OK;
@@ -2381,6 +2461,22 @@ int bdx_site_end_quality(bdx_ctx* c, const bdx_site* sites, const uint8_t* end, 
     });
 }
 
+int bdx_site_clip_peaks(bdx_ctx* c, const bdx_site* sites, const uint8_t* end, size_t n, int32_t window, int32_t min_clip, bdx_clip_peaks* out) {
+    if (!c) return BDX_EINVAL;
+    if (!c->use_clips) return fail(c, BDX_ESTATE, "the context has no clip column (bdx_use_clips)");
+    bool none;
+    BDX_TRY(check_site_call(c, sites, n, window, end && out, &none));
+    if (none) return BDX_OK;
+    if (window > BDX_CLIP_WINDOW_MAX) return fail(c, BDX_EINVAL, "window > " + std::to_string(BDX_CLIP_WINDOW_MAX));
+    if (min_clip < 1 || min_clip > 255) return fail(c, BDX_EINVAL, "min_clip < 1 or min_clip > 255");
+    for (size_t i = 0; i < n; ++i)
+        if (end[i] != 1 && end[i] != 2) return fail(c, BDX_EINVAL, "query " + std::to_string(i) + ": end is neither 1 nor 2");
+    const size_t sbytes = n * sizeof(bdx_site);
+    return run_query(c, {{sites, sbytes}, {end, n}}, out, n * sizeof(bdx_clip_peaks), [&](const char* in, void* results, hipStream_t s) {
+        launch_kp(KpParams{store_view(c), c->b_clip.as<uint32_t>(), (const KsSite*)in, (const uint8_t*)(in + sbytes), (uint32_t)n, window, min_clip, (KpPeaks*)results}, s);
+    });
+}
+
 // Passing read starts inside given intervals (KR, kr_depth.hip): the table of passing records in front of every chunk of the store is built
 // by the call itself, in a scratch buffer, ahead of the queries on the same stream; "depth_plain" answers without one.
 int bdx_count_interval_reads(bdx_ctx* c, const bdx_interval* iv, size_t n, int by_library, uint32_t* counts) {
@@ -2540,7 +2636,7 @@ int bdx_set_process_option(const char* name, int value) {
 int bdx_warm_up(int device) {
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
     warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k9(nullptr);
-    warm_kx(nullptr); warm_kq(nullptr); warm_kr(nullptr);
+    warm_kx(nullptr); warm_kq(nullptr); warm_kr(nullptr); warm_kp(nullptr);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? BDX_OK : BDX_EHIP;
 }
 

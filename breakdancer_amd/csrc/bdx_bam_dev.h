@@ -64,6 +64,7 @@ struct RawColumns {        // columns of every record of a piece, before the rea
     uint8_t *mapq, *lib, *keep;
     uint64_t* key;
     uint64_t* check;
+    uint32_t* clip;        // nullptr: no clip words are kept (bdx_use_clips)
 };
 
 struct DstColumns {        // where the kept records go (the context's resident store, or the decoder's own buffers)
@@ -72,6 +73,7 @@ struct DstColumns {        // where the kept records go (the context's resident 
     uint8_t *mapq, *lib, *bam;
     uint64_t* key;
     uint64_t* check;       // nullptr: the destination keeps no second name hash
+    uint32_t* clip;        // nullptr: ... and no clip words
 };
 
 struct PieceState {        // running state of one file's decode, in device memory; one instance per decoder
@@ -109,6 +111,7 @@ struct GatherSource {      // a decoder's own columns
     const uint16_t *flag, *qlen;
     const uint8_t *mapq, *lib, *bam;
     const uint64_t *key, *check;
+    const uint32_t* clip;  // read only when the destination keeps clip words
     uint64_t n;
 };
 struct GatherSources { GatherSource s[kMaxGatherSources]; int k; };

@@ -115,6 +115,7 @@ struct bdx_bamdec {
     DevBuf d_cb, d_offs, d_base, d_scan, d_state;
     size_t rec_cap_blk = 0;             // members d_cb / d_offs / d_base are sized for
     DevBuf r_tid, r_pos, r_mtid, r_mpos, r_isize, r_flag, r_qlen, r_mapq, r_lib, r_keep, r_key, r_check;
+    DevBuf r_clip;                      // (clips only)
     uint32_t raw_cap = 0;
     // read groups
     DevBuf d_rg_hash, d_rg_off, d_rg_chars, d_rg_lib;
@@ -127,6 +128,8 @@ struct bdx_bamdec {
     uint8_t bam_index = 0;
     // own destination (no sink)
     DevBuf o_tid, o_pos, o_mtid, o_mpos, o_isize, o_flag, o_qlen, o_mapq, o_lib, o_bam, o_key, o_check;
+    DevBuf o_clip;                // (clips only)
+    bool clips = false;           // the records' clip words are kept: the sink has bdx_use_clips on, or record_mode bit 4 says the gather target has
     size_t own_cap = 0;
     // progress record in pinned memory: [0] kept records, [1] error | past_region << 8 | redo << 32, [2] raw records, [3] sequence
     PinBuf h_progress;
@@ -181,12 +184,14 @@ DstColumns bam_dst(bdx_bamdec* d, uint64_t* cap) {
         c.isize = (int32_t*)k->d.isize; c.flag = (uint16_t*)k->d.flag; c.qlen = (uint16_t*)k->d.qlen; c.mapq = (uint8_t*)k->d.mapq;
         c.lib = (uint8_t*)k->d.lib; c.bam = (uint8_t*)k->d.bam; c.key = (uint64_t*)k->d.key;
         c.check = (uint64_t*)k->d.check;   // (null unless bdx_use_name_check)
+        c.clip = k->use_clips ? k->b_clip.as<uint32_t>() : nullptr;
         *cap = k->cap;
     } else {
         c.tid = d->o_tid.as<int32_t>(); c.pos = d->o_pos.as<int32_t>(); c.mtid = d->o_mtid.as<int32_t>(); c.mpos = d->o_mpos.as<int32_t>();
         c.isize = d->o_isize.as<int32_t>(); c.flag = d->o_flag.as<uint16_t>(); c.qlen = d->o_qlen.as<uint16_t>(); c.mapq = d->o_mapq.as<uint8_t>();
         c.lib = d->o_lib.as<uint8_t>(); c.bam = d->o_bam.as<uint8_t>(); c.key = d->o_key.as<uint64_t>();
         c.check = d->o_check.as<uint64_t>();
+        c.clip = d->clips ? d->o_clip.as<uint32_t>() : nullptr;
         *cap = d->own_cap;
     }
     return c;
@@ -198,9 +203,10 @@ int bam_own_reserve(bdx_bamdec* d, size_t cap, uint64_t keep_records) {
     cap = round_up(cap, 1024);
     struct Col { DevBuf* b; size_t esz; };
     Col cols[] = {{&d->o_tid, 4}, {&d->o_pos, 4}, {&d->o_mtid, 4}, {&d->o_mpos, 4}, {&d->o_isize, 4}, {&d->o_flag, 2}, {&d->o_qlen, 2},
-                  {&d->o_mapq, 1}, {&d->o_lib, 1}, {&d->o_bam, 1}, {&d->o_key, 8}, {&d->o_check, 8}};
+                  {&d->o_mapq, 1}, {&d->o_lib, 1}, {&d->o_bam, 1}, {&d->o_key, 8}, {&d->o_check, 8}, {&d->o_clip, 4}};
     if (d->own_cap) BHIP(d, hipStreamSynchronize(d->s_rec));
     for (Col& c : cols) {
+        if (c.b == &d->o_clip && !d->clips) continue;
         DevBuf nb;
         BHIP(d, nb.ensure(cap * c.esz));
         if (keep_records && c.b->p) BHIP(d, hipMemcpy(nb.p, c.b->p, keep_records * c.esz, hipMemcpyDeviceToDevice));
@@ -302,6 +308,7 @@ int bam_record_stage(bdx_bamdec* d, BamPiece& p, const BamPiece* next, int is_la
         BHIP(d, d->r_tid.ensure(cap * 4)); BHIP(d, d->r_pos.ensure(cap * 4)); BHIP(d, d->r_mtid.ensure(cap * 4)); BHIP(d, d->r_mpos.ensure(cap * 4));
         BHIP(d, d->r_isize.ensure(cap * 4)); BHIP(d, d->r_flag.ensure(cap * 2)); BHIP(d, d->r_qlen.ensure(cap * 2)); BHIP(d, d->r_mapq.ensure(cap));
         BHIP(d, d->r_lib.ensure(cap)); BHIP(d, d->r_keep.ensure(cap)); BHIP(d, d->r_key.ensure(cap * 8)); BHIP(d, d->r_check.ensure(cap * 8));
+        if (d->clips) BHIP(d, d->r_clip.ensure(cap * 4));
         BHIP(d, d->d_scan.ensure((cap / 256 + 8) * 4));
         d->raw_cap = (uint32_t)cap;
     }
@@ -358,7 +365,7 @@ int bam_record_stage(bdx_bamdec* d, BamPiece& p, const BamPiece* next, int is_la
                      p.wrapped ? p.ring_beg : 0, s);
     RawColumns raw{d->r_tid.as<int32_t>(), d->r_pos.as<int32_t>(), d->r_mtid.as<int32_t>(), d->r_mpos.as<int32_t>(), d->r_isize.as<int32_t>(),
                    d->r_flag.as<uint16_t>(), d->r_qlen.as<uint16_t>(), d->r_mapq.as<uint8_t>(), d->r_lib.as<uint8_t>(), d->r_keep.as<uint8_t>(),
-                   d->r_key.as<uint64_t>(), d->r_check.as<uint64_t>()};
+                   d->r_key.as<uint64_t>(), d->r_check.as<uint64_t>(), d->clips ? d->r_clip.as<uint32_t>() : nullptr};
     launch_kb_extract(u, blocks, nblk, cb, offs, base, d->rg, d->filt, d->exclude, raw, st, s);
     uint64_t dst_cap = 0;
     DstColumns dst = bam_dst(d, &dst_cap);
@@ -398,6 +405,7 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
     d->bam_index = (uint8_t)p->bam_index;
     d->filt.only_tid = p->only_tid; d->filt.beg = p->region_beg; d->filt.end = p->region_end; d->filt.n_targets = p->n_targets;
     d->filt.keep_all = (p->record_mode & 1) ? 1 : 0; d->filt.mapq_only = (p->record_mode & 2) ? 1 : 0;
+    d->clips = sink ? sink->use_clips : (p->record_mode & 4) != 0;
     std::unique_ptr<bdx_bamdec, void (*)(bdx_bamdec*)> owner(d, bdx_bamdec_destroy);   // (until the decoder is handed out: a failure below destroys it)
     static const bool create_trace = getenv("BDX_BAMDEC_TRACE") != nullptr;   // (where a decoder's set-up time goes, on stderr)
     const auto t_c0 = std::chrono::steady_clock::now();
@@ -516,7 +524,7 @@ int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* 
                 for (DevBuf* b : {&d->r_tid, &d->r_pos, &d->r_mtid, &d->r_mpos, &d->r_isize}) ok = ok && b->ensure(cap * 4) == hipSuccess;
                 ok = ok && d->r_flag.ensure(cap * 2) == hipSuccess && d->r_qlen.ensure(cap * 2) == hipSuccess && d->r_mapq.ensure(cap) == hipSuccess &&
                      d->r_lib.ensure(cap) == hipSuccess && d->r_keep.ensure(cap) == hipSuccess && d->r_key.ensure(cap * 8) == hipSuccess && d->r_check.ensure(cap * 8) == hipSuccess &&
-                     d->d_scan.ensure((cap / 256 + 8) * 4) == hipSuccess;
+                     (!d->clips || d->r_clip.ensure(cap * 4) == hipSuccess) && d->d_scan.ensure((cap / 256 + 8) * 4) == hipSuccess;
                 if (ok) d->raw_cap = (uint32_t)cap;
                 if (ok && d->d_cb.ensure(nbk * sizeof(ChainBlock)) == hipSuccess && d->d_offs.ensure(nbk * kRecSlots * 2) == hipSuccess && d->d_base.ensure((nbk + 2) * 4) == hipSuccess)
                     d->rec_cap_blk = nbk;
@@ -897,6 +905,19 @@ int bdx_bamdec_fetch(bdx_bamdec* d, uint64_t first, uint64_t n, const bdx_batch_
     return BDX_OK;
 }
 
+int bdx_bamdec_fetch_clips(bdx_bamdec* d, uint64_t first, uint64_t n, uint32_t* out) {
+    if (!d) return BDX_EINVAL;
+    if (d->sink) return bfail(d, BDX_ESTATE, "the records went into the sink context");
+    if (!d->clips) return bfail(d, BDX_ESTATE, "the decoder keeps no clip words");
+    if (!d->finished) return bfail(d, BDX_ESTATE, "bdx_bamdec_finish first");
+    if (first > d->confirmed || n > d->confirmed - first) return bfail(d, BDX_EINVAL, "range beyond the decoded records");
+    if (!n) return BDX_OK;
+    if (!out) return BDX_EINVAL;
+    BHIP(d, hipSetDevice(d->device));
+    BHIP(d, hipMemcpy(out, d->o_clip.as<uint32_t>() + first, n * 4, hipMemcpyDeviceToHost));
+    return BDX_OK;
+}
+
 namespace {
 
 // the C ABI's intervals checked and turned into the table of bdx_exclude.h
@@ -996,6 +1017,8 @@ int gather_decoded(bdx_ctx* c, bdx_bamdec* const* decs, int k, const uint8_t* sr
         g.tid = d->o_tid.as<int32_t>(); g.pos = d->o_pos.as<int32_t>(); g.mtid = d->o_mtid.as<int32_t>(); g.mpos = d->o_mpos.as<int32_t>();
         g.isize = d->o_isize.as<int32_t>(); g.flag = d->o_flag.as<uint16_t>(); g.qlen = d->o_qlen.as<uint16_t>(); g.mapq = d->o_mapq.as<uint8_t>();
         g.lib = d->o_lib.as<uint8_t>(); g.bam = d->o_bam.as<uint8_t>(); g.key = d->o_key.as<uint64_t>(); g.check = d->o_check.as<uint64_t>();
+        if (c->use_clips && !d->clips) return fail(c, BDX_EINVAL, "the context keeps clip words and a decoder has none (bdx_bamdec_params::record_mode bit 4)");
+        g.clip = d->clips ? d->o_clip.as<uint32_t>() : nullptr;
         g.n = d->confirmed;
         total += d->confirmed;
     }
@@ -1015,6 +1038,7 @@ int gather_decoded(bdx_ctx* c, bdx_bamdec* const* decs, int k, const uint8_t* sr
         dst.isize = (int32_t*)c->d.isize + base; dst.flag = (uint16_t*)c->d.flag + base; dst.qlen = (uint16_t*)c->d.qlen + base; dst.mapq = (uint8_t*)c->d.mapq + base;
         dst.lib = (uint8_t*)c->d.lib + base; dst.bam = (uint8_t*)c->d.bam + base; dst.key = (uint64_t*)c->d.key + base;
         dst.check = c->d.check ? (uint64_t*)c->d.check + base : nullptr;
+        dst.clip = c->use_clips ? c->b_clip.as<uint32_t>() + base : nullptr;
         launch_kb_gather(src, d_file.as<uint8_t>(), d_index.as<uint32_t>(), n, dst, d_err.as<uint32_t>(), s);
         e = hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, s);
     }

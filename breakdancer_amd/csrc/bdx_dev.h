@@ -265,6 +265,24 @@ struct KmParams {
     KmQuality* out;                     // [nq]
 };
 
+// KP (kp_clip.hip): the piles of clipped reads around one end of given SV sites (bdx_site_clip_peaks)
+struct KpPeaks {                        // = bdx_clip_peaks (include/bdx.h)
+    uint32_t n_left, n_right;           // observations per side
+    int32_t pos_left, pos_right;        // the X most of them share (1-based) ...
+    uint32_t peak_left, peak_right;     // ... and how many do; both 0 with n == 0
+};
+struct KpParams {
+    StoreView st;
+    const uint32_t* clip;               // the clip words (bdx_use_clips); read only for records that pass
+    const KsSite* sites;
+    const uint8_t* end;                 // [nq] 1 or 2: the end of sites[q] that is asked
+    uint32_t nq;
+    int32_t window;                     // 0..BDX_CLIP_WINDOW_MAX: sizes the launch's LDS
+    int32_t min_clip;                   // 1..255
+    KpPeaks* out;                       // [nq]
+};
+void launch_kp(const KpParams& p, hipStream_t s);
+
 // KR (kr_depth.hip): passing read starts inside given intervals, per interval and key (bdx_count_interval_reads)
 struct KrInterval {                     // = bdx_interval (include/bdx.h)
     int32_t tid, beg, end;              // 0-based, half-open

@@ -754,7 +754,7 @@ struct StatWords {
         first = o; o += (size_t)ntids * 3;           // every chromosome's first anomalous read
         mt = o; o += (size_t)world * ntids;          // [rank][mate chromosome]: inter-chromosomal reads
         cen = o; o += (size_t)world * world;         // [rank][owner]: census records
-        flags = o; o += 3;                           // supporting reads wanted | name check on | name check off
+        flags = o; o += 5;                           // supporting reads wanted | name check on | name check off | clip words on | clip words off
         words = o;
     }
 };
@@ -1064,6 +1064,7 @@ int DistRun::pass1_and_counts(std::vector<uint64_t>& v1) {
     }
     v1[W.flags] = d->collect_support ? 1 : 0;
     if (C->n) v1[W.flags + (C->use_check ? 1 : 2)] = 1;
+    if (C->n) v1[W.flags + (C->use_clips ? 3 : 4)] = 1;
     return BDX_OK;
 }
 
@@ -1075,6 +1076,7 @@ int DistRun::agree_statistics(std::vector<uint64_t>& v1, Stats* out) {
     A.want_support = v1[W.flags];
     if (A.want_support != 0 && A.want_support != (uint64_t)world) return dfail(d, BDX_EINVAL, "bdx_dist_set_collect_support is set on some ranks only");
     if (v1[W.flags + 1] && v1[W.flags + 2]) return dfail(d, BDX_EINVAL, "bdx_use_name_check is set on some ranks' contexts only");
+    if (v1[W.flags + 3] && v1[W.flags + 4]) return dfail(d, BDX_EINVAL, "bdx_use_clips is set on some ranks' contexts only");
     A.with_check = v1[W.flags + 1] != 0;
     A.owner.assign(ntids, -1);
     for (int t = 0; t < ntids; ++t) {

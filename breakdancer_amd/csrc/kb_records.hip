@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bdx_bam_dev.h"
+#include "bdx_clip.h"
 
 namespace bdx {
 
@@ -330,6 +331,8 @@ __global__ __launch_bounds__(64) void kb_extract_kernel(const uint8_t* __restric
         hash_name_pair(p + 32, l_read_name ? l_read_name - 1 : 0, nk, nc);
         raw.key[r] = nk;
         raw.check[r] = nc;
+        // (uniform; the CIGAR's 4 n_cigar bytes lie inside the record: the size test above)
+        if (raw.clip) raw.clip[r] = clip_word(p + 32 + l_read_name, n_cigar, l_qseq, flag);
     }
     if (ex.ntids) {   // (uniform; the wave is whole again behind the loop) the lanes' counts summed bit by bit: ballot + popcount, one atomic per wave
         uint32_t total = 0;
@@ -406,6 +409,7 @@ __global__ __launch_bounds__(kCompactThreads) void kb_compact_scatter_kernel(Raw
     dst.flag[d] = raw.flag[i]; dst.qlen[d] = raw.qlen[i]; dst.mapq[d] = raw.mapq[i]; dst.lib[d] = raw.lib[i]; dst.bam[d] = bam_index;
     dst.key[d] = raw.key[i];
     if (dst.check) dst.check[d] = raw.check[i];
+    if (dst.clip) dst.clip[d] = raw.clip[i];
 }
 
 __global__ void kb_compact_finish_kernel(const uint32_t* __restrict__ wg_cnt, uint32_t nwg_cap, PieceState* st, volatile uint64_t* progress, uint64_t sequence) {
@@ -442,6 +446,7 @@ __global__ __launch_bounds__(256) void kb_gather_kernel(GatherSources src, const
     dst.flag[i] = g.flag[j]; dst.qlen[i] = g.qlen[j]; dst.mapq[i] = g.mapq[j]; dst.lib[i] = g.lib[j]; dst.bam[i] = g.bam[j];
     dst.key[i] = g.key[j];
     if (dst.check) dst.check[i] = g.check[j];
+    if (dst.clip) dst.clip[i] = g.clip[j];
 }
 
 void launch_kb_gather(const GatherSources& src, const uint8_t* src_file, const uint32_t* src_index, uint64_t n, DstColumns dst, uint32_t* err, hipStream_t s) {

@@ -7,6 +7,8 @@
 #include <stdexcept>
 #include <thread>
 
+#include "../csrc/bdx_clip.h"
+
 namespace bdhost {
 
 namespace {
@@ -360,6 +362,7 @@ void BamReader::parse_record(const uint8_t* rec, BamRecord& r) {
             if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) endp += (int32_t)len;  // M D N = X consume the reference
         }
         r.end_pos = n_cigar ? endp : r.pos + 1;
+        r.clip = bdx::clip_word(cg, n_cigar, r.l_qseq, r.flag);
     }
     r.seq = q;
     q += ((size_t)r.l_qseq + 1) / 2;

@@ -25,6 +25,7 @@ struct BamRecord {
     const uint8_t* seq;     // 4-bit packed bases, (l_qseq+1)/2 bytes
     const uint8_t* qual;    // l_qseq bytes
     int32_t end_pos;        // bam_calend: pos + reference bases consumed by the CIGAR (pos + 1 without a CIGAR)
+    uint32_t clip;          // the clip word of the CIGAR (include/bdx.h bdx_clip_word; csrc/bdx_clip.h, the device decoder's function)
     uint64_t name_key;      // hash_name(qname)
     uint64_t rg_key;        // hash_name(rg), 0 without an RG tag: lets a consumer recognise runs of one read group without
                             // touching the record's bytes (they were decoded on another core)

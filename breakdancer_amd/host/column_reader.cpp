@@ -401,6 +401,7 @@ void ColumnReader::decode_piece(Scratch& sc, Piece& p, bool known_start, uint64_
         const size_t guess = own / 180 + 16;
         c.tid.reserve(guess); c.pos.reserve(guess); c.mtid.reserve(guess); c.mpos.reserve(guess); c.isize.reserve(guess);
         c.flag.reserve(guess); c.qlen.reserve(guess); c.mapq.reserve(guess); c.lib.reserve(guess); c.name_key.reserve(guess); c.name_check.reserve(guess);
+        c.clip.reserve(guess);
     }
     while (pos < own) {
         while (pos + 4 > sc.filled)
@@ -477,6 +478,7 @@ void ColumnReader::decode_piece(Scratch& sc, Piece& p, bool known_start, uint64_
         c.lib.push_back(lib);
         c.name_key.push_back(hash_name(r.qname, r.l_qname));
         c.name_check.push_back(check_name(r.qname, r.l_qname));
+        c.clip.push_back(r.clip);
     }
     p.next_abs = p.abs_begin + pos;
 }

@@ -94,10 +94,11 @@ struct ColumnChunk {
     std::vector<uint16_t> flag, qlen;
     std::vector<uint8_t> mapq, lib;
     std::vector<uint64_t> name_key, name_check;
+    std::vector<uint32_t> clip;   // the records' clip words (include/bdx.h bdx_clip_word), beside the batch's columns
     size_t size() const { return tid.size(); }
     void clear() {
         tid.clear(); pos.clear(); mtid.clear(); mpos.clear(); isize.clear(); flag.clear(); qlen.clear(); mapq.clear(); lib.clear();
-        name_key.clear(); name_check.clear();
+        name_key.clear(); name_check.clear(); clip.clear();
     }
 };
 

@@ -162,6 +162,7 @@ bdx_bamdec* open_decoder(const DecodeJob& job, const ColumnReader& hdr, const Lo
     p.fallback_lib = (uint8_t)job.cfg.fallback_library();
     p.first_record_offset = at.rec_off;
     fp.apply(p);
+    if (job.clips) p.record_mode |= 4;
     bdx_bamdec* dec = nullptr;
     int rc = bdx_bamdec_create(&dec, job.sink, &p);
     if (rc != BDX_OK) throw std::runtime_error(std::string("bdx_bamdec_create: ") + bdx_strerror(rc));

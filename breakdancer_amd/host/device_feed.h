@@ -39,6 +39,7 @@ struct DecodeJob {
     // sized_for: the largest span the decoder -- new or armed again -- will be used for (its buffers are sized once)
     bdx_bamdec* rearm = nullptr;
     size_t sized_for = 0;
+    bool clips = false;                          // a decoder without a sink keeps the records' clip words (its gather target has bdx_use_clips on)
     bool may_be_unsupported = false;             // the caller can take `unsupported` for an answer (else it is an exception)
     std::vector<std::string>* targets = nullptr; // receives the file's sequence names
 };

@@ -61,6 +61,7 @@ Env read_env() {
     if (const char* d = getenv("BDX_DECODE")) e.decode_host = !strcmp(d, "host");
     if (const char* t = getenv("BDX_THREADS")) e.threads = std::max(1, atoi(t));
     if (const char* t = getenv("BDX_READ_THREADS")) e.read_threads = std::max(1, atoi(t));
+    if (const char* t = getenv("BDX_BATCH_RECORDS")) e.batch_records = (size_t)std::max(1, atoi(t));
     e.timing = getenv("BDX_TIMING") != nullptr;
     if (const char* t = getenv("BDX_TRIM")) e.keep_results = !strcmp(t, "0");
     if (const char* t = getenv("BDX_FORMAT_THREADS")) { e.format_threads_set = true; e.format_threads = atoi(t); }
@@ -128,6 +129,7 @@ Inputs::Inputs(int argc, char** argv, const Env& env)
     }
     ci_window = !opts.ci ? 0 : opts.ci_window >= 0 ? opts.ci_window : cutoff_window(cfg, "--ci");
     mapq_window = !opts.mapq ? 0 : opts.mapq_window >= 0 ? opts.mapq_window : cutoff_window(cfg, "--mapq");
+    clip_window = !opts.clip ? 0 : opts.clip_window >= 0 ? opts.clip_window : clip_default_window(cfg);
     // Decode threads: the work is CPU-bound on zlib (~375 MB/s of inflated bytes per core), so what counts is the number of
     // cores this process may really use -- the cgroup's CPU quota when there is one (a container with "16 CPUs" on a
     // 256-thread host: 16 threads 0.64 s, 32 0.55 s, 64 0.70 s for 15 M records), else the hardware threads.  Twice that
@@ -153,6 +155,7 @@ void Inputs::apply_estimate(const EstimatePlan& plan) {
     if (!opts.sites.empty() && opts.sites_window < 0) sites_window = cutoff_window(cfg, "--sites");
     if (opts.ci && opts.ci_window < 0) ci_window = cutoff_window(cfg, "--ci");
     if (opts.mapq && opts.mapq_window < 0) mapq_window = cutoff_window(cfg, "--mapq");
+    if (opts.clip && opts.clip_window < 0) clip_window = clip_default_window(cfg);
     if (estimate_config.is_open()) {
         estimate_config << plan.config_text;
         estimate_config.close();

@@ -52,6 +52,7 @@ struct Env {
     int format_threads = 0;      // BDX_FORMAT_THREADS
     bool foreground = false;     // BDX_FOREGROUND
     bool clean_exit = false;     // BDX_CLEAN_EXIT
+    size_t batch_records = 0;    // BDX_BATCH_RECORDS: records per batch of the host producer (0: its default, 2^20; tests force several batches)
 };
 Env read_env();
 
@@ -77,6 +78,7 @@ struct Inputs {
     int32_t sites_window = 0;
     int32_t ci_window = 0;       // --ci: without a finite cutoff the run ends here
     int32_t mapq_window = 0;     // --mapq: likewise
+    int32_t clip_window = 0;     // --clip: the largest finite cutoff, at most BDX_CLIP_WINDOW_MAX (that without a finite cutoff)
     unsigned io_threads = 0;     // decode threads of the host producer
     std::vector<bdx_lib> libs;
     std::vector<int> devices;    // BDX_GPUS
@@ -87,7 +89,7 @@ struct Inputs {
                                      // which brings means of its own) a configuration with no finite positive mean insert size fails here too
 
     // --estimate, the one change a run makes to its inputs (between "fed" and "run"): the estimated values replace the configuration's in
-    // cfg and libs, so that everything behind the feed prints and uses the run's libraries; the windows of --sites / --ci / --mapq that
+    // cfg and libs, so that everything behind the feed prints and uses the run's libraries; the windows of --sites / --ci / --mapq / --clip that
     // the command line did not give are computed again from them; --estimate-config is written and closed
     void apply_estimate(const EstimatePlan& plan);
 };

@@ -70,6 +70,10 @@ void print_usage(const bdx_opts& o) {
     fprintf(stderr, "       --ci-window INT    how far from a breakpoint a supporting read of --ci may start [the largest library uppercutoff]\n");
     fprintf(stderr, "       --mapq         add SQN / SQMIN / SQQ1 / SQMED / SQMAX and LQA / LQN / LQF to every --vcf / --sites-vcf record: the mapping quality of the reads that support either end, and the share of low-quality reads around it\n");
     fprintf(stderr, "       --mapq-window INT  how far from a breakpoint a read of --mapq may start [the largest library uppercutoff]\n");
+    fprintf(stderr, "       --clip         add CLN / CLPOS / CLSUP / CLSIDE to every --vcf / --sites-vcf record: where the soft-clipped reads around either end pile up, the breakpoint to the base\n");
+    fprintf(stderr, "       --clip-window INT  how far from a breakpoint a clipped read's clip may stand, 0 to %d [the largest library uppercutoff, at most %d]\n", BDX_CLIP_WINDOW_MAX, BDX_CLIP_WINDOW_MAX);
+    fprintf(stderr, "       --clip-min INT     the clipped bases a read needs to count, 1 to 255 [%d]\n", Options::kClipMinDefault);
+    fprintf(stderr, "       --clip-support INT the reads a pile needs to be reported, 1 to 2^30 [%d]\n", Options::kClipSupportDefault);
     fprintf(stderr, "       --depth        add RCI / RCF / RDR to every sample of a --vcf / --sites-vcf record: passing read starts inside the record, in its flanks, and their ratio\n");
     fprintf(stderr, "       --depth-flank INT  the width of either flank of --depth [%d]\n", Options::kDepthFlankDefault);
     fprintf(stderr, "       --mark-dup     flag duplicate read pairs (same library, positions and strands of both mates) on the GPU; they are ignored like reads with SAM flag 0x400\n");
@@ -95,7 +99,7 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
     // (the reference's letters parse exactly as with getopt; the long options are this tool's own)
-    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank, kMapq, kMapqWindow, kEstimate, kEstimateConfig, kMini, kMiniWindow, kMiniStep, kMiniMinPairs, kMiniScore };
+    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank, kMapq, kMapqWindow, kEstimate, kEstimateConfig, kMini, kMiniWindow, kMiniStep, kMiniMinPairs, kMiniScore, kClip, kClipWindow, kClipMin, kClipSupport };
     static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude},
                                          {"sites", required_argument, nullptr, kSites}, {"sites-vcf", required_argument, nullptr, kSitesVcf},
                                          {"sites-window", required_argument, nullptr, kSitesWindow}, {"mark-dup", no_argument, nullptr, kMarkDup},
@@ -106,6 +110,8 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
                                          {"mini", required_argument, nullptr, kMini}, {"mini-window", required_argument, nullptr, kMiniWindow},
                                          {"mini-step", required_argument, nullptr, kMiniStep}, {"mini-min-pairs", required_argument, nullptr, kMiniMinPairs},
                                          {"mini-score", required_argument, nullptr, kMiniScore},
+                                         {"clip", no_argument, nullptr, kClip}, {"clip-window", required_argument, nullptr, kClipWindow},
+                                         {"clip-min", required_argument, nullptr, kClipMin}, {"clip-support", required_argument, nullptr, kClipSupport},
                                          {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
@@ -143,6 +149,21 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
         }
         if (c == kEstimate) {
             estimate = true;
+            continue;
+        }
+        if (c == kClip) {
+            clip = true;
+            continue;
+        }
+        if (c == kClipWindow || c == kClipMin || c == kClipSupport) {
+            const long lo = c == kClipWindow ? 0 : 1, hi = c == kClipWindow ? BDX_CLIP_WINDOW_MAX : c == kClipMin ? 255 : (1L << 30);
+            char* end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < lo || v > hi) {
+                fprintf(stderr, "--clip-%s takes an integer from %ld to %ld, not '%s'.\n", c == kClipWindow ? "window" : c == kClipMin ? "min" : "support", lo, hi, optarg);
+                exit(1);
+            }
+            (c == kClipWindow ? clip_window : c == kClipMin ? clip_min : clip_support) = (int)v;
             continue;
         }
         if (c == kEstimateConfig) {
@@ -223,6 +244,10 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     }
     if ((mapq && vcf.empty() && sites_vcf.empty()) || (!mapq && mapq_window >= 0)) {
         fprintf(stderr, "--mapq needs --vcf FILE or --sites-vcf FILE to write to (and --mapq-window goes with --mapq).\n");
+        exit(1);
+    }
+    if ((clip && vcf.empty() && sites_vcf.empty()) || (!clip && (clip_window >= 0 || clip_min >= 0 || clip_support >= 0))) {
+        fprintf(stderr, "--clip needs --vcf FILE or --sites-vcf FILE to write to (and --clip-window, --clip-min and --clip-support go with --clip).\n");
         exit(1);
     }
     if (mini.empty() && (mini_window >= 0 || mini_step >= 0 || mini_min_pairs >= 0 || mini_score >= 0)) {

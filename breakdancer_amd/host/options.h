@@ -1,6 +1,6 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
 // (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf, --exclude, --sites / --sites-vcf /
-// --sites-window, --mark-dup, --ci / --ci-window, --depth / --depth-flank, --mapq / --mapq-window, --estimate / --estimate-config and --mini / --mini-window / --mini-step / --mini-min-pairs / --mini-score.
+// --sites-window, --mark-dup, --ci / --ci-window, --depth / --depth-flank, --mapq / --mapq-window, --clip / --clip-window / --clip-min / --clip-support, --estimate / --estimate-config and --mini / --mini-window / --mini-step / --mini-min-pairs / --mini-score.
 #pragma once
 #include <string>
 #include <vector>
@@ -37,6 +37,13 @@ struct Options {
     int mini_score = -1;         // --mini-score: the score a window must reach (-1: from the number of scoring windows)
     static constexpr int kMiniMinPairsDefault = 20;
     static constexpr int kDepthFlankDefault = 1000;
+    bool clip = false;           // --clip: CLN / CLPOS / CLSUP / CLSIDE of every --vcf / --sites-vcf record: the piles of clipped reads at either end (bdx_site_clip_peaks)
+    int clip_window = -1;        // --clip-window: how far from a breakpoint a clip may stand, 0 .. BDX_CLIP_WINDOW_MAX (-1: from the libraries' cutoffs, at most that)
+    int clip_min = -1;           // --clip-min: the clipped bases a read needs to count, 1 .. 255 (-1: kClipMinDefault)
+    int clip_support = -1;       // --clip-support: the reads a pile needs to be reported (-1: kClipSupportDefault)
+    static constexpr int kClipMinDefault = 10, kClipSupportDefault = 2;
+    int min_clip() const { return clip_min > 0 ? clip_min : kClipMinDefault; }
+    int clip_needed() const { return clip_support > 0 ? clip_support : kClipSupportDefault; }
     int flank() const { return depth_flank > 0 ? depth_flank : kDepthFlankDefault; }
     bdx_opts o;                  // numeric options in the C-ABI layout
     std::vector<std::string> orig_argv;

@@ -24,7 +24,9 @@ struct RoutingSink : BatchSink {
     const std::vector<int>& rank_of;
     std::vector<char> store;
     bdx_batch_buf cur{};
-    RoutingSink(const std::vector<bdx_dist*>& r, const std::vector<int>& ro) : ranks(r), rank_of(ro) {}
+    bool clips;                                   // --clip: the contexts keep clip words, put behind every batch
+    std::vector<std::pair<bdx_ctx*, size_t>> held;   // ... at the row their context has reached
+    RoutingSink(const std::vector<bdx_dist*>& r, const std::vector<int>& ro, bool with_clips) : ranks(r), rank_of(ro), clips(with_clips) {}
     bdx_batch_buf acquire(size_t capacity) override {
         const size_t K = (capacity + 63) / 64 * 64;
         store.resize(K * 43 + 64);
@@ -48,6 +50,7 @@ struct RoutingSink : BatchSink {
             bdx_ctx* c = bdx_dist_chromosome(ranks[rank_of[tid]], tid);
             if (!c) throw std::runtime_error("bdx_dist_chromosome failed");
             check(c, bdx_use_name_check(c, 1), "bdx_use_name_check");
+            if (clips) check(c, bdx_use_clips(c, 1), "bdx_use_clips");
             const size_t m = hi - lo;
             bdx_batch_buf b{};
             check(c, bdx_acquire_batch(c, m, &b), "bdx_acquire_batch");
@@ -58,6 +61,12 @@ struct RoutingSink : BatchSink {
             memcpy(b.name_key, cur.name_key + lo, m * 8);
             memcpy(b.name_check, cur.name_check + lo, m * 8);
             check(c, bdx_submit_batch(c, m), "bdx_submit_batch");
+            if (clips) {
+                auto at = std::find_if(held.begin(), held.end(), [c](const std::pair<bdx_ctx*, size_t>& h) { return h.first == c; });
+                if (at == held.end()) at = held.insert(held.end(), {c, 0});
+                check(c, bdx_put_clips(c, at->second, clip + lo, m), "bdx_put_clips");
+                at->second += m;
+            }
             lo = hi;
         }
     }
@@ -71,7 +80,9 @@ struct GpuSink : BatchSink {
     Session& s;
     size_t reserve;
     bool up = false;
-    GpuSink(Session& session, size_t res) : s(session), reserve(res) {}
+    bool clips;          // --clip: the context keeps clip words, put behind every batch ...
+    size_t held = 0;     // ... at the row the store has reached
+    GpuSink(Session& session, size_t res, bool with_clips) : s(session), reserve(res), clips(with_clips) {}
     void bring_up(bool with_store = true) {
         if (up) return;
         if (s.ctx_ready.valid()) check(nullptr, s.ctx_ready.get(), "bdx_create");
@@ -85,7 +96,11 @@ struct GpuSink : BatchSink {
         check(s.ctx, bdx_acquire_batch(s.ctx, capacity, &b), "bdx_acquire_batch");
         return b;
     }
-    void submit(size_t n) override { check(s.ctx, bdx_submit_batch(s.ctx, n), "bdx_submit_batch"); }
+    void submit(size_t n) override {
+        check(s.ctx, bdx_submit_batch(s.ctx, n), "bdx_submit_batch");
+        if (clips) check(s.ctx, bdx_put_clips(s.ctx, held, clip, n), "bdx_put_clips");
+        held += n;
+    }
 };
 
 // --estimate: from the summed histograms to the run's libraries in `in`; returns them for bdx_set_libs / bdx_dist_set_libs
@@ -120,9 +135,10 @@ Fed feed_and_run_single(Inputs& in, const Env& env, Session& s, Clock::time_poin
     // the GPU context (HIP runtime start-up, ~0.1 s) comes up on a helper thread while the BAMs are decoded
     // (the thread has copies of what it reads: it may outlive everything but the session)
     s.ctx_ready = std::async(std::launch::async, [ctx = &s.ctx, o = opts.o, libs = in.libs, nbams = (int)in.cfg.num_bams(), w0 = in.cfg.max_read_window_size(),
-                                                   device = opts.device, mark_dup = opts.mark_dup] {
+                                                   device = opts.device, mark_dup = opts.mark_dup, clips = opts.clip] {
         int rc = bdx_create(ctx, &o, libs.data(), (int)libs.size(), nbams, 0, w0, device);
         if (rc == BDX_OK) rc = bdx_use_name_check(*ctx, 1);   // mates are joined on two hashes of the read name
+        if (rc == BDX_OK && clips) rc = bdx_use_clips(*ctx, 1);
         if (rc == BDX_OK && mark_dup) rc = bdx_set_mark_duplicates(*ctx, 1);
         return rc;
     });
@@ -134,7 +150,7 @@ Fed feed_and_run_single(Inputs& in, const Env& env, Session& s, Clock::time_poin
         if (stat(f.c_str(), &st) == 0) reserve += (size_t)st.st_size / 48;
     }
     reserve = std::min<size_t>(reserve, 0xFFFFFFFFull - 1024);
-    GpuSink sink(s, reserve);
+    GpuSink sink(s, reserve, opts.clip);
     // One BAM: the file goes to the GPU as it is and is decoded there (bdx_bamdec_*: inflate, record boundaries, fields,
     // RG -> library, reader filter in HBM).  Several BAMs are merged in the reference's order by the host producer, which
     // also takes the files the device path does not (BDX_DECODE=host forces it).
@@ -144,12 +160,12 @@ Fed feed_and_run_single(Inputs& in, const Env& env, Session& s, Clock::time_poin
         if (env.timing) fprintf(stderr, "[bdx timing] GPU context + resident store ready %.3f s after start (waited %.3f s for it)\n", secs(t_start, now()), secs(tb, now()));
         bool unsupported = false;
         fed.n_reads = produce_on_device(in.cfg, opts.chr, in.exclude.get(), env.read_threads ? env.read_threads : (int)std::min(std::max(usable_cpus(), 2u), 16u),
-                                        &fed.targets, s.ctx, &unsupported);
+                                        &fed.targets, s.ctx, &unsupported, opts.clip);
         if (unsupported) check(s.ctx, bdx_reset_reads(s.ctx), "bdx_reset_reads");
         else { fed.device_decoded = true; sink.up = true; }
     }
     if (!fed.device_decoded) {
-        fed.n_reads = produce_stream(in.cfg, opts.chr, in.exclude.get(), (int)in.io_threads, &fed.targets, sink);
+        fed.n_reads = produce_stream(in.cfg, opts.chr, in.exclude.get(), (int)in.io_threads, &fed.targets, sink, env.batch_records ? env.batch_records : (size_t)1 << 20);
         sink.bring_up();  // (an input without records never asked for a batch)
     }
     fed.t_decoded = now();
@@ -198,15 +214,15 @@ Fed feed_and_run_sharded(Inputs& in, const Env& env, Session& s, Clock::time_poi
     if (!env.decode_host) {
         bool unsupported = true;
         fed.n_reads = produce_sharded_on_device(in.cfg, in.exclude.get(), (int)std::min(std::max(usable_cpus(), 2u), 32u), &fed.targets, s.ranks, in.devices,
-                                                fed.rank_of, &unsupported);
+                                                fed.rank_of, &unsupported, opts.clip);
         fed.device_decoded = !unsupported;
         if (unsupported)   // (no index: nothing was appended; a file the device path gave up on half way: what it appended goes again)
             for (bdx_dist* r : s.ranks)
                 if (bdx_dist_reset_reads(r) != BDX_OK) throw std::runtime_error(std::string("bdx_dist_reset_reads: ") + bdx_dist_last_error(r));
     }
     if (!fed.device_decoded) {
-        RoutingSink sink(s.ranks, fed.rank_of);
-        fed.n_reads = produce_stream(in.cfg, opts.chr, in.exclude.get(), (int)in.io_threads, &fed.targets, sink);
+        RoutingSink sink(s.ranks, fed.rank_of, opts.clip);
+        fed.n_reads = produce_stream(in.cfg, opts.chr, in.exclude.get(), (int)in.io_threads, &fed.targets, sink, env.batch_records ? env.batch_records : (size_t)1 << 20);
     }
     if (env.timing)
         fprintf(stderr, "[bdx timing] sharded run over %d ranks: %s\n", world,
@@ -342,6 +358,18 @@ Genotypes count_on_store(const Inputs& in, const Env& env, const Session& s, con
         if (env.timing)
             fprintf(stderr, "[bdx timing] --mapq: mapping quality at %zu ends of %zu records (window %d) %.4f s\n", ends,
                     gt.vcf_rows.size() + gt.site_rows.size(), in.mapq_window, secs(tv, now()));
+    }
+    if (opts.clip) {
+        const auto tv = now();
+        uint64_t observations = 0;
+        size_t ends = 0;
+        for (auto* rows : {&gt.vcf_rows, &gt.site_rows}) {
+            observations += fill_clips(opts, rc, in.clip_window, opts.min_clip(), *rows);
+            for (auto const& r : *rows) ends += r.has_clip ? (size_t)r.cl[0].held + (size_t)r.cl[1].held : 0;
+        }
+        if (env.timing)
+            fprintf(stderr, "[bdx timing] --clip: piles of clipped reads at %zu ends of %zu records, %llu clipped observations (window %d, min %d) %.4f s\n", ends,
+                    gt.vcf_rows.size() + gt.site_rows.size(), (unsigned long long)observations, in.clip_window, opts.min_clip(), secs(tv, now()));
     }
     if (opts.depth) {
         const auto tv = now();
@@ -495,10 +523,12 @@ void write_vcfs(const Inputs& in, Genotypes& gt) {
     const VcfDepth* depth = opts.depth ? &depth_info : nullptr;
     const VcfMapq mapq_header{in.mapq_window};
     const VcfMapq* mapq = opts.mapq ? &mapq_header : nullptr;
-    if (in.vcf) in.vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.vcf_rows), opts.exclude, nullptr, opts.mark_dup, ci, depth, mapq, opts.estimate);
+    const VcfClip clip_header{in.clip_window, opts.min_clip(), opts.clip_needed()};
+    const VcfClip* clip = opts.clip ? &clip_header : nullptr;
+    if (in.vcf) in.vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.vcf_rows), opts.exclude, nullptr, opts.mark_dup, ci, depth, mapq, opts.estimate, clip);
     if (in.sites_vcf) {
         const VcfSites info{opts.sites, in.sites_window};
-        in.sites_vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.site_rows), opts.exclude, &info, opts.mark_dup, ci, depth, mapq, opts.estimate);
+        in.sites_vcf->write(opts.orig_argv, in.header.names(), in.header.lengths(), samples, std::move(gt.site_rows), opts.exclude, &info, opts.mark_dup, ci, depth, mapq, opts.estimate, clip);
     }
 }
 

@@ -152,6 +152,7 @@ public:
             memset(buf_.bam + used_, bam, m);
             memcpy(buf_.name_key + used_, c.name_key.data() + lo, m * 8);
             memcpy(buf_.name_check + used_, c.name_check.data() + lo, m * 8);
+            memcpy(clip_.data() + used_, c.clip.data() + lo, m * 4);
             used_ += m; lo += m; total_ += m;
             if (used_ == buf_.capacity) close();
         }
@@ -163,6 +164,7 @@ public:
         buf_.flag[u] = c.flag[i]; buf_.qlen[u] = c.qlen[i]; buf_.mapq[u] = c.mapq[i]; buf_.lib[u] = c.lib[i]; buf_.bam[u] = bam;
         buf_.name_key[u] = c.name_key[i];
         buf_.name_check[u] = c.name_check[i];
+        clip_[u] = c.clip[i];
         ++used_; ++total_;
         if (used_ == buf_.capacity) close();
     }
@@ -173,11 +175,14 @@ private:
     void open() {
         const auto t0 = std::chrono::steady_clock::now();
         buf_ = sink_.acquire(batch_); used_ = 0; open_ = true;
+        if (clip_.size() < buf_.capacity) clip_.resize(buf_.capacity);
         acquire_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
     void close() {
         const auto t0 = std::chrono::steady_clock::now();
+        sink_.clip = clip_.data();
         sink_.submit(used_); open_ = false;
+        sink_.clip = nullptr;
         submit_s_ += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
 public:
@@ -186,6 +191,7 @@ private:
     BatchSink& sink_;
     size_t batch_;
     bdx_batch_buf buf_{};
+    std::vector<uint32_t> clip_;   // the clip words of the batch being filled (BatchSink::clip)
     size_t used_ = 0, total_ = 0;
     bool open_ = false;
 };
@@ -528,6 +534,7 @@ struct ShardedRun {   // what the ranks' threads share, read only
     const std::vector<int>& rank_of;
     int per;   // threads of a rank
     bool timing;
+    bool clips;   // --clip: the ranks' contexts and the decoders keep clip words
 };
 
 struct RankOutcome {
@@ -561,6 +568,7 @@ void decode_rank(const ShardedRun& run, int r, RankOutcome& out) {
         bdx_ctx* c = bdx_dist_chromosome(run.ranks[r], (int)t);
         if (!c) throw std::runtime_error(std::string("bdx_dist_chromosome: ") + bdx_dist_last_error(run.ranks[r]));
         if (bdx_use_name_check(c, 1) != BDX_OK) throw std::runtime_error("bdx_use_name_check");
+        if (run.clips && bdx_use_clips(c, 1) != BDX_OK) throw std::runtime_error(std::string("bdx_use_clips: ") + bdx_last_error(c));
         if (!reserved) {   // the rank's store for ALL of its chromosomes (a record takes 50-150 bytes of BAM): no growing between them
             // (plus what the decoder must assume of a batch in flight before its records are counted: 36 bytes is the smallest record)
             if (bdx_reserve(c, std::min<size_t>(bytes_mine / 48 + largest_any * 8 / 36 + ((size_t)1 << 20), 0xFFFFFFFFull - 1024)) != BDX_OK) throw std::runtime_error("bdx_reserve");
@@ -571,7 +579,7 @@ void decode_rank(const ShardedRun& run, int r, RankOutcome& out) {
             DecodeJob job{run.cfg, b};
             job.whole_tid = (int)t; job.span_bytes = run.span[b][t].end - run.span[b][t].begin;
             job.exclude = run.ex; job.threads = run.per; job.device = run.devices[r]; job.sink = sink;
-            job.rearm = decs[b].get(); job.sized_for = largest[b]; job.may_be_unsupported = true;
+            job.rearm = decs[b].get(); job.sized_for = largest[b]; job.may_be_unsupported = true; job.clips = run.clips;
             DecodeResult res = decode_on_device(job);
             if (res.decoder) decs[b] = std::move(res.decoder);
             out.excluded += res.excluded;
@@ -615,7 +623,7 @@ void decode_rank(const ShardedRun& run, int r, RankOutcome& out) {
 // one gather in HBM behind what the rank's store holds (bdx_append_decoded).  Nothing is decoded twice and no record crosses the host.
 // unsupported: a file without an index (or one that does not cover the header's sequences), nothing was done.
 size_t produce_sharded_on_device(const BamConfig& cfg, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, const std::vector<bdx_dist*>& ranks,
-                                 const std::vector<int>& devices, const std::vector<int>& rank_of, bool* unsupported) {
+                                 const std::vector<int>& devices, const std::vector<int>& rank_of, bool* unsupported, bool clips) {
     *unsupported = true;
     const size_t nb = cfg.num_bams();
     if (nb < 1 || nb > 16) return 0;
@@ -637,7 +645,7 @@ size_t produce_sharded_on_device(const BamConfig& cfg, const ExcludeTable* ex, i
     }
     if (targets) *targets = names;
     const int world = (int)ranks.size();
-    const ShardedRun run{cfg, ex, names, span, ranks, devices, rank_of, std::max(2, threads / std::max(1, world)), getenv("BDX_TIMING") != nullptr};
+    const ShardedRun run{cfg, ex, names, span, ranks, devices, rank_of, std::max(2, threads / std::max(1, world)), getenv("BDX_TIMING") != nullptr, clips};
     std::vector<RankOutcome> outcome(world);
     std::vector<std::thread> th;
     for (int r = 0; r < world; ++r)
@@ -663,7 +671,7 @@ size_t produce_sharded_on_device(const BamConfig& cfg, const ExcludeTable* ex, i
 }
 
 size_t produce_on_device(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, bdx_ctx* ctx,
-                         bool* unsupported) {
+                         bool* unsupported, bool clips) {
     if (unsupported) *unsupported = false;
     const size_t nb = cfg.num_bams();
     if (nb == 0) throw std::runtime_error("BamMerger created with no input streams!");
@@ -673,7 +681,7 @@ size_t produce_on_device(const BamConfig& cfg, const std::string& chr, const Exc
     auto decode = [&](size_t b, bdx_ctx* sink, bdx_bamdec** dec, size_t* n) {
         DecodeJob job{cfg, b};
         job.region = chr; job.exclude = ex; job.threads = threads; job.sink = sink; job.device = sink ? 0 : bdx_device(ctx);
-        job.may_be_unsupported = unsupported != nullptr || !sink; job.targets = b == 0 ? targets : nullptr;
+        job.may_be_unsupported = unsupported != nullptr || !sink; job.targets = b == 0 ? targets : nullptr; job.clips = clips;
         DecodeResult res = decode_on_device(job);
         decs[b] = std::move(res.decoder);
         excluded += res.excluded;

@@ -41,10 +41,13 @@ uint64_t collect_reads(const BamConfig& cfg, const std::string& chr, const Exclu
 // Where the producer puts the merged stream: batches of SoA columns.  acquire() returns columns with room for at least
 // `capacity` records, submit(n) hands the first n back.  Two sinks exist: the GPU context's pinned staging ring
 // (bdx_acquire_batch / bdx_submit_batch: copies and the classifier overlap the decoding of the next batch) and ReadStream.
+// The batch structs have no room for the records' clip words (include/bdx.h bdx_clip_word): the writer of a batch leaves them in `clip`,
+// one per record of the batch, valid during submit(); a sink that keeps them puts them behind the batch (bdx_put_clips).
 struct BatchSink {
     virtual ~BatchSink() {}
     virtual bdx_batch_buf acquire(size_t capacity) = 0;
     virtual void submit(size_t n) = 0;
+    const uint32_t* clip = nullptr;
 };
 
 // chr: empty = all sequences, otherwise the -o region in samtools syntax ("name", "name:beg" or "name:beg-end").
@@ -59,13 +62,14 @@ size_t produce_stream(const BamConfig& cfg, const std::string& chr, const Exclud
 // fields, RG -> library and the reader filter run in HBM, and the records land in ctx's resident store with the classifier
 // behind them.  Returns the number of records appended.  Throws std::runtime_error; `unsupported` (may be null) is set instead
 // when the file is one the device path leaves to the host reader (a record of more than 4 MiB), with nothing appended.
+// clips: the context keeps clip words (bdx_use_clips is on): decoders that are gathered into it keep them too
 size_t produce_on_device(const BamConfig& cfg, const std::string& chr, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, bdx_ctx* ctx,
-                         bool* unsupported);
+                         bool* unsupported, bool clips = false);
 // One whole-genome run over several GPUs from ONE indexed BAM: rank r's thread decodes the chromosomes t with rank_of[t] == r on
 // devices[r], into bdx_dist_chromosome(ranks[r], t).  *unsupported: no index / several files -- nothing was appended, or a file the
 // device path gives up on (the caller then recreates the ranks and takes the host producer).
 size_t produce_sharded_on_device(const BamConfig& cfg, const ExcludeTable* ex, int threads, std::vector<std::string>* targets, const std::vector<bdx_dist*>& ranks,
-                                 const std::vector<int>& devices, const std::vector<int>& rank_of, bool* unsupported);
+                                 const std::vector<int>& devices, const std::vector<int>& rank_of, bool* unsupported, bool clips = false);
 // the decoders produce_on_device used are kept (releasing them costs more than the run that follows): this releases them
 void release_device_decoders();
 // reference sequences of the first BAM of the configuration (names and lengths from its header; io/BamMerger.cpp:78)

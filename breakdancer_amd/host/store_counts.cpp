@@ -240,6 +240,52 @@ void fill_quality(const Options& opts, const RunContexts& rc, int32_t window, st
     }
 }
 
+// As fill_quality, query for query: KP (bdx_site_clip_peaks) instead of KM, on the rank that holds the asked end's chromosome.
+uint64_t fill_clips(const Options& opts, const RunContexts& rc, int32_t window, int32_t min_clip, std::vector<VcfRecord>& out) {
+    constexpr size_t kWords = sizeof(bdx_clip_peaks) / 4;   // (count_on_ranks moves rows of 32-bit words: an end's piles are six)
+    static_assert(sizeof(bdx_clip_peaks) == 24 && alignof(bdx_clip_peaks) == 4, "bdx_clip_peaks is six 32-bit words");
+    std::vector<bdx_site> q;
+    std::vector<uint8_t> q_end;
+    std::vector<int32_t> q_tid;
+    std::vector<size_t> q_row;
+    for (size_t k = 0; k < out.size(); ++k) {
+        VcfRecord& r = out[k];
+        const uint32_t mask = opts.sv_flag_mask(r.type);
+        if ((!rc.held(r.chr1) && !rc.held(r.chr2)) || r.pos1 < 1 || r.pos2 < 1 || mask == 0) continue;
+        const bool swapped = r.chr1 > r.chr2 || (r.chr1 == r.chr2 && r.pos1 > r.pos2);
+        const bdx_site s = swapped ? bdx_site{r.chr2, r.pos2, r.chr1, r.pos1, mask} : bdx_site{r.chr1, r.pos1, r.chr2, r.pos2, mask};
+        r.has_clip = true;
+        r.cl_swapped = swapped;
+        for (int e = 0; e < 2; ++e) {
+            const int32_t t = e ? s.tid2 : s.tid1;
+            r.cl[e] = EndClips{};
+            r.cl[e].pos = e ? s.pos2 : s.pos1;
+            if (!rc.held(t)) continue;
+            r.cl[e].held = true;
+            q.push_back(s); q_end.push_back((uint8_t)(e + 1)); q_tid.push_back(t); q_row.push_back(k);
+        }
+    }
+    std::vector<uint32_t> words;
+    count_on_ranks(rc, q_tid, kWords, "bdx_site_clip_peaks", words, [&](bdx_ctx* c, const std::vector<size_t>& m, uint32_t* w) {
+        std::vector<bdx_site> mine(m.size());
+        std::vector<uint8_t> ends(m.size());
+        for (size_t j = 0; j < m.size(); ++j) { mine[j] = q[m[j]]; ends[j] = q_end[m[j]]; }
+        std::vector<bdx_clip_peaks> b(m.size());
+        const int st = bdx_site_clip_peaks(c, mine.data(), ends.data(), m.size(), window, min_clip, b.data());
+        if (st == BDX_OK) memcpy(w, b.data(), b.size() * sizeof(bdx_clip_peaks));
+        return st;
+    });
+    uint64_t observations = 0;
+    for (size_t i = 0; i < q.size(); ++i) {
+        bdx_clip_peaks b;
+        memcpy(&b, words.data() + i * kWords, sizeof b);
+        EndClips& e = out[q_row[i]].cl[q_end[i] - 1];
+        e.n_left = b.n_left; e.n_right = b.n_right; e.pos_left = b.pos_left; e.pos_right = b.pos_right; e.peak_left = b.peak_left; e.peak_right = b.peak_right;
+        observations += (uint64_t)b.n_left + b.n_right;
+    }
+    return observations;
+}
+
 // Every record with both ends on one sequence the run read and pos1 != pos2 gives three intervals of read starts -- its inside and its two
 // flanks (vcf.h depth_spans), clamped to the sequence -- and all of them go to the GPU in one call (KR, bdx_count_interval_reads; a sharded
 // run's on the rank that holds the sequence).  RCI is the inside's count per sample, RCF the two flanks' together.
@@ -278,6 +324,15 @@ int32_t cutoff_window(const BamConfig& cfg, const char* option) {
     }
     if (ub < 0) throw std::runtime_error(std::string(option) + ": no library has a finite uppercutoff, give " + option + "-window");
     return (int32_t)std::min(ub, 1073741824.0);
+}
+
+int32_t clip_default_window(const BamConfig& cfg) {
+    double ub = -1.0;
+    for (size_t i = 0; i < cfg.num_libs(); ++i) {
+        const double u = cfg.library_config(i).uppercutoff;
+        if (std::isfinite(u)) ub = std::max(ub, std::ceil(u));
+    }
+    return ub < 0 ? BDX_CLIP_WINDOW_MAX : (int32_t)std::min(ub, (double)BDX_CLIP_WINDOW_MAX);
 }
 
 // --mini: the store's insert-size histogram after the run (--mark-dup's marks are in the flag column), summed over the ranks

@@ -39,6 +39,10 @@ void fill_ci(const Options& opts, const RunContexts& rc, int32_t window, std::ve
 // --mapq: SQ* / LQ* of --vcf and --sites-vcf records from the mapping qualities of the reads that support either end and of those around it.
 void fill_quality(const Options& opts, const RunContexts& rc, int32_t window, std::vector<VcfRecord>& out);
 
+// --clip: CL* of --vcf and --sites-vcf records from the piles of clipped reads at either end (KP, bdx_site_clip_peaks); which records take
+// part, and where an end is asked, as in fill_quality.  Returns the observations of all ends together.
+uint64_t fill_clips(const Options& opts, const RunContexts& rc, int32_t window, int32_t min_clip, std::vector<VcfRecord>& out);
+
 // --depth: RCI / RCF of --vcf and --sites-vcf records from the passing read starts inside and beside them; lengths: the sequences' (the
 // flanks are clamped to them), ns: the samples.
 void fill_depth(const Options& opts, const RunContexts& rc, int32_t flank, const std::vector<uint32_t>& lengths, size_t ns, std::vector<VcfRecord>& out);
@@ -53,5 +57,7 @@ void window_insert_shift(const RunContexts& rc, const std::vector<bdx_interval>&
 // How far a supporting mate can start from a breakpoint it brackets: the ceiling of the largest finite library uppercutoff, the window
 // of --sites, --ci and --mapq when theirs is not given.
 int32_t cutoff_window(const BamConfig& cfg, const char* option);
+// --clip's: the same ceiling, at most BDX_CLIP_WINDOW_MAX; that when no cutoff is finite
+int32_t clip_default_window(const BamConfig& cfg);
 
 }  // namespace bdhost

@@ -69,6 +69,36 @@ std::string mapq_info(const EndQuality& e1, const EndQuality& e2, bool swapped) 
            });
 }
 
+ClipWinner clip_winner(const EndClips& e) {
+    ClipWinner w;
+    if (!e.peak_left && !e.peak_right) return w;
+    const int64_t dl = e.pos_left > e.pos ? e.pos_left - e.pos : e.pos - e.pos_left, dr = e.pos_right > e.pos ? e.pos_right - e.pos : e.pos - e.pos_right;
+    const bool right = e.peak_right > e.peak_left || (e.peak_right == e.peak_left && dr < dl);
+    w.side = right ? 'R' : 'L';
+    w.pos = right ? e.pos_right : e.pos_left;
+    w.peak = right ? e.peak_right : e.peak_left;
+    return w;
+}
+
+std::string clip_info(const EndClips& e1, const EndClips& e2, bool swapped, uint32_t support) {
+    const EndClips* e[2] = {swapped ? &e2 : &e1, swapped ? &e1 : &e2};
+    auto key = [&](const char* name, auto entry) {
+        std::string s = std::string(";") + name + "=";
+        for (int k = 0; k < 2; ++k) s += (k ? "," : "") + (e[k]->held ? entry(*e[k]) : std::string("."));
+        return s;
+    };
+    auto of_winner = [support](auto field) {
+        return [support, field](const EndClips& x) {
+            const ClipWinner w = clip_winner(x);
+            return w.side && w.peak >= support ? field(w) : std::string(".");
+        };
+    };
+    return key("CLN", [](const EndClips& x) { return std::to_string((uint64_t)x.n_left + x.n_right); }) +
+           key("CLPOS", of_winner([](const ClipWinner& w) { return std::to_string(w.pos); })) +
+           key("CLSUP", of_winner([](const ClipWinner& w) { return std::to_string(w.peak); })) +
+           key("CLSIDE", of_winner([](const ClipWinner& w) { return std::string(1, w.side); }));
+}
+
 VcfWriter::VcfWriter(const std::string& path) : path_(path) {
     f_ = fopen(path.c_str(), "w");
     if (!f_) throw std::runtime_error("unable to open VCF output file '" + path + "'");
@@ -80,7 +110,7 @@ VcfWriter::~VcfWriter() {
 
 void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                       const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude,
-                      const VcfSites* sites, bool mark_dup, const VcfCi* ci, const VcfDepth* depth, const VcfMapq* mapq, bool estimate) {
+                      const VcfSites* sites, bool mark_dup, const VcfCi* ci, const VcfDepth* depth, const VcfMapq* mapq, bool estimate, const VcfClip* clip) {
     if (!f_) throw std::runtime_error("VCF output file '" + path_ + "' is already closed");
     FILE* f = f_;
     fprintf(f, "##fileformat=VCFv4.2\n##source=breakdancer-max-mi355x\n##command=");
@@ -93,6 +123,7 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
     if (ci) fprintf(f, "##ci_window=%d\n", ci->window);
     if (depth) fprintf(f, "##depth_flank=%d\n", depth->flank);
     if (mapq) fprintf(f, "##mapq_window=%d\n", mapq->window);
+    if (clip) fprintf(f, "##clip_window=%d\n##clip_min=%d\n##clip_support=%d\n", clip->window, clip->min_clip, clip->support);
     for (size_t t = 0; t < contigs.size(); ++t)
         fprintf(f, "##contig=<ID=%s,length=%u>\n", contigs[t].c_str(), t < lengths.size() ? lengths[t] : 0u);
     fputs("##FILTER=<ID=PASS,Description=\"All filters passed\">\n"
@@ -129,6 +160,12 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
               "##INFO=<ID=LQA,Number=2,Type=Integer,Description=\"Mapped reads that start within mapq_window of the breakpoint, whatever their class\">\n"
               "##INFO=<ID=LQN,Number=2,Type=Integer,Description=\"Those among LQA whose mapping quality does not exceed their library's minimum (-q, or the configuration's mapqual)\">\n"
               "##INFO=<ID=LQF,Number=2,Type=Float,Description=\"LQN / LQA\">\n",
+              f);
+    if (clip)
+        fputs("##INFO=<ID=CLN,Number=2,Type=Integer,Description=\"Clipped reads at the first and the second printed breakpoint: passing reads soft- or hard-clipped by clip_min bases or more whose clip stands within clip_window of it, left and right clips together (all samples pooled)\">\n"
+              "##INFO=<ID=CLPOS,Number=2,Type=Integer,Description=\"Where most of them are clipped, 1-based: with CLSIDE L the first aligned base of reads clipped on their left (the junction lies between CLPOS - 1 and CLPOS), with R the last aligned base of reads clipped on their right (between CLPOS and CLPOS + 1); '.' below clip_support reads\">\n"
+              "##INFO=<ID=CLSUP,Number=2,Type=Integer,Description=\"Reads clipped at CLPOS on that side\">\n"
+              "##INFO=<ID=CLSIDE,Number=2,Type=String,Description=\"L or R: the side of the reads that is clipped at CLPOS (the larger pile; ties: the nearer to the breakpoint, then L)\">\n",
               f);
     fputs("##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
           "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: second-smallest PL, capped at 99\">\n"
@@ -167,6 +204,7 @@ void VcfWriter::write(const std::vector<std::string>& argv, const std::vector<st
                     (long long)c2.a, (long long)c2.b, r.ci_n);
         }
         if (mapq && r.has_mapq) fputs(mapq_info(r.mq[0], r.mq[1], r.mq_swapped).c_str(), f);
+        if (clip && r.has_clip) fputs(clip_info(r.cl[0], r.cl[1], r.cl_swapped, (uint32_t)clip->support).c_str(), f);
         fputs(depth ? "\tGT:GQ:PL:DR:DV:RCI:RCF:RDR" : "\tGT:GQ:PL:DR:DV", f);
         for (size_t k = 0; k < samples.size(); ++k) {
             const int64_t dr = k < r.dr.size() ? r.dr[k] : -1, dv = k < r.dv.size() ? r.dv[k] : 0;

@@ -64,6 +64,23 @@ struct EndQuality {
 // LQF is n_low / n_all with three decimals (printf's rounding of the double quotient).
 std::string mapq_info(const EndQuality& e1, const EndQuality& e2, bool swapped);
 
+// --clip: what bdx_site_clip_peaks says about one end of a record; held as in EndQuality; pos: the end's own position P
+struct EndClips {
+    bool held = false;
+    int64_t pos = 0;
+    uint32_t n_left = 0, n_right = 0;
+    int32_t pos_left = 0, pos_right = 0;
+    uint32_t peak_left = 0, peak_right = 0;
+};
+// The winning pile of an end: the side with the larger peak, then the one nearer to P, then the left one.  side 'L' / 'R'; 0: the end has no
+// observation at all.
+struct ClipWinner { char side = 0; int32_t pos = 0; uint32_t peak = 0; };
+ClipWinner clip_winner(const EndClips& e);
+// The INFO fragment of --clip, ";CLN=a,b;CLPOS=a,b;CLSUP=a,b;CLSIDE=a,b": e1 / e2 and swapped as in mapq_info.  CLN is n_left + n_right;
+// CLPOS / CLSUP / CLSIDE are the winning pile's X, its reads and L or R, all three '.' when the winner's peak is below `support` (none is
+// below any support); every entry is '.' for an end that is not held.
+std::string clip_info(const EndClips& e1, const EndClips& e2, bool swapped, uint32_t support);
+
 // one printed row of the table
 struct VcfRecord {
     size_t row = 0;                  // 1-based row number among the printed rows (ID = BDX<row>)
@@ -82,6 +99,9 @@ struct VcfRecord {
     bool has_mapq = false;           // --mapq: the record took part (both positions >= 1, a read class maps to its type, an end the run read) ...
     EndQuality mq[2];                // ... the two ends of the site it was counted as, in the site's order ...
     bool mq_swapped = false;         // ... which is the reverse of the record's own
+    bool has_clip = false;           // --clip: the record took part (--mapq's conditions) ...
+    EndClips cl[2];                  // ... the two ends of the site it was asked as, in the site's order ...
+    bool cl_swapped = false;         // ... which is the reverse of the record's own
 };
 
 // what makes an output a --sites-vcf one: the records are given sites (ID SITE<row>, QUAL '.', INFO without ORI1 / ORI2 / NREADS / BDAF)
@@ -105,6 +125,11 @@ struct VcfMapq {
     int32_t window = 0;              // the window the reads were looked for with
 };
 
+// what makes an output a --clip one: the ##clip_window= / ##clip_min= / ##clip_support= lines and the four CL* header lines
+struct VcfClip {
+    int32_t window = 0, min_clip = 0, support = 0;
+};
+
 class VcfWriter {
 public:
     // opens (truncates) the file at once: an unwritable path fails before any work is done
@@ -116,11 +141,11 @@ public:
     // records' CHROM / CHR2 values); exclude: the --exclude file of the run ("": none) for the ##exclude= line; sites: non-null for a
     // --sites-vcf output; mark_dup: the run marked duplicates (--mark-dup), for the ##mark_dup=1 line; ci: non-null for a run
     // with --ci, depth: for a run with --depth, mapq: for a run with --mapq; estimate: the run took its
-    // libraries from its own pairs (--estimate), for the ##estimate=1 line; the file is closed afterwards
+    // libraries from its own pairs (--estimate), for the ##estimate=1 line; clip: non-null for a run with --clip; the file is closed afterwards
     void write(const std::vector<std::string>& argv, const std::vector<std::string>& contigs, const std::vector<uint32_t>& lengths,
                const std::vector<std::string>& samples, std::vector<VcfRecord> records, const std::string& exclude = "",
                const VcfSites* sites = nullptr, bool mark_dup = false, const VcfCi* ci = nullptr,
-               const VcfDepth* depth = nullptr, const VcfMapq* mapq = nullptr, bool estimate = false);
+               const VcfDepth* depth = nullptr, const VcfMapq* mapq = nullptr, bool estimate = false, const VcfClip* clip = nullptr);
 
 private:
     std::string path_;

@@ -141,6 +141,36 @@ typedef struct bdx_batch_buf {
  * anomalous reads' values are ever looked at: the mate join compares them on every key match, across GPUs as well (bdx_dist), and
  * the read-level replay tells names apart by the pair.  To be called while the context holds no reads; default off. */
 int bdx_use_name_check(bdx_ctx* ctx, int on);
+
+/* The clip word of a record: no counterpart in the reference, which never looks at a CIGAR beyond bam_calend.  What a record's CIGAR
+ * says about clips at its ends and about the reference it covers, the evidence bdx_site_clip_peaks piles up.  The rule, written down
+ * here once (one function for every reader: csrc/bdx_clip.h):
+ *   INPUT   the CIGAR as n_cigar little-endian words (len << 4 | op; M0 I1 D2 N3 S4 H5 P6 =7 X8), l_seq and the SAM flag.
+ *   WORD    left | right << 8 | span << 16.
+ *   left    the summed length of the leading run of S / H operations, capped at 255.
+ *   right   the summed length of the trailing run of S / H operations, capped at 255 -- counted only if at least one other operation
+ *           stands in front of that run: a CIGAR of clips alone has left only, right = 0.
+ *   span    the reference bases consumed (M D N = X, as bam_calend), capped at 65535.  When the cap takes effect (more than 65535)
+ *           right is 0, because its position is unknown.
+ *   ZERO    the word is 0 when n_cigar == 0, when the record is unmapped (flag 0x4), and for htslib's long-CIGAR placeholder (two
+ *           operations: S of length l_seq, then N; the real CIGAR is in the CG tag, which is not read).
+ * bdx_clip_word is a host function and touches no GPU; cigar may be NULL with n_cigar == 0. */
+uint32_t bdx_clip_word(const uint32_t* cigar, uint32_t n_cigar, int32_t l_seq, uint32_t flag);
+#define BDX_CLIP_LEFT(w) ((w) & 255u)
+#define BDX_CLIP_RIGHT(w) (((w) >> 8) & 255u)
+#define BDX_CLIP_SPAN(w) ((w) >> 16)
+/* An optional column of the store beside bdx_batch's: one clip word per record, 4 bytes.  bdx_use_clips switches it on or off while the
+ * context holds no reads (BDX_ESTATE otherwise); default off, and then nothing is allocated and nothing below may be called
+ * (BDX_ESTATE).  With it on the store grows a zero-filled column that growth carries over and bdx_reset_reads empties; a store adopted
+ * with bdx_set_device_reads cannot carry one (BDX_ESTATE).  bdx_put_clips copies n host words into rows [first, first + n) of records
+ * the context already holds (bdx_push, bdx_acquire_batch / bdx_submit_batch: the batch structs are unchanged, the words come behind
+ * them); rows never put stay 0; first + n beyond the records held is BDX_EINVAL.  The words are copied into a pinned buffer of the context's
+ * (a ring of four) and go to the device behind the batches' own copies: `clip` may be reused when the call returns, the call does not wait
+ * for the copy (only for the one four calls back), and the copy is ordered before any later run or query on the context.
+ * bdx_reset_reads zeroes the whole column.  bdx_get_clips reads the first min(cap, records held) words back. */
+int bdx_use_clips(bdx_ctx* ctx, int on);
+int bdx_put_clips(bdx_ctx* ctx, size_t first, const uint32_t* clip, size_t n);
+int bdx_get_clips(bdx_ctx* ctx, uint32_t* out, size_t cap);
 int bdx_reserve(bdx_ctx* ctx, size_t n_reads);
 int bdx_push(bdx_ctx* ctx, const bdx_batch* host_batch);
 int bdx_acquire_batch(bdx_ctx* ctx, size_t capacity, bdx_batch_buf* out);
@@ -423,12 +453,17 @@ typedef struct bdx_bamdec_params {
     int32_t batch_rounds;         /* rounds of the GPU's wave slots an inflate launch takes (7,680 members each), 1..16; 0: from expected_bytes
                                      (one round per 2.5 GB, at most four).  Ignored when batch_blocks is given */
     int32_t record_mode;          /* bits: 1 = no reader filter (secondary / supplementary / unplaced records are kept too), 2 = the quality column is
-                                     MAPQ whether or not a record carries an AM tag.  0 for breakdancer-max's reader; bam2cfg sets them */
+                                     MAPQ whether or not a record carries an AM tag.  0 for breakdancer-max's reader; bam2cfg sets them.
+                                     4 = a decoder WITHOUT a sink keeps the records' clip words (bdx_clip_word) beside its columns, for a
+                                     gather target with bdx_use_clips on (bdx_merge_decoded / bdx_append_decoded refuse a decoder without
+                                     them then: BDX_EINVAL); with a sink the sink's own switch decides and the bit is ignored */
     int32_t missing_lib_plus1;    /* library of records WITHOUT a read-group tag, plus one; 0: fallback_lib, like an unknown read group */
     int32_t time_kernels;         /* != 0: a HIP event pair around every inflate launch; bdx_bamdec_host_ms [12] = their sum in ms, [13] = launches
                                      (a measurement: each pair idles the GPU for a few microseconds) */
 } bdx_bamdec_params;
 int bdx_bamdec_create(bdx_bamdec** out, bdx_ctx* sink, const bdx_bamdec_params* p);
+/* the clip words of records [first, first + n) of a finished decoder that keeps its own columns and clip words (for tests) */
+int bdx_bamdec_fetch_clips(bdx_bamdec* d, uint64_t first, uint64_t n, uint32_t* out);
 void bdx_bamdec_destroy(bdx_bamdec* d);
 const char* bdx_bamdec_last_error(const bdx_bamdec* d);
 int bdx_bamdec_acquire(bdx_bamdec* d, size_t bytes, size_t max_blocks, void** buf, bdx_bgzf_block** blocks);
@@ -574,6 +609,30 @@ int bdx_site_breakpoint_bounds(bdx_ctx* ctx, const bdx_site* sites, size_t n, in
  * all zeros.  Not beside another call on the same context (bdx_trim_results included). */
 typedef struct bdx_site_quality { uint32_t n, n_all, n_low; uint8_t qmin, q1, median, qmax; } bdx_site_quality;   /* 16 bytes */
 int bdx_site_end_quality(bdx_ctx* ctx, const bdx_site* sites, const uint8_t* end, size_t n, int32_t window, bdx_site_quality* out);
+
+/* Where the clipped reads pile up around ONE END of given SV sites: no counterpart in the reference, whose calls are all imprecise.  A read
+ * that crosses a junction is aligned up to it and clipped behind it, so the clips of one breakpoint stand on one base.  The rule, written
+ * down here once (KP, csrc/kp_clip.hip):
+ *   A QUERY       is (site, end) as bdx_site_end_quality takes it; (T, P) is the asked end.  The site's flag_mask is checked like there
+ *                 but NOT used: a clipped read says where a junction is whatever its pair looks like.
+ *   OBSERVATIONS  record i with clip word w (bdx_clip_word) gives up to two:
+ *                   a LEFT one at  X = pos + 1     when BDX_CLIP_LEFT(w) >= min_clip  (its first aligned base: the junction lies
+ *                                                  between X - 1 and X);
+ *                   a RIGHT one at X = pos + span  when BDX_CLIP_RIGHT(w) >= min_clip and 1 <= span <= BDX_CLIP_SPAN_MAX (its last
+ *                                                  aligned base: the junction lies between X and X + 1).
+ *                 pos is the 0-based column, X 1-based, the arithmetic 64-bit; an X outside [1, 2^31 - 1] is no position and gives no
+ *                 observation.
+ *   COUNTS        an observation counts when cls[i] & BDX_CLS_PASS (so -q, 0x400 and bdx_set_mark_duplicates' marks are honoured),
+ *                 tid[i] == T and |X - P| <= window.
+ *   RESULT        per side: n the observations that count, pos the X that most of them share and peak that number.  Ties go to the
+ *                 smaller |X - P|, then to the smaller X.  With n == 0, pos and peak are 0.  All integers: the result is exact.
+ * window in [0, BDX_CLIP_WINDOW_MAX] and min_clip in [1, 255], else BDX_EINVAL.  BDX_ESTATE without bdx_use_clips, and before a run has
+ * classified the reads the context holds; otherwise state, errors and their order are those of bdx_site_end_quality.  A query is
+ * answered by the context that holds T; a chromosome it holds no reads of gives all zeros.  Not beside another call on the same context. */
+#define BDX_CLIP_SPAN_MAX 4096     /* a right clip further than this behind its read's start is not looked for (published for the tests) */
+#define BDX_CLIP_WINDOW_MAX 1023
+typedef struct bdx_clip_peaks { uint32_t n_left, n_right; int32_t pos_left, pos_right; uint32_t peak_left, peak_right; } bdx_clip_peaks;   /* 24 bytes */
+int bdx_site_clip_peaks(bdx_ctx* ctx, const bdx_site* sites, const uint8_t* end, size_t n, int32_t window, int32_t min_clip, bdx_clip_peaks* out);
 
 /* Passing read starts inside given intervals: no counterpart in the reference, which says nothing about read depth (the input of --depth's
  * RCI / RCF / RDR).  The rule, written down here once:
