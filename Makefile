@@ -8,7 +8,7 @@ KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
 HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/device_feed.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp $(HOST)/table.cpp $(HOST)/store_counts.cpp $(HOST)/inputs.cpp $(HOST)/estimate.cpp $(HOST)/mini.cpp
 
-all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check bin/bdx-feed-probe tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so oracle
+all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check bin/bdx-feed-probe tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so tests/prims/libbdx_assemble.so oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -99,6 +99,11 @@ tests/prims/libbdx_stages.so: tests/prims/stages.hip $(CSRC)/k3_regions.hip $(CS
 tests/prims/libbdx_compact.so: tests/prims/compact.hip $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/bdx_finalize.h $(CSRC)/bdx_dev.h include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -shared -Wl,--no-undefined -o $@ tests/prims/compact.hip $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip
 
+# test tooling: K6's pair groups, components, device walks and final table on their own -- launch_k6_groups, launch_k6_walk and launch_k6_table with
+# their translation unit and the host walk's, unchanged, behind plain C entry points (tests/test_gpu_assemble.py); nothing of it goes into libbdx.so
+tests/prims/libbdx_assemble.so: tests/prims/assemble.hip $(CSRC)/k6_assemble.hip $(CSRC)/bdx_walk.cpp $(CSRC)/bdx_walk.h $(CSRC)/bdx_insert.h $(CSRC)/bdx_poisson.h $(CSRC)/bdx_k3.h $(CSRC)/bdx_scan.h $(CSRC)/bdx_dev.h include/bdx.h
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -shared -Wl,--no-undefined -o $@ tests/prims/assemble.hip $(CSRC)/k6_assemble.hip $(CSRC)/bdx_walk.cpp
+
 # measurement tool (bench.py): the feeder's ceilings -- page cache -> pinned -> HBM
 bin/bdx-feed-probe: tools/feed_probe.hip
 	@mkdir -p bin
@@ -116,7 +121,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so
+	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so tests/prims/libbdx_assemble.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

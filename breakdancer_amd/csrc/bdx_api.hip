@@ -1102,21 +1102,7 @@ int size_join(StageBufs& b, const StageDims& d, std::string* err) {
     return BDX_OK;
 }
 
-// capacities of K6's lists for `na` regions: candidates and list entries <= reads / 2, each consuming a read pair
-struct K6Caps {
-    uint32_t sv, term, cn, lib_stride;
-    size_t p2, nsort;   // the inserted list (k6_insert_kernel): device order keys padded to a power of two for the sort; k6_ranksort_kernel's output (lists of that many entries at most)
-};
-K6Caps k6_caps(const StageDims& d) {
-    K6Caps k{};
-    const uint32_t na = d.k6_regions();
-    k.sv = na / 2 + 1; k.term = na / 2 + 1; k.cn = (na / 2 + 1) * (uint32_t)d.nkeys;
-    k.lib_stride = (uint32_t)std::min(d.nlibs, kK6LibStride);
-    k.p2 = 1;
-    while (k.p2 < k.sv) k.p2 <<= 1;
-    k.nsort = std::min<size_t>(k.sv, kK6RankSortMax);
-    return k;
-}
+K6Caps k6_caps(const StageDims& d) { return k6_caps_of(d.k6_regions(), d.nkeys, d.nlibs); }
 
 int size_k6(StageBufs& b, const StageDims& d, hipStream_t s, std::string* err) {
     const size_t cap = d.k6_regions();
@@ -1482,13 +1468,7 @@ int stage_host_svs(bdx_ctx* c, K6Arrays& a) {
         uint64_t* hkey = c->h_hs_aux.as<uint64_t>();
         uint32_t* hcnt = (uint32_t*)(hkey + nh);
         for (uint32_t j = 0; j < nh; ++j) {
-            // order key (see K6Arrays): a traversal started at one of its window's own vertices is placed right before the
-            // device's candidates of that start vertex, one started from an earlier window's vertex before all of its window
-            const uint64_t key = H.sv_key[j];
-            const bool from_old = !((key >> 32) & 1ull);
-            const uint64_t start = key & 0xffffffffull;
-            const uint64_t T = from_old ? (key >> 33) * period : start;
-            hkey[j] = (T << 34) | (from_old ? 0ull : 1ull << 33) | (start << 7);
+            hkey[j] = host_order_key(H.sv_key[j], period);
             if (a.force_host) hkey[j] = 0;  // no device candidates to interleave with (and the ids may carry the phantom shift)
             hcnt[j] = (uint32_t)H.svs[j].sv.lib_count | ((uint32_t)H.svs[j].sv.cn_count << 16);
         }

@@ -1803,7 +1803,7 @@ int DistRun::merge_tables(const Regions& B, const Packages& G, const TableCounts
                 size_t bad = 0;
                 for (size_t i = 1; i < kk.size(); ++i) bad += kk[i] < kk[i - 1];
                 fprintf(stderr, "[bdx dist] table of rank %d: %zu rows, %zu out of key order; first keys", q, kk.size(), bad);
-                for (size_t i = 0; i < kk.size() && i < 6; ++i) fprintf(stderr, " (T %llu own %llu start %llu)", kk[i] >> 34, (kk[i] >> 33) & 1, (kk[i] >> 7) & 0x3FFFFFF);
+                for (size_t i = 0; i < kk.size() && i < 6; ++i) fprintf(stderr, " (T %llu own %llu start %llu)", kk[i] >> kKeyShiftT, (kk[i] >> kKeyShiftOwn) & 1, (kk[i] >> kKeyShiftStart) & kKeyStartMask);
                 fprintf(stderr, "\n");
             }
         }

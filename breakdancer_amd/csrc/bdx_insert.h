@@ -7,23 +7,8 @@
 
 namespace bdx {
 
-// order key of a candidate that is placed by key (see K6Arrays)
-constexpr int kKeyShiftT = 34, kKeyShiftStart = 7;
-// Both walks count the candidates that the traversals started at vertices of EARLIER windows emit into one flush window (nseq: from 0
-// per component and window, running on over those start vertices) and keep 7 bits of the count.  A candidate consumes one pair group,
-// every group once, and a window's flush consumes only groups whose later region lies in that window, never the self group of an
-// earlier window's region.
-//   k6_walk_kernel (<= kK6MaxMembers = 4 regions): 4 * 3 / 2 groups between the regions and, with one region in an earlier window,
-//     3 self groups: nseq <= 8, asserted below.
-//   walk_big (<= kK6BigMembers = 64 regions): a group is found through its later region's list of incoming groups (kK6MaxIn = 3
-//     entries; a region with more sends its component to the host), so m regions of one window take at most 4 m - 3 candidates (the
-//     first of them has one earlier region to be reached from, the second two): 249 for m = 63.  NO bound below 128 holds here.  The
-//     smallest component past it has 34 regions: one in a window, 33 in the next, these with their self groups and three incoming
-//     groups each (one and two for the first two), every candidate passing process_sv's gates -- 129 candidates of one (T, start), the
-//     last with the key of the first.  The rank and bucket routes of the merge below assume keys that differ (k6_ranksort_kernel
-//     alone settles equal keys by index).
-constexpr uint32_t kKeySeqMask = 127u;
-static_assert(kK6MaxMembers * (kK6MaxMembers - 1) / 2 + (kK6MaxMembers - 1) <= (int)kKeySeqMask + 1, "k6_walk_kernel: the candidates of one component and window have sequence numbers of their own");
+// (the order key of a candidate that is placed by key, its constants and the bounds of its sequence number: bdx_k3.h.  The rank and bucket
+// routes of the merge below assume keys that differ; k6_ranksort_kernel alone settles equal keys by index.)
 
 __device__ __forceinline__ uint32_t count_below(const uint32_t* v, uint32_t n, uint32_t x) {  // #elements < x, v ascending
     uint32_t lo = 0, hi = n;
@@ -78,7 +63,7 @@ __device__ __forceinline__ uint64_t ins_bucket_span(uint32_t n_regions, uint32_t
 }
 __device__ __forceinline__ uint32_t ins_bucket_of(uint64_t key, uint32_t period, uint64_t span) {
     constexpr uint32_t kSub = kInsSub;
-    const uint32_t T = (uint32_t)(key >> kKeyShiftT), own = (uint32_t)(key >> 33) & 1u, start = (uint32_t)(key >> kKeyShiftStart) & 0x3FFFFFFu;
+    const uint32_t T = (uint32_t)(key >> kKeyShiftT), own = (uint32_t)(key >> kKeyShiftOwn) & 1u, start = (uint32_t)(key >> kKeyShiftStart) & kKeyStartMask;
     const uint32_t W = T / period, r = T - W * period;
     uint32_t sub = kSub;   // (a threshold inside a window, or a candidate of its own window: behind every entry of that flush)
     if (!r && !own) {

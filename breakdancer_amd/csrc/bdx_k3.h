@@ -195,6 +195,53 @@ constexpr int kK6LabelRounds = 2;  // min-label propagation rounds (the first in
                                    // the closure check and goes to the host
 constexpr int kK6LabelRoundsGather = 3;  // ... in rank 0's device walk of the components gathered from a sharded run's ranks
 
+// Order key of a candidate that is placed by key (see K6Arrays): T << kKeyShiftT | own << kKeyShiftOwn | start << kKeyShiftStart | sequence
+// number.  Every writer and reader of the layout goes through these: both walks, stage_host_svs, ins_bucket_of, the score kernel's sv_key.
+// Region ids (T, start) have 26 bits (kMaxRegions).  The sequence number counts the candidates that the traversals started at vertices of
+// EARLIER windows emit into one flush window (from 0 per component and window, running on over those start vertices).  A candidate consumes
+// one pair group, every group once, and a window's flush consumes only groups whose later region lies in that window, never the self group
+// of an earlier window's region.
+//   k6_walk_kernel (<= kK6MaxMembers = 4 regions): 4 * 3 / 2 groups between the regions and, with one region in an earlier window,
+//     3 self groups: at most 9 candidates.
+//   walk_big (<= kK6BigMembers = 64 regions): a group is found through its later region's list of incoming groups (kK6MaxIn = 3 entries;
+//     a region with more sends its component to the host), so m regions of one window take at most 4 m - 3 candidates (the first of them
+//     has one earlier region to be reached from, the second two): 249 for m = 63, every one of them passing process_sv's gates only
+//     where -r is 0 or less (a self group's reads have left with the group that reached its region).  Seven bits were one too few: 34
+//     regions, one in a window and 33 in the next with their self groups and three incoming groups each, emit 129.
+constexpr int kKeyShiftT = 35, kKeyShiftOwn = 34, kKeyShiftStart = 8;
+constexpr uint32_t kKeySeqMask = 255u;
+constexpr uint32_t kKeyStartMask = (1u << 26) - 1;
+static_assert(kKeyShiftOwn == kKeyShiftStart + 26 && kKeyShiftT == kKeyShiftOwn + 1 && kKeyShiftT + 26 <= 64 && kKeySeqMask + 1 == 1u << kKeyShiftStart,
+              "order key: sequence number, 26 bits of start vertex, the own bit, 26 bits of T");
+static_assert(kK6MaxMembers * (kK6MaxMembers - 1) / 2 + (kK6MaxMembers - 1) <= (int)kKeySeqMask + 1, "k6_walk_kernel: the candidates of one component and window have sequence numbers of their own");
+static_assert(4 * (kK6BigMembers - 1) - 3 <= (int)kKeySeqMask + 1, "walk_big: the candidates of one component and window have sequence numbers of their own");
+__host__ __device__ __forceinline__ uint64_t order_key(uint64_t T, bool own, uint64_t start, uint32_t seq) {
+    return (T << kKeyShiftT) | (own ? 1ull << kKeyShiftOwn : 0ull) | (start << kKeyShiftStart) | (uint64_t)(seq & kKeySeqMask);
+}
+// the host walk's key of a traversal (sv_order_key, bdx_walk.h: window << 33 | own << 32 | start) as the order key its candidates are
+// placed by: a traversal started at one of its window's own vertices is placed right before the device's candidates of that start vertex,
+// one started from an earlier window's vertex before all of its window
+inline uint64_t host_order_key(uint64_t walk_key, uint64_t period) {
+    const bool from_old = !((walk_key >> 32) & 1ull);
+    const uint64_t start = walk_key & 0xffffffffull;
+    return order_key(from_old ? (walk_key >> 33) * period : start, !from_old, start, 0);
+}
+
+// capacities of K6's lists for `na` regions: candidates and list entries <= reads / 2, each consuming a read pair
+struct K6Caps {
+    uint32_t sv, term, cn, lib_stride;
+    size_t p2, nsort;   // the inserted list (k6_insert_kernel): device order keys padded to a power of two for the sort; k6_ranksort_kernel's output (lists of that many entries at most)
+};
+inline K6Caps k6_caps_of(uint32_t na, int nkeys, int nlibs) {
+    K6Caps k{};
+    k.sv = na / 2 + 1; k.term = na / 2 + 1; k.cn = (na / 2 + 1) * (uint32_t)nkeys;
+    k.lib_stride = (uint32_t)(nlibs < kK6LibStride ? nlibs : kK6LibStride);
+    k.p2 = 1;
+    while (k.p2 < k.sv) k.p2 <<= 1;
+    k.nsort = k.sv < kK6RankSortMax ? k.sv : kK6RankSortMax;
+    return k;
+}
+
 struct RegSum {        // per accepted region r, written by k6_pairs_kernel
     uint32_t np_all;   // sorted, merged (lo, flag, lib) parts of the pairs whose second mate is in r, at parts[first ..)
     uint32_t np_emit;  // those the host walk would need: the self group and every group that passes the gate
@@ -315,7 +362,7 @@ struct K6Arrays {
     // Candidates that are placed by their order key instead of by their start vertex: the host walk's (pinned host
     // memory) and the device's own whose traversal started from a vertex of an earlier flush window.  k6_insert_kernel
     // merges the two lists by key; entry j of the merged list precedes the candidates of start vertex ins_T[j] and after.
-    // Order key: (T << 34) | (started at a vertex of its own window ? 1 << 33 : 0) | (start vertex << 7) | sequence number,
+    // Order key (order_key above): T | started at a vertex of its own window | start vertex | sequence number,
     // T = the start vertex, or the first vertex of the flush window for a traversal started from an earlier window's vertex.
     const SvOut* hs_rec;           // [nh] lib_begin / cn_begin index the host lists below
     const uint64_t* hs_key;        // [nh] ascending order keys
@@ -367,7 +414,7 @@ struct K6Arrays {
     // the ranks between k6_pairs_kernel and k6_classify_kernel): their components go to the host list, i.e. to rank 0's walk
     uint8_t* taint;                // [cap]; null: single-context run
     int wire_rows;                 // sv_out takes SvWire rows (the table goes to pinned host memory: single-context runs)
-    unsigned long long* sv_key;    // [sv_cap] order key of every row of the final table (T << 34 | own << 33 | start << 7): what rank 0 merges
+    unsigned long long* sv_key;    // [sv_cap] order key of every row of the final table (order_key with sequence number 0): what rank 0 merges
                                    // the ranks' tables by; null: not wanted
 };
 

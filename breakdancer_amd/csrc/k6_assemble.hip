@@ -566,7 +566,10 @@ __device__ bool assemble_sv(const K6Arrays& a, const RunConst& rc_, const PartRe
 
     if (ncn != 0x7FFFFFFFu) KPROF(kprow, 3);   // (the proper-read samples have arrived: copy numbers done)
     if (flag != BDX_ARP_RF && flag != BDX_ARP_RR && pos[0] + max_readlen - 5 < pos[1]) pos[0] += max_readlen - 5;
-    const int diffspan = (int)((double)__fdiv_rn(diff, (float)flag_count) + 0.5);
+    // (a candidate without a read -- every gate is open at -r 0 or less -- divides 0 by 0: int(NaN) is INT_MIN on x86-64 (cvttsd2si), where the
+    // reference and the host walk run; the device's conversion gives 0)
+    const double dspan = __dadd_rn((double)__fdiv_rn(diff, (float)flag_count), 0.5);
+    const int diffspan = (dspan != dspan || dspan >= 2147483648.0 || dspan <= -2147483649.0) ? INT32_MIN : (int)dspan;
 
     SvOut o;
     for (int i = 0; i < 2; ++i) { o.sv.chr[i] = chr[i]; o.sv.pos[i] = pos[i] + 1; o.sv.fwd[i] = fwd[i]; o.sv.rev[i] = rev[i]; }
@@ -829,7 +832,7 @@ __device__ __forceinline__ void walk_big(const K6Arrays& a, BigTab& B, uint32_t 
                             if (from_old) {
                                 if (lane == 0) {
                                     const uint32_t q = atomicAdd(&a.counts->n_old, 1u);
-                                    a.old_key[q] = ((uint64_t)(W * period) << kKeyShiftT) | ((uint64_t)start << kKeyShiftStart) | (uint64_t)(nseq & kKeySeqMask);
+                                    a.old_key[q] = order_key(W * period, false, start, nseq);
                                     a.old_slot[q] = slot;
                                 }
                                 ++nseq;
@@ -1150,7 +1153,7 @@ __global__ __launch_bounds__(64) void k6_walk_kernel(K6Arrays a) {
                                 c == 0 ? 16384u + blockIdx.x : ~0u)) {
                     if (from_old) {  // placed by its order key: after the earlier windows, before this window's own
                         const uint32_t q = atomicAdd(&a.counts->n_old, 1u);
-                        a.old_key[q] = ((uint64_t)(W * period) << kKeyShiftT) | ((uint64_t)start << kKeyShiftStart) | (uint64_t)(nseq & kKeySeqMask);
+                        a.old_key[q] = order_key(W * period, false, start, nseq);
                         a.old_slot[q] = slot;
                         ++nseq;
                     } else {
@@ -1387,7 +1390,7 @@ __global__ __launch_bounds__(kScanBlock) void k6_score_kernel(K6Arrays a, double
         }
         if (a.sv_key && act) {   // placed at vertex T: before T's own candidates unless the traversal started at T itself
             const unsigned long long T = a.sv_vx[c0 + lane], st = o->start;
-            a.sv_key[c0 + lane] = (T << kKeyShiftT) | (T == st ? 1ull << 33 : 0ull) | (st << kKeyShiftStart);
+            a.sv_key[c0 + lane] = order_key(T, T == st, st, 0);
         }
         const uint32_t npr = (uint32_t)__popcll(__ballot(pr));
         if (lane == 0 && npr) atomicAdd(&s_printed, npr);

@@ -3,7 +3,7 @@ k6_ranksort_kernel, k6_insert_kernel) to them through tests/prims/prims.hip.  No
 checks the reference against a naive placement, the model against the routes the cases are there for, and the cases against slips
 of the two index computations no library restates.
 
-Order key: T << 34 | own << 33 | start << 7 | sequence number.  The device's list (any order, keys that differ) and the host's
+Order key (csrc/bdx_k3.h): T << 35 | own << 34 | start << 8 | sequence number.  The device's list (any order, keys that differ) and the host's
 (ascending, runs of equal keys) never share a (T, own, start).  The reference is a plain stable merge: numpy's stable argsort over
 the host's keys followed by the device's sorted ones; the running totals are numpy's cumulative sums in uint32."""
 import numpy as np
@@ -25,14 +25,15 @@ CONSTANTS = [INS_THREADS, INS_LDS, INS_BUCKET_MAX, INS_CNT_LDS, INS_BUCKETS, INS
 INS_SUB = 64             # kInsSub
 FILL = 0xA5A5A5A5
 HOST_BIT = 0x80000000
-SHIFT_T, SHIFT_START = 34, 7
+SHIFT_T, SHIFT_OWN, SHIFT_START = 35, 34, 8     # kKeyShiftT, kKeyShiftOwn, kKeyShiftStart
+SEQ_MASK = 255                                # kKeySeqMask
 START_MASK = 0x3FFFFFF
 
 ROUTES = ("rank", "bucket", "lds_bitonic", "hbm_bitonic", "ranksort")
 
 
 def make_key(T, own, start, seq):
-    return (np.asarray(T, np.uint64) << np.uint64(SHIFT_T)) | (np.asarray(own, np.uint64) << np.uint64(33)) | (np.asarray(start, np.uint64) << np.uint64(SHIFT_START)) | np.asarray(seq, np.uint64)
+    return (np.asarray(T, np.uint64) << np.uint64(SHIFT_T)) | (np.asarray(own, np.uint64) << np.uint64(SHIFT_OWN)) | (np.asarray(start, np.uint64) << np.uint64(SHIFT_START)) | np.asarray(seq, np.uint64)
 
 
 # ---- the route model ----------------------------------------------------------------------------------------------------------
@@ -43,7 +44,7 @@ def bucket_model(keys, n_regions, period, clamp=True):
     span = (n_regions // period + 2) * INS_SUB + 1
     k = np.asarray(keys, np.uint64)
     T = (k >> np.uint64(SHIFT_T)).astype(np.int64)
-    own = ((k >> np.uint64(33)) & np.uint64(1)).astype(np.int64)
+    own = ((k >> np.uint64(SHIFT_OWN)) & np.uint64(1)).astype(np.int64)
     start = ((k >> np.uint64(SHIFT_START)) & np.uint64(START_MASK)).astype(np.int64)
     W = T // period
     r = T - W * period
@@ -119,7 +120,7 @@ def host_keys(rng, nh, n_regions, period, mode="any"):
 
 
 def device_pool(rng, want, n_regions, period, far=0.25, ge=0.0, w_lo=1, w_hi=None):
-    """keys as the walks write them: T = W * period, own bit 0, sequence number <= 127; the start vertex in the window before T, far
+    """keys as the walks write them: T = W * period, own bit 0, sequence number <= SEQ_MASK; the start vertex in the window before T, far
     before it (translocations), or -- ge -- at or behind it.  More than `want` distinct keys in random order"""
     period = max(period, 1)
     w_max = n_regions // period if w_hi is None else w_hi
@@ -135,7 +136,7 @@ def device_pool(rng, want, n_regions, period, far=0.25, ge=0.0, w_lo=1, w_hi=Non
     gev = np.minimum(T + rng.integers(0, 1000, m), START_MASK)
     start = np.where(u < ge, gev, np.where(u < ge + far, farv, local))
     start = np.where(T == 0, gev, start)
-    k = np.unique(make_key(T, 0, start, rng.integers(0, 128, m)))
+    k = np.unique(make_key(T, 0, start, rng.integers(0, SEQ_MASK + 1, m)))
     rng.shuffle(k)
     return k
 
@@ -160,11 +161,11 @@ def thin(pool, n_regions, period, most=64, keep_out=()):
     return out
 
 
-def window_pool(W, period, starts=None):
-    """every key of window W's threshold with a start vertex of the window before (or the given ones) and every sequence number"""
+def window_pool(W, period, starts=None, nseq=128):
+    """every key of window W's threshold with a start vertex of the window before (or the given ones) and the sequence numbers 0 .. nseq - 1"""
     T = W * period
     s = np.arange(max(T - period, 0), max(T, 1)) if starts is None else np.asarray(starts)
-    s, q = np.meshgrid(s, np.arange(128), indexing="ij")
+    s, q = np.meshgrid(s, np.arange(nseq), indexing="ij")
     return make_key(T, 0, s.ravel(), q.ravel())
 
 
@@ -211,6 +212,10 @@ def _cases():
         out.append(case("depth-128-%s" % where, 2048, 300, gen="deep", W=W, depth=INS_BUCKET_DEPTH))
         out.append(case("depth-129-%s-lds" % where, 2048, 300, gen="deep", W=W, depth=INS_BUCKET_DEPTH + 1, crowded=True))
         out.append(case("depth-129-%s-hbm" % where, 4000, 300, gen="deep", W=W, depth=INS_BUCKET_DEPTH + 1, crowded=True))
+    # the same bucket filled with sequence numbers 128 ... 255 alone (the key's eighth bit): rank counting, the buckets, the LDS sort
+    out.append(case("depth-128-high-seq-rank", 1000, 300, gen="deep", W=1500, depth=INS_BUCKET_DEPTH, seqs=SEQ_MASK + 1))
+    out.append(case("depth-128-high-seq", 2048, 300, gen="deep", W=1500, depth=INS_BUCKET_DEPTH, seqs=SEQ_MASK + 1))
+    out.append(case("depth-129-high-seq-lds", 2048, 300, gen="deep", W=1500, depth=INS_BUCKET_DEPTH + 1, crowded=True, seqs=SEQ_MASK + 1))
     # interleaving
     for nd in (900, 3000, 9000):
         out.append(case("device-below-host-%d" % nd, nd, 900, gen="split", device_first=True))
@@ -298,7 +303,10 @@ def build(c):
         # `depth` entries in the bucket of window W's last sub-slots (T = 0: of its only one), host keys of the same threshold among them, and a
         # list around them that leaves this bucket alone and is thin elsewhere
         W, depth = a["W"], a["depth"]
-        wp = window_pool(W, P, None if W else np.arange(0, 400))
+        seqs = a.get("seqs", 128)
+        wp = window_pool(W, P, None if W else np.arange(0, 400), nseq=seqs)
+        if seqs > 128:
+            wp = wp[(wp & np.uint64(SEQ_MASK)) >= np.uint64(128)]
         b = bucket_model(wp, R, P)
         target = int(b.max())
         inside = wp[b == target]
@@ -318,7 +326,7 @@ def build(c):
         mid = (R // P) // 2
         lo, hi = dict(w_lo=1, w_hi=mid - 1), dict(w_lo=mid + 1, w_hi=R // P)
         dk = device_pool(rng, nd, R, P, **(lo if a["device_first"] else hi))
-        hp = device_pool(rng, nh, R, P, **(hi if a["device_first"] else lo))[:nh] & ~np.uint64(127)
+        hp = device_pool(rng, nh, R, P, **(hi if a["device_first"] else lo))[:nh] & ~np.uint64(SEQ_MASK)
         extra = make_key((hp >> np.uint64(SHIFT_T)) + np.uint64(3), 1, hp >> np.uint64(SHIFT_T), 0)[: nh // 3]   # thresholds inside a window, own bit set
         hk = np.concatenate([hp[: nh - len(extra)], extra])
         hk.sort()
@@ -332,7 +340,7 @@ def build(c):
         if c["expect"] == "bucket":
             p = np.sort(thin(p, R, P, most=100))
         p = p[: nd + nh]
-        dk, hk = p[0::2].copy(), (p[1::2] & ~np.uint64(127))
+        dk, hk = p[0::2].copy(), (p[1::2] & ~np.uint64(SEQ_MASK))
         rng.shuffle(dk)
     elif gen == "runs":
         # runs of one host key, device keys of the same threshold at the start vertices on both sides of it

@@ -25,7 +25,7 @@ def same(a, b):
 
 
 def test_the_generators_keep_the_kernels_preconditions(built):
-    """device keys that differ, with the own bit clear, T a multiple of the period and 7 bits of sequence number; host keys ascending with
+    """device keys that differ, with the own bit clear, T a multiple of the period and a sequence number inside its bits; host keys ascending with
     sequence number 0 and runs of equal keys somewhere; no (T, own, start) on both sides; slots that differ, below the staging size"""
     runs = 0
     for c in ALL:
@@ -33,9 +33,9 @@ def test_the_generators_keep_the_kernels_preconditions(built):
         dk, hk = d["old_key"], d["hs_key"]
         assert len(dk) == c["nd"] and len(hk) == c["nh"], c["name"]
         assert len(np.unique(dk)) == len(dk), c["name"]
-        assert ((dk >> np.uint64(33)) & np.uint64(1) == 0).all(), c["name"]
+        assert ((dk >> np.uint64(ic.SHIFT_OWN)) & np.uint64(1) == 0).all(), c["name"]
         assert ((dk >> np.uint64(ic.SHIFT_T)) % np.uint64(max(c["period"], 1)) == 0).all(), c["name"]
-        assert (hk[1:] >= hk[:-1]).all() and (hk & np.uint64(127) == 0).all(), c["name"]
+        assert (hk[1:] >= hk[:-1]).all() and (hk & np.uint64(ic.SEQ_MASK) == 0).all(), c["name"]
         assert not np.isin(dk >> np.uint64(ic.SHIFT_START), hk >> np.uint64(ic.SHIFT_START)).any(), c["name"]
         assert len(np.unique(d["old_slot"])) == c["nd"] and (d["old_slot"] < 2 * c["handle"][0]).all(), c["name"]
         assert d["cnt_by_slot"].max(initial=0) < 65536
