@@ -4,11 +4,11 @@ ARCH ?= gfx950
 CSRC := breakdancer_amd/csrc
 HOST := breakdancer_amd/host
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-result -Iinclude
-KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/kq_queries.hip $(CSRC)/kp_clip.hip $(CSRC)/kr_depth.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/kh_insert_hist.hip $(CSRC)/km_mini.hip $(CSRC)/bdx_api.hip
+KERNELS := $(CSRC)/k1_classify.hip $(CSRC)/k2_compact.hip $(CSRC)/k3_regions.hip $(CSRC)/k4_join.hip $(CSRC)/k5_poisson.hip $(CSRC)/k6_assemble.hip $(CSRC)/k7_exchange.hip $(CSRC)/kq_queries.hip $(CSRC)/kp_clip.hip $(CSRC)/kr_depth.hip $(CSRC)/k9_shard.hip $(CSRC)/kz_inflate.hip $(CSRC)/kb_records.hip $(CSRC)/kx_exclude.hip $(CSRC)/kd_markdup.hip $(CSRC)/kc_insert_stats.hip $(CSRC)/kh_insert_hist.hip $(CSRC)/km_mini.hip $(CSRC)/ka_anchor.hip $(CSRC)/bdx_api.hip
 OBJS := $(KERNELS:.hip=.o) $(CSRC)/bdx_walk.o $(CSRC)/bdx_walk_reads.o
-HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/device_feed.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp $(HOST)/table.cpp $(HOST)/store_counts.cpp $(HOST)/inputs.cpp $(HOST)/estimate.cpp $(HOST)/mini.cpp
+HOSTCOMMON := $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/bam_reader.cpp $(HOST)/fast_inflate.cpp $(HOST)/column_reader.cpp $(HOST)/producer.cpp $(HOST)/device_feed.cpp $(HOST)/dumps.cpp $(HOST)/cache.cpp $(HOST)/vcf.cpp $(HOST)/exclude.cpp $(HOST)/sites.cpp $(HOST)/table.cpp $(HOST)/store_counts.cpp $(HOST)/inputs.cpp $(HOST)/estimate.cpp $(HOST)/mini.cpp $(HOST)/anchor.cpp
 
-all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check bin/bdx-feed-probe tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so tests/prims/libbdx_assemble.so oracle
+all: breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-anchor-check bin/bdx-table-check bin/bdx-feed-check bin/bdx-feed-probe tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so tests/prims/libbdx_assemble.so oracle
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/bdx.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -73,6 +73,11 @@ bin/bdx-mini-check: $(HOST)/mini_check_main.cpp $(HOST)/mini.cpp $(HOST)/mini.h 
 	@mkdir -p bin
 	g++ $(HOSTFLAGS) -o $@ $(HOST)/mini_check_main.cpp $(HOST)/mini.cpp
 
+# test tooling: the host half of --anchor (anchor.cpp) on rows given as text, without libbdx (tests/test_anchor.py)
+bin/bdx-anchor-check: $(HOST)/anchor_check_main.cpp $(HOST)/anchor.cpp $(HOST)/anchor.h $(HOST)/mini.h include/bdx.h
+	@mkdir -p bin
+	g++ $(HOSTFLAGS) -o $@ $(HOST)/anchor_check_main.cpp $(HOST)/anchor.cpp
+
 # test tooling: the table formatter (table.cpp) on its own, without libbdx (tests/test_table.py builds it again under the sanitizers)
 bin/bdx-table-check: $(HOST)/table_check_main.cpp $(HOST)/table.cpp $(HOST)/options.cpp $(HOST)/config.cpp $(HOST)/table.h $(HOST)/options.h $(HOST)/config.h include/bdx.h
 	@mkdir -p bin
@@ -121,7 +126,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-table-check bin/bdx-feed-check tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so tests/prims/libbdx_assemble.so
+	rm -f $(CSRC)/*.o breakdancer_amd/libbdx.so bin/breakdancer-max bin/bdx-dump-reads bin/bam2cfg bin/bdx-feed-probe bin/bdx-inflate-check bin/bdx-sites-check bin/bdx-ci-check bin/bdx-depth-check bin/bdx-mapq-check bin/bdx-clip-check bin/bdx-clip-store bin/bdx-estimate-check bin/bdx-mini-check bin/bdx-anchor-check bin/bdx-table-check bin/bdx-feed-check tests/prims/libbdx_prims.so tests/prims/libbdx_stages.so tests/prims/libbdx_compact.so tests/prims/libbdx_assemble.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

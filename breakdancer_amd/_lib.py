@@ -60,7 +60,7 @@ EXPORTS = ["bdx_opts_default", "bdx_create", "bdx_destroy", "bdx_strerror", "bdx
            "bdx_count_junction_pairs", "bdx_bamdec_set_exclude", "bdx_bamdec_excluded", "bdx_exclude_mask", "bdx_count_site_pairs", "bdx_site_breakpoint_bounds", "bdx_count_interval_reads", "bdx_site_end_quality",
            "bdx_set_mark_duplicates", "bdx_get_duplicates", "bdx_dist_set_mark_duplicates", "bdx_dist_get_duplicates", "bdx_mark_duplicates",
            "bdx_insert_size_histogram", "bdx_dist_insert_size_histogram", "bdx_estimate_insert_size", "bdx_set_libs", "bdx_dist_set_libs",
-           "bdx_set_insert_null", "bdx_window_insert_shift", "bdx_insert_shift_score",
+           "bdx_set_insert_null", "bdx_window_insert_shift", "bdx_insert_shift_score", "bdx_window_anchor_split",
            "bdx_clip_word", "bdx_use_clips", "bdx_put_clips", "bdx_get_clips", "bdx_site_clip_peaks", "bdx_bamdec_fetch_clips"]
 
 # kDupT (csrc/bdx_dev.h): KD compares the records of a run directly when the run has at most this many, longer runs go through its table
@@ -89,6 +89,10 @@ MINI_CAP = 4096
 # bdx_insert_shift: one library's row of one window: observations, those beyond the bins, saturated, pad, the sum of the observations, and
 # n N times the one-sided Kolmogorov-Smirnov distances against the null
 INSERT_SHIFT_DTYPE = np.dtype([("n", "<u4"), ("n_over", "<u4"), ("saturated", "<u4"), ("pad", "<u4"), ("sum", "<u8"), ("t_plus", "<i8"), ("t_minus", "<i8")])
+# bdx_anchor_split: one window's row of bdx_window_anchor_split: the anchors by direction, the class-9 records of low quality, the anchors
+# on either side of the split and their distinct starts, the split, and the innermost anchor position of either side (-1: none)
+ANCHOR_SPLIT_DTYPE = np.dtype([("n_fwd", "<u4"), ("n_rev", "<u4"), ("n_low", "<u4"), ("n_left", "<u4"), ("n_right", "<u4"), ("u_left", "<u4"), ("u_right", "<u4"),
+                               ("split", "<i4"), ("last_left", "<i4"), ("first_right", "<i4")])
 
 
 class bdx_insert_estimate(C.Structure):
@@ -170,6 +174,7 @@ def load():
     L.bdx_set_insert_null.argtypes = [vp, vp]
     L.bdx_window_insert_shift.argtypes = [vp, vp, C.c_size_t, vp]
     L.bdx_insert_shift_score.argtypes = [vp, C.c_uint64, vp, vp]
+    L.bdx_window_anchor_split.argtypes = [vp, vp, C.c_size_t, C.c_int32, vp]
     L.bdx_clip_word.argtypes = [vp, C.c_uint32, C.c_int32, C.c_uint32]
     L.bdx_clip_word.restype = C.c_uint32
     L.bdx_use_clips.argtypes = [vp, C.c_int]

@@ -472,6 +472,21 @@ class BreakDancer:
         self._chk(self.lib.bdx_window_insert_shift(self.h, p(iv), len(iv), p(out)), "bdx_window_insert_shift")
         return out
 
+    def window_anchor_split(self, intervals, min_qual=-1):
+        """The one-end-anchored reads of the last run that start inside given windows, and the position that best splits them
+        (bdx_window_anchor_split; the rule is in include/bdx.h): `intervals` as for count_interval_reads.  A record of class
+        MATE_UNMAPPED whose quality passes -- above its library's minimum with min_qual = -1, at least min_qual otherwise -- is an anchor
+        and points right on the forward strand (left under -l).  Returns an (n,) array of _lib.ANCHOR_SPLIT_DTYPE."""
+        if isinstance(intervals, np.ndarray) and intervals.dtype == L.INTERVAL_DTYPE:
+            iv = np.ascontiguousarray(intervals)
+        else:
+            rows = [tuple(int(v) for v in r) for r in intervals]
+            iv = np.array(rows, dtype=L.INTERVAL_DTYPE) if rows else np.zeros(0, dtype=L.INTERVAL_DTYPE)
+        out = np.zeros(len(iv), dtype=L.ANCHOR_SPLIT_DTYPE)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.bdx_window_anchor_split(self.h, p(iv), len(iv), int(min_qual), p(out)), "bdx_window_anchor_split")
+        return out
+
     def set_stage_timing(self, on=True):
         """HIP events between the stages (compact / regions / join timings); costs a few microseconds per event."""
         self._chk(self.lib.bdx_set_stage_timing(self.h, int(on)), "bdx_set_stage_timing")

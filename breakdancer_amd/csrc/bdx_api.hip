@@ -2607,6 +2607,30 @@ int bdx_insert_shift_score(const bdx_insert_shift* row, uint64_t N, double* scor
     return BDX_OK;
 }
 
+// ---- --anchor: the one-end-anchored reads of given windows and their best split (KA, ka_anchor.hip) ----
+
+int bdx_window_anchor_split(bdx_ctx* c, const bdx_interval* iv, size_t n, int32_t min_qual, bdx_anchor_split* out) {
+    bool none;
+    BDX_TRY(check_query_state(c, n, &none));
+    if (none) return BDX_OK;
+    if (!iv || !out) return fail(c, BDX_EINVAL, "null array");
+    if (min_qual < -1 || min_qual > 255) return fail(c, BDX_EINVAL, "min_qual < -1 or min_qual > 255");
+    if (n > ((size_t)1 << 31)) return fail(c, BDX_ELIMIT, "more than 2^31 intervals in one call");
+    for (size_t i = 0; i < n; ++i)
+        if (iv[i].tid < 0 || iv[i].beg < 0 || iv[i].end < iv[i].beg)
+            return fail(c, BDX_EINVAL, "interval " + std::to_string(i) + ": tid < 0, beg < 0 or end < beg");
+    // quality ABOVE least: the libraries' minima as K1 resolved them, or min_qual - 1 for every library (then no table and no lib column)
+    std::vector<int32_t> least(c->libs.size());
+    for (size_t i = 0; i < least.size(); ++i) least[i] = min_qual < 0 ? resolved_min_mapq(c->opts, c->libs[i]) : min_qual - 1;
+    const int nlibs = c->nlibs;
+    const bool many = nlibs > 1 && min_qual < 0;
+    const size_t ibytes = n * sizeof(bdx_interval);   // (12 n: the table behind it is 4-aligned)
+    return run_query(c, {{iv, ibytes}, {least.data(), many ? least.size() * 4 : 0}}, out, n * sizeof(bdx_anchor_split), [&](const char* in, void* results, hipStream_t s) {
+        launch_ka(KaParams{store_view(c), c->d.mapq, many ? c->d.lib : nullptr, (const KrInterval*)in, (uint64_t)n, nlibs, c->opts.illumina_long_insert ? 1 : 0,
+                           least.empty() ? 0 : least[0], many ? (const int32_t*)(in + ibytes) : nullptr, (KaSplit*)results}, s);
+    });
+}
+
 int bdx_set_process_option(const char* name, int value) {
     if (!name) return BDX_EINVAL;
     if (!strcmp(name, "pin_malloc")) { PinBuf::registered_switch().store(value == 0); return BDX_OK; }
@@ -2616,7 +2640,7 @@ int bdx_set_process_option(const char* name, int value) {
 int bdx_warm_up(int device) {
     if (hipSetDevice(device) != hipSuccess) return BDX_EHIP;
     warm_k1(nullptr); warm_k2(nullptr); warm_k3(nullptr); warm_k4(nullptr); warm_k5(nullptr); warm_k6(nullptr); warm_k7(nullptr); warm_k9(nullptr);
-    warm_kx(nullptr); warm_kq(nullptr); warm_kr(nullptr); warm_kp(nullptr);
+    warm_kx(nullptr); warm_kq(nullptr); warm_kr(nullptr); warm_kp(nullptr); warm_ka(nullptr);
     return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess ? BDX_OK : BDX_EHIP;
 }
 

@@ -331,6 +331,26 @@ struct KwParams {
 };
 void launch_kw(const KwParams& p, hipStream_t s);
 
+// KA (ka_anchor.hip): the one-end-anchored reads that start inside given windows and their best split (bdx_window_anchor_split)
+struct KaSplit {                        // = bdx_anchor_split (include/bdx.h)
+    uint32_t n_fwd, n_rev, n_low;
+    uint32_t n_left, n_right, u_left, u_right;
+    int32_t split, last_left, first_right;
+};
+struct KaParams {
+    StoreView st;
+    const uint8_t* mapq;                // quality column (AM tag if present, else MAPQ); read only for class-9 records
+    const uint8_t* lib;                 // library column; read only when qtab is given
+    const KrInterval* iv;
+    uint64_t nq;                        // up to 2^31: the grid strides over them
+    int nlibs;                          // 1..255
+    int32_t long_insert;                // -l: reads point away from their fragment
+    int32_t q0;                         // a candidate is an anchor when its quality is ABOVE this (min_qual - 1, or library 0's minimum) ...
+    const int32_t* qtab;                // ... or above its library's [nlibs]; null: q0 for every record (one library, or min_qual >= 0)
+    KaSplit* out;                       // [nq]
+};
+void launch_ka(const KaParams& p, hipStream_t s);
+
 // KD (kd_markdup.hip): duplicate marking over the resident store (bdx_set_mark_duplicates, bdx_mark_duplicates)
 constexpr int kDupT = 64;               // neighbours a record looks at each way; runs of more records go through the table
 struct KdCounts {

@@ -170,6 +170,6 @@ void launch_k9_bucket_groups(const unsigned long long* base, const SegList& sg, 
 
 // one no-op launch per translation unit (see bdx_warm_up)
 void warm_k1(hipStream_t s); void warm_k2(hipStream_t s); void warm_k3(hipStream_t s); void warm_k4(hipStream_t s);
-void warm_k5(hipStream_t s); void warm_k6(hipStream_t s); void warm_k7(hipStream_t s); void warm_k9(hipStream_t s); void warm_kq(hipStream_t s); void warm_kr(hipStream_t s); void warm_kp(hipStream_t s);
+void warm_k5(hipStream_t s); void warm_k6(hipStream_t s); void warm_k7(hipStream_t s); void warm_k9(hipStream_t s); void warm_kq(hipStream_t s); void warm_kr(hipStream_t s); void warm_kp(hipStream_t s); void warm_ka(hipStream_t s);
 
 }  // namespace bdx

@@ -209,6 +209,11 @@ class DistRun:
         (a sequence this rank holds nothing of gives zero rows)"""
         return self.context().window_insert_shift(intervals)
 
+    def window_anchor_split(self, intervals, min_qual=-1):
+        """bdx_window_anchor_split over this rank's own store, after run: the caller sends a window to the rank that holds its sequence
+        (a sequence this rank holds nothing of gives empty rows)"""
+        return self.context().window_anchor_split(intervals, min_qual)
+
     def set_libs(self, libs, max_read_window_size):
         """bdx_dist_set_libs: the libraries and the initial window of the run that follows, on every rank alike"""
         libs = list(libs)

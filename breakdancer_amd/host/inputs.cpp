@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "anchor.h"
 #include "mini.h"
 #include "producer.h"
 #include "store_counts.h"
@@ -146,6 +147,11 @@ Inputs::Inputs(int argc, char** argv, const Env& env)
         mini_out.open(opts.mini.c_str());
         if (!mini_out.is_open()) throw std::runtime_error("unable to open --mini file '" + opts.mini + "' for writing");
         if (opts.mini_window < 0 && !opts.estimate) (void)mini_mean_window(libs);
+    }
+    if (!opts.anchor.empty()) {
+        anchor_out.open(opts.anchor.c_str());
+        if (!anchor_out.is_open()) throw std::runtime_error("unable to open --anchor file '" + opts.anchor + "' for writing");
+        if (opts.anchor_window < 0 && !opts.estimate) (void)anchor_default_window(libs);
     }
 }
 

@@ -1,5 +1,5 @@
 // What a run is given, settled before the GPU is touched: the BDX_* environment knobs, the options (or the -R cache's), the
-// configuration, and the opened or parsed option inputs (--vcf, --exclude, --sites, --ci, --mapq, --estimate-config, --mini).  bdx-dump-reads shares the two helpers.
+// configuration, and the opened or parsed option inputs (--vcf, --exclude, --sites, --ci, --mapq, --estimate-config, --mini, --anchor).  bdx-dump-reads shares the two helpers.
 #pragma once
 #include <cstdint>
 #include <fstream>
@@ -58,7 +58,7 @@ Env read_env();
 
 struct Inputs {
     // Fails in this order, each before the GPU is touched: option parsing, -R / config, (no BAM files: see no_bams), --vcf open, --exclude
-    // parse, --sites-vcf open and --sites parse, --ci window, --mapq window, --estimate-config open, --mini open and window.
+    // parse, --sites-vcf open and --sites parse, --ci window, --mapq window, --estimate-config open, --mini open and window, --anchor open and window.
     Inputs(int argc, char** argv, const Env& env);
     Inputs(const Inputs&) = delete;
     Inputs& operator=(const Inputs&) = delete;
@@ -87,6 +87,9 @@ struct Inputs {
 
     std::ofstream mini_out;          // --mini: opened at once -- an unwritable path fails here; without --mini-window (and without --estimate,
                                      // which brings means of its own) a configuration with no finite positive mean insert size fails here too
+
+    std::ofstream anchor_out;        // --anchor: opened at once, likewise; without --anchor-window (and without --estimate, which brings cutoffs of
+                                     // its own) a configuration with no finite positive uppercutoff fails here too
 
     // --estimate, the one change a run makes to its inputs (between "fed" and "run"): the estimated values replace the configuration's in
     // cfg and libs, so that everything behind the feed prints and uses the run's libraries; the windows of --sites / --ci / --mapq / --clip that

@@ -77,6 +77,7 @@ int run(int argc, char** argv, const Env& env) {
         // (--vcf: the junction counts run before the trimmer starts, which must not run beside another call on the context)
         Genotypes gt = count_on_store(in, env, s, fed, calls);
         call_mini(in, env, s, fed);
+        call_anchor(in, env, s, fed);
         // (a large run's pinned result tables go back while the table is printed: the process's end is that much shorter.  BDX_TRIM=0: kept)
         if (fed.n_reads > (size_t)(8u << 20) && !in.want_dumps && !env.clean_exit && !env.keep_results) s.start_trimmer();
         Support sup = fetch_support(in, s, fed, calls);

@@ -84,6 +84,11 @@ void print_usage(const bdx_opts& o) {
     fprintf(stderr, "       --mini-step INT    the distance between the starts of two windows [half the window]\n");
     fprintf(stderr, "       --mini-min-pairs INT   the pairs of one library a window needs to be tested [%d]\n", Options::kMiniMinPairsDefault);
     fprintf(stderr, "       --mini-score INT   the score a window must reach [20 + 10 log10 of the number of tested windows]\n");
+    fprintf(stderr, "       --anchor FILE  insertions longer than the fragment: windows where reads whose mate is unmapped pile up on both sides of a position, written to FILE\n");
+    fprintf(stderr, "       --anchor-window INT  the window's width, 1 to 2^30 [twice the largest library uppercutoff]\n");
+    fprintf(stderr, "       --anchor-step INT    the distance between the starts of two windows, 1 to 2^30 [half the window]\n");
+    fprintf(stderr, "       --anchor-min INT     the distinct read starts a call needs on either side, 1 to 2^30 [%d]\n", Options::kAnchorMinDefault);
+    fprintf(stderr, "       --anchor-mapq INT    the quality an anchoring read needs, 0 to 255 [above its library's minimum]\n");
     fprintf(stderr, "\n");
 }
 
@@ -99,7 +104,7 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     bdx_opts_default(&o);
     const std::string spec = getopt_string();
     // (the reference's letters parse exactly as with getopt; the long options are this tool's own)
-    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank, kMapq, kMapqWindow, kEstimate, kEstimateConfig, kMini, kMiniWindow, kMiniStep, kMiniMinPairs, kMiniScore, kClip, kClipWindow, kClipMin, kClipSupport };
+    enum { kVcf = 256, kExclude, kSites, kSitesVcf, kSitesWindow, kMarkDup, kCi, kCiWindow, kDepth, kDepthFlank, kMapq, kMapqWindow, kEstimate, kEstimateConfig, kMini, kMiniWindow, kMiniStep, kMiniMinPairs, kMiniScore, kClip, kClipWindow, kClipMin, kClipSupport, kAnchor, kAnchorWindow, kAnchorStep, kAnchorMin, kAnchorMapq };
     static const struct option kLong[] = {{"vcf", required_argument, nullptr, kVcf}, {"exclude", required_argument, nullptr, kExclude},
                                          {"sites", required_argument, nullptr, kSites}, {"sites-vcf", required_argument, nullptr, kSitesVcf},
                                          {"sites-window", required_argument, nullptr, kSitesWindow}, {"mark-dup", no_argument, nullptr, kMarkDup},
@@ -112,6 +117,9 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
                                          {"mini-score", required_argument, nullptr, kMiniScore},
                                          {"clip", no_argument, nullptr, kClip}, {"clip-window", required_argument, nullptr, kClipWindow},
                                          {"clip-min", required_argument, nullptr, kClipMin}, {"clip-support", required_argument, nullptr, kClipSupport},
+                                         {"anchor", required_argument, nullptr, kAnchor}, {"anchor-window", required_argument, nullptr, kAnchorWindow},
+                                         {"anchor-step", required_argument, nullptr, kAnchorStep}, {"anchor-min", required_argument, nullptr, kAnchorMin},
+                                         {"anchor-mapq", required_argument, nullptr, kAnchorMapq},
                                          {nullptr, 0, nullptr, 0}};
     int c;
     while ((c = getopt_long(argc, argv, spec.c_str(), kLong, nullptr)) >= 0) {
@@ -187,6 +195,22 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
             (c == kMiniWindow ? mini_window : c == kMiniStep ? mini_step : c == kMiniMinPairs ? mini_min_pairs : mini_score) = (int)v;
             continue;
         }
+        if (c == kAnchor) {
+            anchor = optarg;
+            continue;
+        }
+        if (c == kAnchorWindow || c == kAnchorStep || c == kAnchorMin || c == kAnchorMapq) {
+            const long lo = c == kAnchorMapq ? 0 : 1, hi = c == kAnchorMapq ? 255 : (1L << 30);
+            const char* name = c == kAnchorWindow ? "window" : c == kAnchorStep ? "step" : c == kAnchorMin ? "min" : "mapq";
+            char* end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (end == optarg || *end || v < lo || v > hi) {
+                fprintf(stderr, "--anchor-%s takes an integer from %ld to %ld, not '%s'.\n", name, lo, hi, optarg);
+                exit(1);
+            }
+            (c == kAnchorWindow ? anchor_window : c == kAnchorStep ? anchor_step : c == kAnchorMin ? anchor_min : anchor_mapq) = (int)v;
+            continue;
+        }
         if (c == kDepthFlank) {
             char* end = nullptr;
             const long v = strtol(optarg, &end, 10);
@@ -252,6 +276,10 @@ Options::Options(int argc, char** argv) : orig_argv(argv, argv + argc) {
     }
     if (mini.empty() && (mini_window >= 0 || mini_step >= 0 || mini_min_pairs >= 0 || mini_score >= 0)) {
         fprintf(stderr, "--mini-window, --mini-step, --mini-min-pairs and --mini-score go with --mini FILE.\n");
+        exit(1);
+    }
+    if (anchor.empty() && (anchor_window >= 0 || anchor_step >= 0 || anchor_min >= 0 || anchor_mapq >= 0)) {
+        fprintf(stderr, "--anchor-window, --anchor-step, --anchor-min and --anchor-mapq go with --anchor FILE.\n");
         exit(1);
     }
     if (!estimate && !estimate_config.empty()) {

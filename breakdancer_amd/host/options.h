@@ -1,6 +1,7 @@
 // Command line of breakdancer-max: same getopt string, defaults and usage text as the reference
 // (common/Options.cpp:27-122), -C / -R (the pass-1 cache, cache.h) included, plus the long options --vcf, --exclude, --sites / --sites-vcf /
-// --sites-window, --mark-dup, --ci / --ci-window, --depth / --depth-flank, --mapq / --mapq-window, --clip / --clip-window / --clip-min / --clip-support, --estimate / --estimate-config and --mini / --mini-window / --mini-step / --mini-min-pairs / --mini-score.
+// --sites-window, --mark-dup, --ci / --ci-window, --depth / --depth-flank, --mapq / --mapq-window, --clip / --clip-window / --clip-min / --clip-support, --estimate / --estimate-config, --mini / --mini-window / --mini-step / --mini-min-pairs / --mini-score and
+// --anchor / --anchor-window / --anchor-step / --anchor-min / --anchor-mapq.
 #pragma once
 #include <string>
 #include <vector>
@@ -36,6 +37,12 @@ struct Options {
     int mini_min_pairs = -1;     // --mini-min-pairs: the pairs of one library a window needs for its row to score (-1: kMiniMinPairsDefault)
     int mini_score = -1;         // --mini-score: the score a window must reach (-1: from the number of scoring windows)
     static constexpr int kMiniMinPairsDefault = 20;
+    std::string anchor;          // --anchor: insertion sites from clusters of reads whose mate is unmapped, written to this file (anchor.h)
+    int anchor_window = -1;      // --anchor-window: the window's width (-1: twice the ceiling of the largest finite library uppercutoff)
+    int anchor_step = -1;        // --anchor-step: the distance between two windows' starts (-1: half the window)
+    int anchor_min = -1;         // --anchor-min: the distinct starts a call needs on either side (-1: kAnchorMinDefault)
+    int anchor_mapq = -1;        // --anchor-mapq: bdx_window_anchor_split's min_qual, 0 .. 255 (-1: the libraries' own minima)
+    static constexpr int kAnchorMinDefault = 3;
     static constexpr int kDepthFlankDefault = 1000;
     bool clip = false;           // --clip: CLN / CLPOS / CLSUP / CLSIDE of every --vcf / --sites-vcf record: the piles of clipped reads at either end (bdx_site_clip_peaks)
     int clip_window = -1;        // --clip-window: how far from a breakpoint a clip may stand, 0 .. BDX_CLIP_WINDOW_MAX (-1: from the libraries' cutoffs, at most that)

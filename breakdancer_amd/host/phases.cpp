@@ -8,6 +8,7 @@
 #include <iostream>
 #include <stdexcept>
 
+#include "anchor.h"
 #include "mini.h"
 #include "store_counts.h"
 
@@ -460,6 +461,79 @@ void call_mini(Inputs& in, const Env& env, const Session& s, const Fed& fed) {
         fprintf(stderr, "[bdx timing] --mini: %llu windows (window %lld, step %lld), %llu scoring, %llu saturated, %zu calls, threshold %d; histogram %.4f s, kernel calls %.4f s, host %.4f s\n",
                 (unsigned long long)windows, (long long)p.window, (long long)p.step, (unsigned long long)scoring, (unsigned long long)saturated, calls.size(), threshold,
                 secs(t0, t1), t_gpu, secs(t1, now()) - t_gpu);
+}
+
+// --anchor: behind the run and behind --mini -- the grid windows of every sequence the run read go to the GPU in batches (KA), the windows
+// that call are merged and written (anchor.h).  The rule does not look at BDX_CLS_PASS, so -t changes nothing here
+void call_anchor(Inputs& in, const Env& env, const Session& s, const Fed& fed) {
+    if (in.opts.anchor.empty()) return;
+    const Options& opts = in.opts;
+    const auto t0 = now();
+    const int only_tid = opts.chr.empty() ? -1 : region_tid(in.header.names(), opts.chr);
+    const RunContexts rc{s.ctx, s.ranks, fed.rank_of, only_tid};
+    AnchorParams p;
+    p.window = opts.anchor_window > 0 ? opts.anchor_window : anchor_default_window(in.libs);
+    p.step = opts.anchor_step > 0 ? opts.anchor_step : anchor_default_step(p.window);
+    p.min = opts.anchor_min > 0 ? opts.anchor_min : Options::kAnchorMinDefault;
+    p.mapq = opts.anchor_mapq;
+    // (every `tile`-th window, when the step divides the window: those windows cut the sequence without overlap, so their sums count a record once)
+    const uint64_t tile = p.window % p.step == 0 ? (uint64_t)(p.window / p.step) : 0;
+    double t_gpu = 0;
+    // (a sequence is taken to end at 2^31 - 2 at the latest, as --mini takes it)
+    std::vector<uint32_t> lengths = in.header.lengths();
+    for (uint32_t& l : lengths) l = std::min<uint32_t>(l, 2147483646u);
+    const size_t batch = (size_t)1 << 22;
+    std::vector<AnchorCall> called;
+    uint64_t windows = 0, candidates = 0, anchors = 0, any_candidate = 0, any_anchor = 0;
+    std::vector<bdx_interval> iv;
+    std::vector<std::pair<int32_t, uint64_t>> which;
+    std::vector<bdx_anchor_split> rows;
+    auto flush = [&] {
+        if (iv.empty()) return;
+        const auto tg = now();
+        window_anchor_split(rc, iv, p.mapq, rows);
+        t_gpu += secs(tg, now());
+        for (size_t i = 0; i < iv.size(); ++i) {
+            const bdx_anchor_split& r = rows[i];
+            const uint64_t a = (uint64_t)r.n_fwd + r.n_rev;
+            any_candidate += a + r.n_low;
+            any_anchor += a;
+            if (tile && which[i].second % tile == 0) { candidates += a + r.n_low; anchors += a; }
+            if (anchor_calls(r, p.min)) called.push_back(AnchorCall{which[i].first, r, 1});
+        }
+        windows += iv.size();
+        iv.clear();
+        which.clear();
+    };
+    for (size_t t = 0; t < lengths.size(); ++t) {
+        if (!rc.held((int)t)) continue;
+        const int64_t len = lengths[t];
+        const uint64_t nw = mini_grid((uint64_t)len, p.step);
+        for (uint64_t j = 0; j < nw; ++j) {
+            const int64_t beg = (int64_t)j * p.step;
+            iv.push_back(bdx_interval{(int32_t)t, (int32_t)beg, (int32_t)std::min<int64_t>(beg + p.window, len)});
+            which.emplace_back((int32_t)t, j);
+            if (iv.size() == batch) flush();
+        }
+    }
+    flush();
+    if (any_candidate && !any_anchor)
+        fprintf(stderr, "WARNING: --anchor: the run holds reads whose mate is unmapped, and none passes the quality test.  The store keeps the AM tag where "
+                        "the aligner wrote one, the smaller quality of the two mates, which is 0 for these reads: give --anchor-mapq 0\n");
+    const std::vector<AnchorCall> calls = anchor_merge(std::move(called));
+    std::ofstream& out = in.anchor_out;
+    out << "#Software: breakdancer-max --anchor\n#Command: ";
+    for (auto const& a : opts.orig_argv) out << a << " ";
+    out << "\n#Window: " << p.window << "\n#Step: " << p.step << "\n#Min: " << p.min << "\n#Mapq: " << p.mapq << "\n";
+    anchor_write_table(out, calls, in.header.names());
+    out.close();
+    if (out.fail()) throw std::runtime_error("unable to write --anchor file '" + opts.anchor + "'");
+    if (env.timing) {
+        char seen[96] = "";
+        if (tile) snprintf(seen, sizeof seen, " %llu candidates, %llu anchors,", (unsigned long long)candidates, (unsigned long long)anchors);
+        fprintf(stderr, "[bdx timing] --anchor: %llu windows (window %lld, step %lld),%s %zu calls; kernel calls %.4f s, host %.4f s\n", (unsigned long long)windows,
+                (long long)p.window, (long long)p.step, seen, calls.size(), t_gpu, secs(t0, now()) - t_gpu);
+    }
 }
 
 // supporting reads of the printed SVs: a second decode pass fetches just those records (the reference keeps

@@ -77,6 +77,10 @@ Genotypes count_on_store(const Inputs& in, const Env& env, const Session& s, con
 // count_on_store it runs before the trimmer starts
 void call_mini(Inputs& in, const Env& env, const Session& s, const Fed& fed);
 
+// --anchor: the windowed split of the one-end-anchored reads the run holds, written to the file the inputs opened (anchor.h).  Behind
+// call_mini, before the trimmer starts
+void call_anchor(Inputs& in, const Env& env, const Session& s, const Fed& fed);
+
 // -g / -d: the supporting reads of the printed SVs and the opened dump files
 struct Support {
     std::vector<uint32_t> off;

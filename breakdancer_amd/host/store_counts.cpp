@@ -374,4 +374,16 @@ void window_insert_shift(const RunContexts& rc, const std::vector<bdx_interval>&
     });
 }
 
+void window_anchor_split(const RunContexts& rc, const std::vector<bdx_interval>& iv, int32_t min_qual, std::vector<bdx_anchor_split>& rows) {
+    if (iv.size() > ((size_t)1 << 22)) throw std::runtime_error("window_anchor_split: more than 2^22 windows in one call");
+    std::vector<int32_t> q_tid(iv.size());
+    for (size_t i = 0; i < iv.size(); ++i) q_tid[i] = iv[i].tid;
+    count_on_ranks(rc, q_tid, 1, "bdx_window_anchor_split", rows, [&](bdx_ctx* c, const std::vector<size_t>& m, bdx_anchor_split* out) {
+        if (m.size() == iv.size()) return bdx_window_anchor_split(c, iv.data(), iv.size(), min_qual, out);   // (the single context: all of them, in order)
+        std::vector<bdx_interval> mine(m.size());
+        for (size_t j = 0; j < m.size(); ++j) mine[j] = iv[m[j]];
+        return bdx_window_anchor_split(c, mine.data(), m.size(), min_qual, out);
+    });
+}
+
 }  // namespace bdhost

@@ -1,4 +1,4 @@
-// --vcf / --sites / --ci / --depth / --mapq / --mini: the counts over the records a finished run holds on the GPU (K8, KS, KI, KR, KM of include/bdx.h), turned into the
+// --vcf / --sites / --ci / --depth / --mapq / --mini / --anchor: the counts over the records a finished run holds on the GPU (K8, KS, KI, KR, KM, KW, KA of include/bdx.h), turned into the
 // records VcfWriter prints (vcf.h).
 #pragma once
 #include <cstdint>
@@ -53,6 +53,10 @@ void fill_depth(const Options& opts, const RunContexts& rc, int32_t flank, const
 void store_insert_histogram(const RunContexts& rc, size_t nlibs, std::vector<uint64_t>& hist);
 void set_insert_null(const RunContexts& rc, const uint64_t* hist);
 void window_insert_shift(const RunContexts& rc, const std::vector<bdx_interval>& iv, size_t nlibs, std::vector<bdx_insert_shift>& rows);
+
+// --anchor: the rows [windows] of bdx_window_anchor_split (KA), each window answered by the rank that holds its sequence (every iv[i].tid is
+// a sequence the run holds); at most 2^22 windows per call (160 MiB of rows)
+void window_anchor_split(const RunContexts& rc, const std::vector<bdx_interval>& iv, int32_t min_qual, std::vector<bdx_anchor_split>& rows);
 
 // How far a supporting mate can start from a breakpoint it brackets: the ceiling of the largest finite library uppercutoff, the window
 // of --sites, --ci and --mapq when theirs is not given.

@@ -774,6 +774,45 @@ int bdx_set_insert_null(bdx_ctx* ctx, const uint64_t* hist /*[nlibs][BDX_ISIZE_B
 int bdx_window_insert_shift(bdx_ctx* ctx, const bdx_interval* iv, size_t n, bdx_insert_shift* out /*[n][nlibs]*/);
 int bdx_insert_shift_score(const bdx_insert_shift* row, uint64_t N, double* score, double* D);
 
+/* One-end-anchored reads inside given windows and the position that best splits them: no counterpart in the C++ reference.  An insertion
+ * longer than the fragment (novel sequence, a mobile element, a viral integration) leaves no anomalous pair: its only trace is reads whose
+ * mates fell into the inserted sequence and did not map -- those on the forward strand pile up left of the junction, those on the reverse
+ * strand right of it (the anchor step of NovelSeq, MELT and Pindel; the CLI's --anchor).  The rule, written down here once:
+ *   CANDIDATE    record i of the resident store is a candidate for interval (tid, [beg, end)) -- 0-based, half-open, bdx_interval as
+ *                everywhere -- when tid[i] == tid, beg <= pos[i] < end and cls[i] == BDX_MATE_UNMAPPED, the whole byte: the classifier
+ *                writes 9 exactly for a paired record without 0x400, itself mapped (0x4 clear) with its mate unmapped (0x8 set), and such
+ *                a record never carries BDX_CLS_PASS.  A duplicate flag the BAM carries is honoured that way; bdx_set_mark_duplicates never
+ *                marks these records (its candidates need a mapped mate), which is why the row reports distinct starts.  The unmapped mate's
+ *                own record is class BDX_UNMAPPED and no candidate.
+ *   ANCHOR       a candidate whose quality (the store's one quality per record: the AM tag where the aligner wrote one, else MAPQ) passes:
+ *                min_qual < 0: quality > its library's minimum as the classifier resolved it (bdx_site_end_quality's test; the library
+ *                index resolves as everywhere: out of range is library 0); min_qual >= 0: quality >= min_qual, for every library.  A
+ *                candidate that fails counts in n_low and nowhere else.
+ *   DIRECTION    an anchor points right when flag & 0x10 is clear, left when it is set; with opts.illumina_long_insert (-l) the other way
+ *                round, exactly as bdx_site_breakpoint_bounds inverts strands.
+ *   SPLIT        for an integer S in [beg, end]: A(S) = the right-pointing anchors with pos < S, B(S) = the left-pointing anchors with
+ *                pos >= S.  split = the smallest S that maximises A(S) + B(S); n_left = A(split), n_right = B(split); u_left / u_right =
+ *                the distinct pos among those; last_left = the largest pos of a right-pointing anchor with pos < split, first_right = the
+ *                smallest pos of a left-pointing anchor with pos >= split, -1 where there is none.  n_fwd / n_rev = all anchors of the
+ *                window by direction.  So: no anchor, or n_left == 0, gives split == beg; n_left > 0 gives split == last_left + 1.  The rule
+ *                speaks of positions, never of indices: records of equal pos give the same row in any store order.  Everything is an exact
+ *                integer, positions in 64-bit arithmetic (end may be 2^31 - 1).  An empty interval (end == beg) gives zeros, split = beg,
+ *                last_left = first_right = -1, as does a tid the context holds nothing of.
+ * bdx_window_anchor_split (KA, csrc/ka_anchor.hip): state, errors and their order are those of bdx_window_insert_shift without its null --
+ * BDX_ESTATE before a run has classified the reads the context holds or while a sizing pass is in flight; n == 0 is BDX_OK; BDX_EINVAL for
+ * a null array with n > 0, min_qual outside -1..255, tid < 0, beg < 0 or end < beg; BDX_ELIMIT above 2^31 intervals.  After bdx_run, or
+ * on a rank's context (bdx_dist_chromosome) after bdx_dist_run.  Not beside another call on the same context. */
+typedef struct bdx_anchor_split {
+    uint32_t n_fwd, n_rev;      /* anchors in the window pointing right / pointing left */
+    uint32_t n_low;             /* class-9 records in the window that fail the quality test */
+    uint32_t n_left, n_right;   /* A(split), B(split) */
+    uint32_t u_left, u_right;   /* distinct pos among those */
+    int32_t  split;             /* 0-based: the first position right of the split */
+    int32_t  last_left;         /* largest pos of a right-pointing anchor with pos < split; -1: none */
+    int32_t  first_right;       /* smallest pos of a left-pointing anchor with pos >= split; -1: none */
+} bdx_anchor_split;             /* 40 bytes, 4-aligned */
+int bdx_window_anchor_split(bdx_ctx* ctx, const bdx_interval* iv, size_t n, int32_t min_qual, bdx_anchor_split* out /*[n]*/);
+
 /* device the context is bound to and the HIP stream it launches on (as void*), for callers that time it */
 int bdx_device(const bdx_ctx* ctx);
 void* bdx_stream(const bdx_ctx* ctx);
